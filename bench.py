@@ -31,10 +31,15 @@ all_gather_into_tensor of the pixels on device tensors at the end of every step,
 the code path of the N > 1 runs on a box with one GPU.  Default "auto": collectives only when N > 1.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel - the fine render pass (192 samples/ray) -
-timed with events on the launch stream inside the timed region; `cpu_baseline` is the CPU oracle
-(oracle/nerf_oracle.py, kind "port") on the host cores (N = 1 only); `extra.configs` (N = 1 only, measured AFTER and
-outside the headline's timed region) carries the other configs and the training step with their own roofline
-fractions, so that every number DESIGN.md quotes sits in a driver-run record."""
+timed with events on the launch stream inside the timed region.  A plain run stops there: set-up, warm-up, the timed
+steps, the optional output dump, the line.  --full adds, after the timed region: `cpu_baseline`, the CPU oracle
+(oracle/nerf_oracle.py, kind "port") on the host cores (N = 1 only), and `extra.configs` (N = 1 only) with the other
+configs and the training step with their own roofline fractions plus `extra.satellites`, so that every number
+DESIGN.md quotes sits in a driver-run record.
+
+--dump-outputs DIR: after the timed steps, the arrays the timed path returned in its LAST step (rgb, disp, acc and, for
+render(), its extras) as DIR/<name>.npy in float32 (at most 64 MB in all: a seeded row sample of anything larger).
+Everything is seeded, so two runs with the same arguments see the same inputs."""
 import argparse
 import json
 import os
@@ -81,8 +86,12 @@ def parse_args():
                     help="C2 (default): the headline; train: the reference's TRAINING step on the C2 shape (not the BASELINE metric)")
     ap.add_argument("--collective", choices=["auto", "always"], default="auto",
                     help="always: also at N = 1 join an RCCL group (world 1) and end every step with the real all-gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra.configs block")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the CPU baseline and the extra.configs / extra.satellites blocks")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra.configs block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays of the last timed step as DIR/<name>.npy (float32, <= 64 MB in all)")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "bf16x3-fine"], default="fp32",
                     help="arithmetic of the fused passes; fp32 (default) is the metric BASELINE.json names and the only one the "
                          "driver measures - the others are the opt-in bf16x3 paths (DESIGN.md 7c), labelled as such in the line")
@@ -90,7 +99,35 @@ def parse_args():
     ds, dw = DEFAULT_STEPS[args.config]
     args.steps = ds if args.steps is None else args.steps
     args.warmup = dw if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra = True
     return args
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> tensor of the last timed step.  Written as float32 (float64 stays float64); if the total exceeds
+    DUMP_LIMIT_BYTES every array keeps the same seeded sample of its leading rows (np.random.default_rng(0))."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = max(a.shape[0] for a in host.values())
+        keep = int(n * DUMP_LIMIT_BYTES / total)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        host = {k: (a[rows[rows < a.shape[0]]] if a.ndim else a) for k, a in host.items()}
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] wrote {len(host)} arrays ({sum(a.nbytes for a in host.values()) / 2 ** 20:.2f} MB) to {path}",
+          file=sys.stderr, flush=True)
 
 
 def host_cores():
@@ -526,6 +563,7 @@ def worker(args):
         dist.barrier()
     from swnerf import synth, render, parallel
     render.set_precision(args.precision)
+    torch.manual_seed(0)                                 # perturb=1 (train) draws torch.rand: same inputs run to run
     x3 = args.precision != "fp32"
 
     cfg = args.config
@@ -544,6 +582,8 @@ def worker(args):
     render.PASS_HOOK = hook
 
     pending = []                                         # all-gathers in flight: (work, out)
+    last = {}                                            # --dump-outputs: render()'s extras of the latest step
+    keep_extras = args.dump_outputs is not None
 
     def gather(px):
         """The step's collective, issued asynchronously: the all-gather of this step's pixels is enqueued behind the render
@@ -570,7 +610,9 @@ def worker(args):
         n_local, rays_per_step, scaling = N_RAND, world * N_RAND, "weak"
 
         def local():                                     # this rank's part of a step: no collective
-            rgb, disp, acc, _ = render.render(H, W, K, chunk=1024 * 32, rays=(rays_o, rays_d), **kw)
+            rgb, disp, acc, ex = render.render(H, W, K, chunk=1024 * 32, rays=(rays_o, rays_d), **kw)
+            if keep_extras:
+                last["extras"] = ex
             return torch.cat([rgb, disp[:, None], acc[:, None]], -1)
         if train:
             # the reference's training step; every rank draws its own batch (seed 2 + rank), gradients are averaged
@@ -585,6 +627,8 @@ def worker(args):
             def local():
                 with torch.enable_grad():
                     rgb, disp, acc, ex = render.render(H, W, K, chunk=1024 * 32, rays=(rays_o, rays_d), **kwt)
+                    if keep_extras:
+                        last["extras"] = {k: v.detach() for k, v in ex.items() if torch.is_tensor(v)}
                     loss = torch.mean((rgb - tgt) ** 2) + torch.mean((ex['rgb0'] - tgt) ** 2)
                     bucket.zero()
                     loss.backward()
@@ -640,6 +684,10 @@ def worker(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert out.shape == ((n_local if train else rays_per_step), 5) and bool(torch.isfinite(out[:, :3]).all())
+    if rank == 0 and args.dump_outputs is not None:
+        arrays = {"rgb": out[:, :3], "disp": out[:, 3], "acc": out[:, 4]}
+        arrays.update({k: v for k, v in last.get("extras", {}).items() if torch.is_tensor(v)})
+        dump_outputs(args.dump_outputs, arrays)
 
     ms_kernel = [fine_events[i].elapsed_time(fine_events[i + 1]) for i in range(0, len(fine_events), 2)]
     fine_ms = float(np.mean(ms_kernel)) if ms_kernel else float("nan")

@@ -1,6 +1,5 @@
 """reference-format checkpoints load into the swnerf modules (and back)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -9,7 +8,6 @@ import torch
 import cases
 from swnerf import checkpoint, model, synth
 
-REF = "/root/reference"
 
 
 def _nets():
@@ -45,42 +43,42 @@ def test_roundtrip_and_discovery(tmp_path):
     assert checkpoint.load_checkpoint(str(tmp_path / "legacy.tar"), c, d, opt2) == 7
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
-def test_checkpoint_written_by_the_reference_classes_loads(tmp_path):
-    """A .tar written exactly as nerf/run.py:716-724 does, from the reference's own nn.Modules."""
-    sys.dont_write_bytecode = True
-    saved = sys.modules.pop("model", None)
-    sys.path.insert(0, REF)
-    try:
-        import importlib
-        refmodel = importlib.import_module("model")
-    finally:
-        sys.path.remove(REF)
-        sys.modules.pop("model", None)
-        if saved is not None:
-            sys.modules["model"] = saved
+def _reference_state_dict(golden, tag, values):
+    """A state_dict laid out as the reference's nn.Module writes it (key order and shapes captured from the reference's
+    own modules: tests/golden/make_golden_runners.py), filled with `values`."""
+    from collections import OrderedDict
+    keys = [str(k) for k in golden[f"ckpt_{tag}_keys"]]
+    assert sorted(keys) == sorted(values.keys())
+    sd = OrderedDict()
+    for k, shape in zip(keys, golden[f"ckpt_{tag}_shapes"].tolist()):
+        v = torch.from_numpy(values[k].copy())
+        assert list(v.shape) == [n for n in shape if n >= 0], k
+        sd[k] = v
+    return sd
+
+
+def test_checkpoint_written_by_the_reference_classes_loads(golden, tmp_path):
+    """A .tar written exactly as nerf/run.py:716-724 does, with the state_dict layout of the reference's own nn.Modules
+    (g13_runners.npz)."""
+    g = golden("g13_runners")
     sd_c, sd_f = cases.weights_static()
-    nets = []
-    for sd in (sd_c, sd_f):
-        m = refmodel.vallina_NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=5, skips=[4], use_viewdirs=True)
-        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-        nets.append(m)
-    opt = torch.optim.Adam(params=list(nets[0].parameters()) + list(nets[1].parameters()), lr=5e-4, betas=(0.9, 0.999))
+    sds = [_reference_state_dict(g, "static", sd) for sd in (sd_c, sd_f)]
+    params = [torch.nn.Parameter(v.clone()) for sd in sds for v in sd.values()]
+    opt = torch.optim.Adam(params=params, lr=5e-4, betas=(0.9, 0.999))
     path = tmp_path / "200000.tar"
-    torch.save({'global_step': 200000, 'network_fn_state_dict': nets[0].state_dict(),
-                'network_fine_state_dict': nets[1].state_dict(), 'optimizer_state_dict': opt.state_dict()}, path)
+    torch.save({'global_step': 200000, 'network_fn_state_dict': sds[0],
+                'network_fine_state_dict': sds[1], 'optimizer_state_dict': opt.state_dict()}, path)
     a, b = _nets()
     assert checkpoint.load_checkpoint(str(path), a, b) == 200000
     for ours, sd in ((a, sd_c), (b, sd_f)):
         got = ours.state_dict()
         assert list(got.keys()) == list(sd.keys()) and all(np.array_equal(got[k].numpy(), sd[k]) for k in sd)
-    dn = refmodel.NeRF.get_by_name("direct_temporal", D=8, W=256, input_ch=63, output_ch=5, skips=[4], input_ch_views=27,
-                                   input_ch_time=21, use_viewdirs=True, embed_fn=None, zero_canonical=True)
-    dn.load_state_dict({k: torch.from_numpy(v) for k, v in cases.weights_dnerf().items()})
     path = tmp_path / "800000.tar"
-    torch.save({'global_step': 800000, 'network_fn_state_dict': dn.state_dict(), 'optimizer_state_dict': {}}, path)   # run_dnerf.py:757-770
+    torch.save({'global_step': 800000, 'network_fn_state_dict': _reference_state_dict(g, "dnerf", cases.weights_dnerf()),
+                'optimizer_state_dict': {}}, path)   # run_dnerf.py:757-770
     ours = model.DirectTemporalNeRF(D=8, W=256, input_ch=63, input_ch_views=27, input_ch_time=21, skips=[4], use_viewdirs=True)
     assert checkpoint.load_checkpoint(str(path), ours) == 800000
+    assert list(ours.state_dict().keys()) == [str(k) for k in g["ckpt_dnerf_keys"]]
     assert all(np.array_equal(ours.state_dict()[k].numpy(), v) for k, v in cases.weights_dnerf().items())
 
 

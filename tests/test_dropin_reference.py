@@ -1,97 +1,91 @@
-"""INTEGRATION.md, checked against the real runners (build container only: skipped where
-/root/reference does not exist, e.g. on the GPU box).  Imports nerf/run.py and
-d_nerf/run_dnerf.py with sw-nerf_amd/dropin first on sys.path, so their star-imports resolve to this
-build, then runs the reference's OWN create_nerf and checks that its network_query_fn lambda is
-recognised by the fused dispatch.  Nothing is executed on a device."""
+"""INTEGRATION.md, checked against what the real runners see.  tests/golden/g13_runners.npz (make_golden_runners.py)
+holds what nerf/run.py and d_nerf/run_dnerf.py reach through their star-imports, the parameter lists of their
+render_rays / render / run_network, and what their OWN create_nerf returned when they were loaded with
+sw-nerf_amd/dropin first on sys.path (key order, counts, the fused plan of their network_query_fn lambda).
+Here the drop-in modules must supply every one of those names as this build's objects, and this build's
+create_nerf / create_dnerf must return the same.  Nothing is executed on a device."""
 import importlib.util
+import inspect
 import os
-import sys
-import types
 from argparse import Namespace
 
 import pytest
 
-REF = "/root/reference"
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+DROPIN = os.path.join(ROOT, "sw-nerf_amd", "dropin")
+NOT_PROVIDED = {"TNeRF"}         # dropin/model.py: T-NeRF is out of scope
+ARGS = dict(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=128, netdepth=8, netwidth=256,
+            netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, ft_path=None, no_reload=True, perturb=1.,
+            N_samples=64, white_bkgd=True, raw_noise_std=0., dataset_type="blender", no_ndc=False, lindisp=False)
 
 
-def _load_runner(rel, name):
-    sys.dont_write_bytecode = True
-    for mod in ["imageio", "lpips", "skimage", "skimage.metrics", "cv2", "configargparse", "torch.utils.tensorboard"]:
-        try:
-            importlib.import_module(mod)
-        except Exception:
-            sys.modules[mod] = types.ModuleType(mod)
-    for attr in ("peak_signal_noise_ratio", "structural_similarity"):
-        if not hasattr(sys.modules["skimage.metrics"], attr):
-            setattr(sys.modules["skimage.metrics"], attr, None)
-    if not hasattr(sys.modules["torch.utils.tensorboard"], "SummaryWriter"):
-        sys.modules["torch.utils.tensorboard"].SummaryWriter = object
-    os.environ.setdefault("MPLBACKEND", "Agg")
-    dropin = os.path.join(ROOT, "sw-nerf_amd", "dropin")
-    saved = list(sys.path)
-    saved_mods = {k: sys.modules.pop(k) for k in ("ray", "embedder", "model", "utils") if k in sys.modules}
-    sys.path[:0] = [dropin, os.path.join(REF, os.path.dirname(rel)), REF]
-    try:
-        spec = importlib.util.spec_from_file_location(name, os.path.join(REF, rel))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        sys.path[:] = saved
-        for k in ("ray", "embedder", "model", "utils"):
-            sys.modules.pop(k, None)
-        sys.modules.update(saved_mods)
+@pytest.fixture(scope="module")
+def runners():
+    import numpy as np
+    import cases
+    with np.load(os.path.join(cases.GOLDEN_DIR, "g13_runners.npz"), allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _dropin(name):
+    spec = importlib.util.spec_from_file_location(f"swnerf_dropin_{name}", os.path.join(DROPIN, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
     return mod
 
 
-def test_static_runner_resolves_to_this_build(tmp_path):
-    import swnerf.ray, swnerf.embedder, swnerf.model, swnerf.render
-    run = _load_runner("nerf/run.py", "ref_run_dropin")
-    assert run.get_rays is swnerf.ray.get_rays and run.raw2outputs is swnerf.ray.raw2outputs
-    assert run.sample_pdf is swnerf.ray.sample_pdf and run.ndc_rays is swnerf.ray.ndc_rays
-    assert run.get_embedder is swnerf.embedder.get_embedder
-    assert run.NeRF is swnerf.model.vallina_NeRF                      # `from model import vallina_NeRF as NeRF`
-    args = Namespace(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=128, netdepth=8,
-                     netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4,
-                     basedir=str(tmp_path), expname="x", ft_path=None, no_reload=True, perturb=1., N_samples=64,
-                     white_bkgd=True, raw_noise_std=0., dataset_type="blender", no_ndc=False, lindisp=False)
-    os.makedirs(tmp_path / "x")
-    kw_train, kw_test, start, grad_vars, opt = run.create_nerf(args)
-    assert isinstance(kw_test["network_fn"], swnerf.model.vallina_NeRF) and isinstance(kw_test["network_fine"], swnerf.model.vallina_NeRF)
-    assert len(grad_vars) == 48 and start == 0
-    # the reference's own lambda is recognised -> render_rays would take the fused pass
+def _check_star_imports(g, tag, modules):
+    for m in modules:
+        d = _dropin(m)
+        want = [str(n) for n in g[f"{tag}__star_{m}"]]
+        missing = [n for n in want if n not in NOT_PROVIDED and not hasattr(d, n)]
+        assert not missing, (m, missing)
+        yield m, d
+
+
+def _check_create(g, tag, ret, need_time):
     import torch
-    with torch.no_grad():        # render_only / test-time rendering (nerf/run.py:566-571)
-        assert swnerf.render.fused_plan(kw_test["network_query_fn"], [kw_test["network_fn"], kw_test["network_fine"]]) == (10, 4, 0)
+    import swnerf.render
+    kw_train, kw_test, start, grad_vars, opt = ret
+    assert list(kw_train.keys()) == [str(k) for k in g[f"{tag}__train_keys"]]
+    assert list(kw_test.keys()) == [str(k) for k in g[f"{tag}__test_keys"]]
+    assert [len(grad_vars), start, sum(p.numel() for p in grad_vars)] == g[f"{tag}__counts"].tolist()
+    assert [float(kw_test["perturb"]), float(kw_test["raw_noise_std"])] == g[f"{tag}__test_perturb_noise"].tolist()
+    assert kw_test["perturb"] is False
+    nets = [kw_test["network_fn"], kw_test["network_fine"]]
+    assert [type(n).__name__ if n is not None else "None" for n in nets] == [str(c) for c in g[f"{tag}__net_classes"]]
+    with torch.no_grad():        # render_only / test-time rendering (nerf/run.py:566-571): the fused pass
+        assert swnerf.render.fused_plan(kw_test["network_query_fn"], nets, need_time=need_time) == tuple(g[f"{tag}__fused_plan"].tolist())
     with torch.enable_grad():    # train(): trainable parameters -> the differentiable op path
-        assert swnerf.render.fused_plan(kw_train["network_query_fn"], [kw_train["network_fn"], kw_train["network_fine"]]) is None
-    assert kw_test["perturb"] is False and kw_test["raw_noise_std"] == 0.
+        assert g[f"{tag}__fused_plan_train"].tolist() == [-1, -1, -1]
+        assert swnerf.render.fused_plan(kw_train["network_query_fn"], nets, need_time=need_time) is None
+
+
+def test_static_runner_resolves_to_this_build(runners, tmp_path):
+    import swnerf.ray, swnerf.embedder, swnerf.model, swnerf.render, swnerf.runner
+    g = runners
+    mods = dict(_check_star_imports(g, "static", ("embedder", "ray")))
+    ray, emb = mods["ray"], mods["embedder"]
+    assert ray.get_rays is swnerf.ray.get_rays and ray.raw2outputs is swnerf.ray.raw2outputs
+    assert ray.sample_pdf is swnerf.ray.sample_pdf and ray.ndc_rays is swnerf.ray.ndc_rays
+    assert emb.get_embedder is swnerf.embedder.get_embedder
+    assert _dropin("model").vallina_NeRF is swnerf.model.vallina_NeRF          # `from model import vallina_NeRF as NeRF`
     # kwargs of the reference's render_rays == ours (level-2 patch is signature-compatible)
-    import inspect
-    assert list(inspect.signature(run.render_rays).parameters) == list(inspect.signature(swnerf.render.render_rays).parameters)
-    assert list(inspect.signature(run.render).parameters) == list(inspect.signature(swnerf.render.render).parameters)
-    assert list(inspect.signature(run.run_network).parameters) == list(inspect.signature(swnerf.render.run_network).parameters)
+    for fn in ("render_rays", "render", "run_network"):
+        assert list(inspect.signature(getattr(swnerf.render, fn)).parameters) == [str(p) for p in g[f"static__params_{fn}"]], fn
+    args = Namespace(**ARGS, basedir=str(tmp_path), expname="x")
+    os.makedirs(tmp_path / "x")
+    _check_create(g, "static", swnerf.runner.create_nerf(args, device="cpu"), need_time=False)
 
 
-def test_dnerf_runner_resolves_to_this_build(tmp_path):
-    import inspect
-    import swnerf.model, swnerf.render, swnerf.render_dnerf
-    drun = _load_runner("d_nerf/run_dnerf.py", "ref_drun_dropin")
-    assert drun.NeRF is swnerf.model.NeRF and drun.torch is not None and drun.np is not None     # via star-imports
-    args = Namespace(multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=128, netdepth=8,
-                     netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4,
-                     basedir=str(tmp_path), expname="y", ft_path=None, no_reload=True, perturb=1., N_samples=64,
-                     white_bkgd=True, raw_noise_std=0., dataset_type="blender", no_ndc=False, lindisp=False,
-                     nerf_type="direct_temporal", not_zero_canonical=False, use_two_models_for_fine=False,
-                     do_half_precision=False)
+def test_dnerf_runner_resolves_to_this_build(runners, tmp_path):
+    import swnerf.model, swnerf.render_dnerf, swnerf.runner
+    g = runners
+    mods = dict(_check_star_imports(g, "dnerf", ("embedder", "model", "ray")))
+    assert mods["model"].NeRF is swnerf.model.NeRF and mods["model"].torch is not None and mods["model"].np is not None
+    for fn in ("render_rays", "render", "run_network"):
+        assert list(inspect.signature(getattr(swnerf.render_dnerf, fn)).parameters) == [str(p) for p in g[f"dnerf__params_{fn}"]], fn
+    args = Namespace(**ARGS, basedir=str(tmp_path), expname="y", nerf_type="direct_temporal", not_zero_canonical=False,
+                     use_two_models_for_fine=False, do_half_precision=False)
     os.makedirs(tmp_path / "y")
-    kw_train, kw_test, start, grad_vars, opt = drun.create_nerf(args)
-    net = kw_test["network_fn"]
-    assert isinstance(net, swnerf.model.DirectTemporalNeRF) and kw_test["network_fine"] is None
-    import torch
-    with torch.no_grad():
-        assert swnerf.render.fused_plan(kw_test["network_query_fn"], [net, None], need_time=True) == (10, 4, 10)
-    assert list(inspect.signature(drun.render_rays).parameters) == list(inspect.signature(swnerf.render_dnerf.render_rays).parameters)
-    assert list(inspect.signature(drun.render).parameters) == list(inspect.signature(swnerf.render_dnerf.render).parameters)
-    assert list(inspect.signature(drun.run_network).parameters) == list(inspect.signature(swnerf.render_dnerf.run_network).parameters)
+    _check_create(g, "dnerf", swnerf.runner.create_dnerf(args, device="cpu"), need_time=True)

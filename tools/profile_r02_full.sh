@@ -3,7 +3,7 @@
 # (c) PMC of the D-NeRF pass (bench.py --config C5), (d) kernel trace + PMC of the training step.  Each PMC set is its own run.
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_r02; rm -rf $OUT; mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/trace.log 2>&1 || { echo "trace failed"; tail -5 $OUT/trace.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/trace.log 2>&1 || { echo "trace failed"; tail -5 $OUT/trace.log; exit 1; }
 f=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 python3 tools/summarize_trace.py $f 0 > $OUT/kernel_trace_all.md
 grep '^{' $OUT/trace.log > $OUT/bench_under_rocprof.json
