@@ -219,6 +219,28 @@ int swnerf_deform_backward_dx(const float* packed_bwd, const float* bits_d, cons
 int swnerf_query_points(const float* packed, const float* pts, int64_t M, const float* dirs, int64_t n_dirs,
                         int shared_dirs, int L_pos, int L_dir, float* out /*[M,4]*/, void* stream);
 
+/* Marching cubes (nerf/extract_mesh.py generate_mesh :92-131, in place of skimage.measure.marching_cubes): the iso-surface
+ * f = level of a scalar field of nx * ny * nz points in C order (i slowest), consecutive points `ld` floats apart (ld = 1: a
+ * dense [nx,ny,nz] array; ld = 4: the sigma column of swnerf_query_points' [M,4] output).  A corner is inside iff f > level
+ * (strict, fp32; NaN is outside).  Every dimension must be >= 2.  Two calls on one workspace of
+ * swnerf_mc_workspace_bytes(nx,ny,nz) bytes (0 for a dimension < 2):
+ *   swnerf_mc_count  classifies the grid and writes totals[2] = {vertices, triangles} (DEVICE int64); the caller reads them
+ *                    once (the only host synchronisation) to size the outputs
+ *   swnerf_mc_emit   same field / level / workspace; writes verts [V,3], normals [V,3] (unit, pointing toward lower f; (0,0,0)
+ *                    where the interpolated gradient is zero or not finite), faces [F,3] int32 wound outward from the dense
+ *                    side, and with colors != NULL (3 floats per point, `colors_ld` floats apart) vertex_colors [V,3] = the
+ *                    colour of the edge end point nearer the vertex.  spacing / origin are HOST float[3]: vertex coordinate
+ *                    = index * spacing + origin.  V or F above INT32_MAX is an error; V = F = 0 writes nothing.
+ * Vertices are shared per grid edge (ordered by owner point, then axis x < y < z), so the mesh is indexed and, away from the
+ * grid faces, closed.  Deterministic: no atomics. */
+size_t swnerf_mc_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int swnerf_mc_count(const float* field, int64_t nx, int64_t ny, int64_t nz, int64_t ld, float level,
+                    void* workspace, int64_t* totals /*[2]*/, void* stream);
+int swnerf_mc_emit(const float* field, const float* colors, int64_t nx, int64_t ny, int64_t nz, int64_t ld, int64_t colors_ld,
+                   float level, const float* spacing /*HOST [3]*/, const float* origin /*HOST [3]*/, void* workspace,
+                   int64_t n_verts, int64_t n_tris, float* verts /*[V,3]*/, int32_t* faces /*[F,3]*/, float* normals /*[V,3]*/,
+                   float* vertex_colors /*[V,3] or NULL*/, void* stream);
+
 /* Coarse sampling of render_rays on its own (nerf/run.py:355-385): z_vals [N,S] = near(1-t)+far*t with t = linspace(0,1,S)
  * (or the lindisp form, :365), stratified jitter when t_rand [N,S] is given (:369-383: replaces torch.rand);
  * pts [N,S,3] = rays_o + rays_d * z (:385) may be NULL.  ray_batch as for swnerf_render_pass (columns 0-7 are read). */

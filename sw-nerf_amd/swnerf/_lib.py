@@ -22,7 +22,8 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_packed_bwd_noview_floats", "swnerf_pack_net_bwd_noview", "swnerf_render_pass_backward_noview",
            "swnerf_linear", "swnerf_gemm_nn", "swnerf_relu_mask",
            "swnerf_packed_x3_floats", "swnerf_pack_net_x3", "swnerf_render_pass_x3",
-           "swnerf_packed_x3_floats_kind", "swnerf_pack_net_x3_kind"]
+           "swnerf_packed_x3_floats_kind", "swnerf_pack_net_x3_kind",
+           "swnerf_mc_workspace_bytes", "swnerf_mc_count", "swnerf_mc_emit"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -138,9 +139,16 @@ def lib():
     L.swnerf_packed_x3_floats_kind.restype = c_size_t
     L.swnerf_packed_x3_floats_kind.argtypes = [c_int]
     L.swnerf_pack_net_x3_kind.argtypes = [c_int, POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.swnerf_mc_workspace_bytes.restype = c_size_t
+    L.swnerf_mc_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    L.swnerf_mc_count.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p, c_void_p]
+    L.swnerf_mc_emit.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float,
+                                 POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p, c_int64, c_int64,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
-                        "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats"):
+                        "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",
+                        "swnerf_mc_workspace_bytes"):
             getattr(L, name).restype = c_int
     if L.swnerf_version() != 110:
         raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 110 - rebuild it "
