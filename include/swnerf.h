@@ -35,6 +35,19 @@ extern "C" {
 #define SWNERF_NET_DNERF   1     /* DirectTemporalNeRF: deformation net then canonical net   */
 #define SWNERF_NET_NOVIEW  2     /* vallina_NeRF with use_viewdirs=False (the reference's argparse default, utils.py:43;
                                     model.py:59-60): 8x256, skip@4, outputs = output_linear(h), 4 or 5 channels */
+#define SWNERF_NET_TNERF   3     /* TNeRF (model.py:152-210; t_nerf/run_tnerf.py): 8x128 ELU trunk, skip [gamma(x)|gamma(t)] @5,
+                                    density, feature -> layer_9 (64, ELU) -> color (3, ReLU); fused render pass only */
+
+/* SWNERF_NET_TNERF packing: `params` = the 24 TNeRF tensors in named_parameters() order (model.py:155-190):
+ *   [0..15]  layers.{0..7}.0.{weight,bias}       layer 0 [128, C_pos + C_time], layer 5 [128, C_pos + C_time + 128], others [128,128]
+ *   [16,17]  density.0.{weight,bias}             [1,128]
+ *   [18,19]  feature.0.{weight,bias}             [128,128]
+ *   [20,21]  layer_9.0.{weight,bias}             [64, 128 + C_dir]
+ *   [22,23]  color.0.{weight,bias}               [3,64]
+ * swnerf_pack_net(SWNERF_NET_TNERF, params, L_pos, L_dir, L_time, packed, stream); L_dir >= 1.
+ * swnerf_packed_floats(SWNERF_NET_TNERF) = (steps + 16) * 256 + 45 * 32 + 64 * 160 + 64 = 165344 floats, steps = 40 per-ray
+ * prefix steps + 544 per-tile steps (1 step = 256 floats = the A operands of 4 MFMAs; 16 = the ring tail; 45 bias-style tiles of
+ * 32 floats; the folded layer_9, [64][160] + its bias).  The pack step folds feature into layer_9 (fp64 product, one rounding). */
 
 int         swnerf_version(void);
 const char* swnerf_last_error(void);
@@ -411,6 +424,17 @@ int swnerf_linear(const float* x, int ldx, int64_t M, int K, const float* weight
 int swnerf_gemm_nn(const float* a, int lda, int64_t M, int K, const float* b, int ldb, int N, float* c, int ldc,
                    void* stream);
 int swnerf_relu_mask(float* dy, const float* y, int64_t n, void* stream);
+
+/* The same GEMM with a choice of epilogue, and the ELU backward (TNeRF, model.py:152-210, on the op path):
+ * linear_act: y = act(x . weight^T + bias), act = SWNERF_ACT_NONE / SWNERF_ACT_RELU / SWNERF_ACT_ELU (alpha = 1; an
+ *             expm1-accurate form, max abs error 1.2e-7 against expm1 on [-20, 0]; the fused T-NeRF pass uses the same one)
+ * elu_grad  : dy[e] *= (y[e] > 0 ? 1 : y[e] + 1), in place   ELU backward from its output (elu'(x) = exp(x) = y + 1 for x <= 0) */
+#define SWNERF_ACT_NONE 0
+#define SWNERF_ACT_RELU 1
+#define SWNERF_ACT_ELU  2
+int swnerf_linear_act(const float* x, int ldx, int64_t M, int K, const float* weight /*[N,K]*/, const float* bias /*[N]*/,
+                      int N, int act, float* y, int ldy, void* stream);
+int swnerf_elu_grad(float* dy, const float* y, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

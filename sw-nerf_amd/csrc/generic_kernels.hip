@@ -7,6 +7,7 @@
 //   linear   : Y[M,N] = act(X[M,K] . W[N,K]^T + b)         (torch.nn.functional.linear [+ relu])
 //   gemm_nn  : dX[M,K] = dY[M,N] . W[N,K]                   (its input gradient)
 //   relu_mask: dY *= (Y > 0)                                (relu backward, in place)
+//   linear_act / elu_grad: the same GEMM with an ELU epilogue (elu.h) and its backward from the output (TNeRF, model.py:152-210)
 // The weight gradient dW = dY^T . X and db = column sums are swnerf_gemm_tn (backward_kernels.hip).
 //
 // One workgroup (4 waves) owns a 64 x 64 block of the output, wave w the 32 x 32 tile (w&1, w>>1); the K dimension
@@ -16,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/swnerf.h"
 #include "host_util.h"
+#include "elu.h"
 #include <cstdlib>
 #include <cstdint>
 
@@ -30,7 +32,7 @@ struct GenericGemm {
     const float* B; int ldb;     // BT: [N, K] row-major (C = A.B^T);  else [K, N] row-major (C = A.B)
     const float* bias;           // [N] or NULL
     float* C; int ldc;           // [M, N]
-    int64_t M; int N, K; int relu;
+    int64_t M; int N, K; int act;    // epilogue: SWNERF_ACT_NONE / _RELU / _ELU
 };
 
 template <bool BT>
@@ -87,7 +89,8 @@ __global__ void __launch_bounds__(256) generic_gemm_kernel(GenericGemm P) {
         const int64_t m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (m < P.M) {
             float v = acc[r] + bv;
-            if (P.relu) v = fmaxf(v, 0.f);
+            if (P.act == SWNERF_ACT_RELU) v = fmaxf(v, 0.f);
+            else if (P.act == SWNERF_ACT_ELU) v = sw_elu(v);
             P.C[m * P.ldc + n] = v;
         }
     }
@@ -233,7 +236,8 @@ __global__ void __launch_bounds__(256, 2) generic_gemm128_kernel(GenericGemm P) 
                 const int64_t m = m0 + wm + 32 * x + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (m < P.M) {
                     float v = acc[2 * x + y][r] + bv;
-                    if (P.relu) v = fmaxf(v, 0.f);
+                    if (P.act == SWNERF_ACT_RELU) v = fmaxf(v, 0.f);
+                    else if (P.act == SWNERF_ACT_ELU) v = sw_elu(v);
                     P.C[m * P.ldc + n] = v;
                 }
             }
@@ -268,14 +272,14 @@ static int generic_launch(const GenericGemm& P, bool bt, void* stream, const cha
 extern "C" int swnerf_linear(const float* x, int ldx, int64_t M, int K, const float* weight, const float* bias, int N,
                              int relu, float* y, int ldy, void* stream) {
     GenericGemm P;
-    P.A = x; P.lda = ldx; P.B = weight; P.ldb = K; P.bias = bias; P.C = y; P.ldc = ldy; P.M = M; P.N = N; P.K = K; P.relu = relu;
+    P.A = x; P.lda = ldx; P.B = weight; P.ldb = K; P.bias = bias; P.C = y; P.ldc = ldy; P.M = M; P.N = N; P.K = K; P.act = relu ? SWNERF_ACT_RELU : SWNERF_ACT_NONE;
     return generic_launch(P, true, stream, "linear");
 }
 
 extern "C" int swnerf_gemm_nn(const float* a, int lda, int64_t M, int K, const float* b, int ldb, int N, float* c, int ldc,
                               void* stream) {
     GenericGemm P;
-    P.A = a; P.lda = lda; P.B = b; P.ldb = ldb; P.bias = nullptr; P.C = c; P.ldc = ldc; P.M = M; P.N = N; P.K = K; P.relu = 0;
+    P.A = a; P.lda = lda; P.B = b; P.ldb = ldb; P.bias = nullptr; P.C = c; P.ldc = ldc; P.M = M; P.N = N; P.K = K; P.act = SWNERF_ACT_NONE;
     return generic_launch(P, false, stream, "gemm_nn");
 }
 
@@ -289,4 +293,29 @@ extern "C" int swnerf_relu_mask(float* dy, const float* y, int64_t n, void* stre
     if (!dy || !y || n < 0) return sw_fail(SWNERF_E_ARG, "relu_mask: NULL pointer or negative count");
     hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, y, n);
     return sw_check(hipGetLastError(), "relu_mask launch");
+}
+
+extern "C" int swnerf_linear_act(const float* x, int ldx, int64_t M, int K, const float* weight, const float* bias, int N,
+                                 int act, float* y, int ldy, void* stream) {
+    if (act != SWNERF_ACT_NONE && act != SWNERF_ACT_RELU && act != SWNERF_ACT_ELU)
+        return sw_fail(SWNERF_E_ARG, "linear_act: unknown activation %d (0 none, 1 relu, 2 elu)", act);
+    GenericGemm P;
+    P.A = x; P.lda = ldx; P.B = weight; P.ldb = K; P.bias = bias; P.C = y; P.ldc = ldy; P.M = M; P.N = N; P.K = K; P.act = act;
+    return generic_launch(P, true, stream, "linear_act");
+}
+
+// ELU backward from the output: elu'(x) = 1 for x > 0, exp(x) = y + 1 otherwise
+__global__ void __launch_bounds__(256) elu_grad_kernel(float* dy, const float* y, int64_t n) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < n) {
+        const float v = y[e];
+        dy[e] = (v > 0.f) ? dy[e] : dy[e] * (v + 1.f);
+    }
+}
+
+extern "C" int swnerf_elu_grad(float* dy, const float* y, int64_t n, void* stream) {
+    if (n == 0) return 0;
+    if (!dy || !y || n < 0) return sw_fail(SWNERF_E_ARG, "elu_grad: NULL pointer or negative count");
+    hipLaunchKernelGGL(elu_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, y, n);
+    return sw_check(hipGetLastError(), "elu_grad launch");
 }

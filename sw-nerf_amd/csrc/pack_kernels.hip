@@ -248,8 +248,77 @@ struct Packer {
     }
 };
 
+// TNeRF (model.py:152-210): `feature` (no activation) folded into layer_9: fold[u][i] = sum_o W9[u][o] Wf[o][i] for i < 128,
+// fold[u][128 + c] = W9[u][128 + c] for the Cdir view-direction columns (0 beyond), and behind the 64 rows
+// b9f[u] = sum_o W9[u][o] bf[o] + b9[u].  fp64 accumulation, one rounding.  Block u (64), thread i (160).
+__global__ void __launch_bounds__(256) fold_tnerf_kernel(const float* W9, const float* b9, const float* Wf, const float* bf, int Cdir,
+                                                         float* fold) {
+    __shared__ float wrow[128];
+    const int u = blockIdx.x, i = threadIdx.x;
+    const int ld9 = 128 + Cdir;
+    if (i < 128) wrow[i] = W9[(size_t)u * ld9 + i];
+    __syncthreads();
+    float* row = fold + (size_t)u * SW_TN_FOLD_LD;
+    if (i < 128) {
+        double acc = 0.0;
+        for (int o = 0; o < 128; ++o) acc += (double)wrow[o] * (double)Wf[(size_t)o * 128 + i];
+        row[i] = (float)acc;
+    } else if (i < SW_TN_FOLD_LD) {
+        const int c = i - 128;
+        row[i] = c < Cdir ? W9[(size_t)u * ld9 + 128 + c] : 0.f;
+    } else if (i == SW_TN_FOLD_LD) {
+        double b = 0.0;
+        for (int o = 0; o < 128; ++o) b += (double)wrow[o] * (double)bf[o];
+        fold[(size_t)64 * SW_TN_FOLD_LD + u] = (float)(b + (double)b9[u]);
+    }
+}
+
+// The T-NeRF stream (swnerf_common.h SW_TN_*): T0 | T5 | DIR | MAIN | ring tail, then the bias-style tiles, then the fold.
+static int pack_tnerf(const float* const* params, int L_pos, int L_dir, int L_time, float* packed, hipStream_t st) {
+    const int Cpos = 3 * (1 + 2 * L_pos), Cdir = 3 * (1 + 2 * L_dir), Ct = 1 + 2 * L_time;
+    const int Cin = Cpos + Ct;
+    float* fold = packed + SW_TN_FOLD_OFFSET;
+    hipLaunchKernelGGL(fold_tnerf_kernel, dim3(64), dim3(256), 0, st, params[20], params[21], params[18], params[19], Cdir, fold);
+    int rc = sw_check(hipGetLastError(), "pack_net (T-NeRF) fold launch");
+    if (rc) return rc;
+    Packer pk(st, packed, packed + SW_TN_W_FLOATS, L_pos, L_dir, L_time);
+    const int kt_time[1] = {KT_TIME}, kb_time[1] = {Cpos};
+    const int kt_dir[1] = {KT_DIR}, kb_dir[1] = {128};
+    const int kt_pos[2] = {KT_POS0, KT_POS1}, kb_pos[2] = {0, 0};
+    const int kt4[4] = {KT_TRUNK, KT_TRUNK, KT_TRUNK, KT_TRUNK}, kb4[4] = {0, 32, 64, 96};
+    const int kb5[4] = {Cin, Cin + 32, Cin + 64, Cin + 96};
+    // per-ray prefix (evaluated once per ray: tnerf_kernels.hip tn_ray_tile); the ring tail repeats the head of MAIN
+    pk.seg(params[0], params[1], 128, Cin, 4, 1, kt_time, kb_time);                 // T0: layers.0 gamma(t) columns + bias
+    pk.seg(params[10], params[11], 128, Cin + 128, 4, 1, kt_time, kb_time);         // T5: layers.5 gamma(t) columns + bias
+    pk.seg(fold, fold + 64 * SW_TN_FOLD_LD, 64, SW_TN_FOLD_LD, 2, 1, kt_dir, kb_dir);  // DIR: layer_9 gamma(d) columns + b9f
+    pk.have_head = false;
+    pk.seg(params[0], nullptr, 128, Cin, 4, 2, kt_pos, kb_pos);                     // L0: gamma(x) columns
+    for (int l = 1; l < 8; ++l) {
+        if (l == 5) {                                                                // input = cat([gamma(x), gamma(t)], h4)
+            pk.seg(params[10], nullptr, 128, Cin + 128, 4, 4, kt4, kb5);
+            pk.seg(params[10], nullptr, 128, Cin + 128, 4, 2, kt_pos, kb_pos);
+        } else {
+            pk.seg(params[2 * l], params[2 * l + 1], 128, 128, 4, 4, kt4, kb4);
+        }
+    }
+    pk.vecs(params[16], 1, 128);                                                     // density.weight
+    pk.headbias(params[17], 1, params[23], 3);                                       // [b_density, b_r, b_g, b_b]
+    pk.seg(fold, nullptr, 64, SW_TN_FOLD_LD, 2, 4, kt4, kb4);                        // L9: W9f on h7
+    pk.vecs(params[22], 3, 64);                                                      // color.weight
+    if (!pk.rc && (pk.w != packed + (size_t)SW_TN_STEPS * SW_STEP_FLOATS || pk.b != packed + SW_TN_FOLD_OFFSET))
+        return sw_fail(SWNERF_E_ARG, "pack_net (T-NeRF): internal layout mismatch");
+    pk.tail();
+    return pk.flush();
+}
+
 extern "C" int swnerf_pack_net(int kind, const float* const* params, int L_pos, int L_dir, int L_time, float* packed, void* stream) {
     if (!params || !packed) return sw_fail(SWNERF_E_ARG, "pack_net: NULL pointer");
+    if (kind == SWNERF_NET_TNERF) {
+        if (L_pos < 0 || L_pos > 10 || L_dir < 1 || L_dir > 4 || L_time < 0 || L_time > 10)
+            return sw_fail(SWNERF_E_UNSUPP, "pack_net: T-NeRF embedder bands (%d,%d,%d) outside (0..10, 1..4, 0..10)", L_pos, L_dir, L_time);
+        for (int i = 0; i < 24; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net: params[%d] is NULL", i);
+        return pack_tnerf(params, L_pos, L_dir, L_time, packed, (hipStream_t)stream);
+    }
     if (kind != SWNERF_NET_CANON && kind != SWNERF_NET_DNERF) return sw_fail(SWNERF_E_ARG, "pack_net: unknown kind %d", kind);
     if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4 || L_time < 0 || L_time > 10)
         return sw_fail(SWNERF_E_UNSUPP, "pack_net: embedder bands (%d,%d,%d) exceed (10,4,10)", L_pos, L_dir, L_time);

@@ -70,11 +70,19 @@ __global__ void __launch_bounds__(256, 1) query_points_kernel(QueryDev P) {
     }
 }
 
+int sw_tnerf_render_launch(const swnerf_pass_args& a, hipStream_t st);     // tnerf_kernels.hip
+
 extern "C" int swnerf_render_pass(const swnerf_pass_args* args, void* stream) {
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass: NULL args");
     const swnerf_pass_args& a = *args;
     if (!a.packed || (!a.ray_batch && a.n_rays != 0)) return sw_fail(SWNERF_E_ARG, "render_pass: NULL ray_batch/packed");
     if (a.n_rays < 0 || a.n_samples < 2) return sw_fail(SWNERF_E_ARG, "render_pass: n_rays %lld, n_samples %d", (long long)a.n_rays, a.n_samples);
+    if (a.kind == SWNERF_NET_TNERF) {            // the T-NeRF pass lives in its own translation unit (tnerf_kernels.hip)
+        if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4 || a.L_time < 0 || a.L_time > 10)
+            return sw_fail(SWNERF_E_UNSUPP, "render_pass: embedder bands (%d,%d,%d) exceed (10,4,10)", a.L_pos, a.L_dir, a.L_time);
+        if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "render_pass: t_rand only applies to coarse sampling");
+        return sw_tnerf_render_launch(a, (hipStream_t)stream);
+    }
     const bool noview = a.kind == SWNERF_NET_NOVIEW;
     if (noview ? a.cols != 8 : (a.cols != 11 && a.cols != 12))
         return sw_fail(SWNERF_E_ARG, "render_pass: ray_batch must have 11 or 12 columns (use_viewdirs) or 8 (SWNERF_NET_NOVIEW), got %d for kind %d", a.cols, a.kind);

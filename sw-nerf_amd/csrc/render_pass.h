@@ -381,6 +381,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
                       lds_bias + ((P.dir_steps ? SW_DIR_BIAS_TILES : 0) + (P.time_steps ? 8 : 0)) * SW_BIAS_TILE_FLOATS, lane);
 
         // ---- raw2outputs on this tile (ray.py:155-198); both lane halves mirror each other
+        // (TWIN: tnerf_kernels.hip repeats this scan and the map writes below for the T-NeRF pass; change both together)
         const float c0 = rgb[0], c1 = rgb[1], c2 = rgb[2];
         float sg = head[0];
         if (a.raw && live && h == 0) {

@@ -225,3 +225,30 @@ SW_HD float sw_linspace(float start, float end, int steps, int i) {
     const float step = (end - start) / (float)(steps - 1);
     return (i < steps / 2) ? fmaf(step, (float)i, start) : fmaf(-step, (float)(steps - 1 - i), end);
 }
+
+// ---- T-NeRF (SWNERF_NET_TNERF; model.py:152-210) ---------------------------------------------------------------
+// 8 layers of width 128 with ELU, the skip input [gamma(x) | gamma(t)] in front of h4 at layer 5, `density` (128 -> 1, no
+// activation), `feature` (128 -> 128, no activation) -> layer_9 on [feature | gamma(d)] (-> 64, ELU) -> `color` (64 -> 3, ReLU).
+// Width 128 = 4 accumulator tiles (NT = KT = 4).  The gamma(t) columns of layers 0 and 5 and the gamma(d) columns of layer_9 are
+// per-RAY constants (one frame time per batch, run_tnerf.py:52; one direction per ray): the pass evaluates them once per ray, with
+// the layer's bias, into per-wave LDS tiles that start the layer's accumulators (the D-NeRF TIME segment's scheme).
+// `feature` is folded into layer_9 at pack time like feature_linear into views_linears.0:
+//   W9f = W9[:, :128] . Wf (64 x 128),  b9f = W9[:, :128] . bf + b9  (fp64 accumulation, one rounding).
+//   stream: T0 (4x1) | T5 (4x1) | DIR (2x1) | MAIN = L0 (4x2, gamma(x)) | L1..L4 (4x4) | L5 (4x4 on h4, then 4x2 on gamma(x)) |
+//           L6 L7 (4x4) | L9 (2x4 on h7 through W9f) ;  ring tail = copy of MAIN's first SW_TAIL steps
+#define SW_TN_STEPS_T0     16
+#define SW_TN_STEPS_T5     16
+#define SW_TN_STEPS_DIR    8
+#define SW_TN_PREFIX_STEPS (SW_TN_STEPS_T0 + SW_TN_STEPS_T5 + SW_TN_STEPS_DIR)
+#define SW_TN_MAIN_STEPS   (32 + 4 * 64 + (64 + 32) + 2 * 64 + 32)      // 544 steps = 2176 MFMAs per 32-sample tile
+#define SW_TN_STEPS        (SW_TN_PREFIX_STEPS + SW_TN_MAIN_STEPS)
+// bias-style tiles in consumption order: b0 4 (T0) | b5 4 (T5) | b9f 2 (DIR) | L1-4 16 | L6-7 8 | density.weight 4 |
+//   1 head-bias tile [b_density, b_r, b_g, b_b] | color.weight 3 x 2
+#define SW_TN_PREFIX_BIAS_TILES 10
+#define SW_TN_BIAS_TILES   (SW_TN_PREFIX_BIAS_TILES + 16 + 8 + 4 + 1 + 6)
+// the folded layer_9 rides at the end of the blob: [64][SW_TN_FOLD_LD] = [W9f | W9[:, 128:] | 0 pad] then b9f[64]
+#define SW_TN_FOLD_LD      160
+#define SW_TN_FOLD_FLOATS  (64 * SW_TN_FOLD_LD + 64)
+#define SW_TN_W_FLOATS     ((SW_TN_STEPS + SW_TAIL) * SW_STEP_FLOATS)
+#define SW_TN_FOLD_OFFSET  (SW_TN_W_FLOATS + SW_TN_BIAS_TILES * SW_BIAS_TILE_FLOATS)
+#define SW_TN_FLOATS       (SW_TN_FOLD_OFFSET + SW_TN_FOLD_FLOATS)

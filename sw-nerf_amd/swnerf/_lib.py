@@ -8,7 +8,8 @@ from ctypes import c_int, c_int64, c_double, c_void_p, c_size_t, c_char_p, POINT
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libswnerf_hip.so")
 
-NET_CANON, NET_DNERF, NET_NOVIEW = 0, 1, 2
+NET_CANON, NET_DNERF, NET_NOVIEW, NET_TNERF = 0, 1, 2, 3
+ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
 
 EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swnerf_pack_net", "swnerf_pack_net_noview", "swnerf_mlp_forward_noview",
            "swnerf_get_rays", "swnerf_ndc_rays", "swnerf_pack_ray_batch", "swnerf_raw2outputs", "swnerf_raw2outputs_backward",
@@ -23,7 +24,8 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_linear", "swnerf_gemm_nn", "swnerf_relu_mask",
            "swnerf_packed_x3_floats", "swnerf_pack_net_x3", "swnerf_render_pass_x3",
            "swnerf_packed_x3_floats_kind", "swnerf_pack_net_x3_kind",
-           "swnerf_mc_workspace_bytes", "swnerf_mc_count", "swnerf_mc_emit"]
+           "swnerf_mc_workspace_bytes", "swnerf_mc_count", "swnerf_mc_emit",
+           "swnerf_linear_act", "swnerf_elu_grad"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -132,6 +134,8 @@ def lib():
     L.swnerf_linear.argtypes = [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
     L.swnerf_gemm_nn.argtypes = [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
     L.swnerf_relu_mask.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
+    L.swnerf_linear_act.argtypes = [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
+    L.swnerf_elu_grad.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
     L.swnerf_packed_x3_floats.restype = c_size_t
     L.swnerf_packed_x3_floats.argtypes = []
     L.swnerf_pack_net_x3.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p, c_void_p]

@@ -16,13 +16,18 @@ def _c32(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def _linear_raw(x, weight, bias, relu):
+def _linear_raw(x, weight, bias, act):
+    """act: _lib.ACT_NONE / ACT_RELU / ACT_ELU"""
     L = _lib.lib()
     M, K = x.shape
     N = weight.shape[0]
     y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _lib.check(L.swnerf_linear(_lib.ptr(x), x.stride(0), M, K, _lib.ptr(weight), _lib.ptr(bias), N, int(relu), _lib.ptr(y), N,
-                               _lib.stream_of(x)), "linear")
+    if act == _lib.ACT_ELU:
+        _lib.check(L.swnerf_linear_act(_lib.ptr(x), x.stride(0), M, K, _lib.ptr(weight), _lib.ptr(bias), N, act, _lib.ptr(y), N,
+                                       _lib.stream_of(x)), "linear_act")
+    else:
+        _lib.check(L.swnerf_linear(_lib.ptr(x), x.stride(0), M, K, _lib.ptr(weight), _lib.ptr(bias), N, int(act == _lib.ACT_RELU),
+                                   _lib.ptr(y), N, _lib.stream_of(x)), "linear")
     return y
 
 
@@ -30,10 +35,10 @@ class _Linear(torch.autograd.Function):
     """y = act(x . W^T + b) with hand-written forward and backward kernels."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu):
-        y = _linear_raw(x, weight, bias, relu)
-        ctx.relu = relu
-        ctx.save_for_backward(x, weight, y if relu else x.new_empty(0))
+    def forward(ctx, x, weight, bias, act):
+        y = _linear_raw(x, weight, bias, act)
+        ctx.act = act
+        ctx.save_for_backward(x, weight, y if act != _lib.ACT_NONE else x.new_empty(0))
         ctx.has_bias = bias is not None
         return y
 
@@ -45,9 +50,12 @@ class _Linear(torch.autograd.Function):
         M, K = x.shape
         N = weight.shape[0]
         dy = _c32(dy)
-        if ctx.relu:
+        if ctx.act == _lib.ACT_RELU:
             dy = dy.clone()                                  # masked in place; the caller's tensor stays untouched
             _lib.check(L.swnerf_relu_mask(_lib.ptr(dy), _lib.ptr(y), dy.numel(), st), "relu_mask")
+        elif ctx.act == _lib.ACT_ELU:
+            dy = dy.clone()                                  # scaled in place by elu'(x) = y + 1 (x <= 0)
+            _lib.check(L.swnerf_elu_grad(_lib.ptr(dy), _lib.ptr(y), dy.numel(), st), "elu_grad")
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((M, K), dtype=torch.float32, device=x.device)
@@ -62,15 +70,17 @@ class _Linear(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def linear(x, lin, relu=False):
-    """nn.Linear `lin` applied to x [M, K] by the HIP GEMM (+ relu fused)."""
+def linear(x, lin, relu=False, act=None):
+    """nn.Linear `lin` applied to x [M, K] by the HIP GEMM with a fused epilogue: `act` (_lib.ACT_NONE / ACT_RELU / ACT_ELU),
+    or, when act is None, relu if `relu`."""
+    act = (_lib.ACT_RELU if relu else _lib.ACT_NONE) if act is None else int(act)
     x = _lib.dev_f32(x, "x", lin.in_features)
     w, b = lin.weight, lin.bias
     if not w.is_cuda:
         raise RuntimeError("swnerf: module parameters must be on the GPU (call .to('cuda')); no CPU fallback")
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)):
-        return _Linear.apply(x, _c32(w), None if b is None else _c32(b), bool(relu))
-    return _linear_raw(x, _c32(w.detach()), None if b is None else _c32(b.detach()), bool(relu))
+        return _Linear.apply(x, _c32(w), None if b is None else _c32(b), act)
+    return _linear_raw(x, _c32(w.detach()), None if b is None else _c32(b.detach()), act)
 
 
 def canonical_forward(mod, x):
@@ -150,3 +160,34 @@ def temporal_forward(mod, x, ts):
         input_pts = embed_with_grad(mod.embed_fn, input_pts[:, :3] + dx)
     out = canonical_forward(mod._occ, torch.cat([input_pts, input_views], dim=-1))
     return out.reshape(*lead, out.shape[-1]), dx.reshape(*lead, 3)
+
+
+def tnerf_forward(mod, inp, vdir, dyn_t):
+    """TNeRF.forward (model.py:192-210) for any depth / width / skip_layer: layer by layer on the generic GEMM with the ELU
+    epilogue, differentiable.  Where the reference fails, this fails the same way: vdir None (AttributeError on .shape), or a
+    depth whose skip concatenation leaves a layer the wrong width (RuntimeError, as torch's matmul raises)."""
+    inp = inp[:, :mod.in_feat]
+    inp = torch.cat([_lib.dev_f32(inp, "inp"), _lib.dev_f32(dyn_t, "dyn_t")], dim=-1)
+    inp_n_samples, inp_c = inp.shape
+    dir_n_samples, vdir_c = vdir.shape
+    vdir = _lib.dev_f32(vdir, "vdir").reshape(-1, vdir_c)
+
+    def lin(x, layer, act):
+        if x.shape[-1] != layer.in_features:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({x.shape[0]}x{x.shape[-1]} and "
+                               f"{layer.in_features}x{layer.out_features})")
+        return linear(x, layer, act=act)
+
+    x = inp
+    for i in range(mod.depth):
+        x = lin(x, mod.layers[i][0], _lib.ACT_ELU)
+        if (i % mod.skip_layer == 0) and (i > 0):
+            x = torch.cat([inp, x], dim=-1)
+    sigma = lin(x, mod.density[0], _lib.ACT_NONE)
+    x = lin(x, mod.feature[0], _lib.ACT_NONE)
+    x = torch.cat([x, vdir], dim=-1)
+    x = lin(x, mod.layer_9[0], _lib.ACT_ELU)
+    rgb = lin(x, mod.color[0], _lib.ACT_RELU)
+    sigma = torch.reshape(sigma, [-1, inp_n_samples, 1])
+    rgb = torch.reshape(rgb, [-1, inp_n_samples, 3])
+    return torch.cat([rgb, sigma], dim=-1)

@@ -8,7 +8,8 @@ The register-resident kernel is built for the configuration every shipped config
 use_viewdirs=True with get_embedder-sized inputs.  Any other shape (use_viewdirs=False - the reference's argparse
 default -, other D / W / skips / input sizes) runs layer by layer on the generic MFMA GEMM kernels (swnerf/generic.py,
 csrc/generic_kernels.hip): slower, same results, differentiable.
-TNeRF (model.py:152-210) is out of scope.
+TNeRF (model.py:152-210, the T-NeRF runner's net): forward runs layer by layer on the generic GEMMs with an ELU epilogue
+(differentiable); swnerf.render_tnerf renders it with the fused T-NeRF pass (csrc/tnerf_kernels.hip) under no_grad.
 Training: with grad enabled, forward saves the activations and backward runs the
 register-resident dX chain + TN MFMA GEMMs (`_MlpTrain`, `_DnerfTrain`); gradients w.r.t. the embedded inputs are
 not produced (rays are data in the reference's train()).
@@ -471,3 +472,70 @@ class NeRF:
         if type == "direct_temporal":
             return DirectTemporalNeRF(*args, **kwargs)
         raise ValueError("Type %s not recognized." % type)
+
+
+_TNERF_ORDER = ([f"layers.{i}.0.{p}" for i in range(8) for p in ("weight", "bias")]
+                + [f"{n}.0.{p}" for n in ("density", "feature", "layer_9", "color") for p in ("weight", "bias")])
+
+
+class TNeRF(nn.Module):
+    """model.py:152-210: `depth` layers of width `net_dim` with ELU, the input [gamma(x) | gamma(t)] concatenated in front of
+    the activations after layer `skip_layer` (and every multiple of it), `density` (no activation), `feature` (no activation)
+    -> `layer_9` on [feature | gamma(d)] (ELU) -> `color` (ReLU).  Same submodules, parameter shapes and construction order
+    as the reference, so a seed gives the same initial weights and reference state_dicts load strictly.
+    forward(inp, vdir, dyn_t) -> [1, M, 4] runs on the generic HIP GEMMs (swnerf/generic.py tnerf_forward) and is
+    differentiable; swnerf.render_tnerf.render_rays renders the default shape (8 x 128, skip 4) with the fused pass."""
+
+    def __init__(self, depth, in_feat, dir_feat, time_feat, net_dim=128, skip_layer=4):
+        super().__init__()
+        self.depth = depth
+        self.skip_layer = skip_layer
+        units = [in_feat + time_feat] + [net_dim] * (self.depth + 1)
+        self.layers = nn.ModuleList([])
+        self.bnorm_layers = nn.ModuleList([])
+        self.in_feat = in_feat
+        self.dir_feat, self.time_feat, self.net_dim = dir_feat, time_feat, net_dim
+        for i in range(self.depth):
+            if (i % (self.skip_layer + 1) == 0) and (i > 0):
+                self.layers.append(nn.Sequential(nn.Linear(in_features=units[i] + in_feat + time_feat, out_features=units[i + 1]), nn.ELU()))
+            else:
+                self.layers.append(nn.Sequential(nn.Linear(in_features=units[i], out_features=units[i + 1]), nn.ELU()))
+        self.density = nn.Sequential(nn.Linear(in_features=net_dim, out_features=1))
+        self.feature = nn.Sequential(nn.Linear(in_features=net_dim, out_features=net_dim))
+        self.layer_9 = nn.Sequential(nn.Linear(in_features=net_dim + dir_feat, out_features=net_dim // 2), nn.ELU())
+        self.color = nn.Sequential(nn.Linear(in_features=net_dim // 2, out_features=3), nn.ReLU())
+        self._pack_key, self._packed = None, None
+
+    def forward(self, inp, vdir, dyn_t):
+        from .generic import tnerf_forward
+        return tnerf_forward(self, inp, vdir, dyn_t)
+
+    def fused_bands(self):
+        """(L_pos, L_dir, L_time) when this net has the shape the fused T-NeRF pass is built for (depth 8, width 128, skip 4,
+        get_embedder-sized inputs with L_pos, L_time <= 10 and 1 <= L_dir <= 4); else None."""
+        if not (self.depth == 8 and self.net_dim == 128 and self.skip_layer == 4):
+            return None
+        Lp, Ld, Lt = _bands(self.in_feat, 3), _bands(self.dir_feat, 3), _bands(self.time_feat, 1)
+        if Lp is None or Ld is None or Lt is None or Lp > 10 or not 1 <= Ld <= 4 or Lt > 10:
+            return None
+        return Lp, Ld, Lt
+
+    def packed(self):
+        """(kind SWNERF_NET_TNERF, packed float tensor, L_pos, L_dir, L_time); repacked when a parameter changed or moved."""
+        bands = self.fused_bands()
+        if bands is None:
+            raise NotImplementedError("swnerf: the fused T-NeRF pass is built for depth 8, net_dim 128, skip_layer 4 with "
+                                      "get_embedder-sized inputs (L_pos, L_time <= 10, 1 <= L_dir <= 4)")
+        sd = dict(self.named_parameters())
+        ps = [sd[n] for n in _TNERF_ORDER]
+        if not ps[0].is_cuda:
+            raise RuntimeError("swnerf: module parameters must be on the GPU (call .to('cuda')); no CPU fallback")
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._pack_key:
+            L = _lib.lib()
+            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
+            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
+            buf = torch.empty(L.swnerf_packed_floats(_lib.NET_TNERF), dtype=torch.float32, device=ps[0].device)
+            _lib.check(L.swnerf_pack_net(_lib.NET_TNERF, arr, *bands, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net")
+            self._packed, self._pack_key = buf, key
+        return (_lib.NET_TNERF, self._packed) + bands

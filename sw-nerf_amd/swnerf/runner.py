@@ -6,10 +6,10 @@ written against the reference only swaps its imports.  `args` is any object with
 `render.fused_plan` finds the encoders and sends `render_rays` to the fused HIP pass."""
 import torch
 
-from . import render, render_dnerf
+from . import render, render_dnerf, render_tnerf
 from .checkpoint import reload_latest
 from .embedder import get_embedder
-from .model import vallina_NeRF, NeRF
+from .model import vallina_NeRF, NeRF, TNeRF
 
 
 def _render_kwargs(args, network_query_fn, model, model_fine, extra=None):
@@ -100,3 +100,43 @@ def create_dnerf(args, device=None):
     train, test = _render_kwargs(args, network_query_fn, model, model_fine,
                                  {'use_two_models_for_fine': args.use_two_models_for_fine})
     return train, test, start, grad_vars, optimizer
+
+
+def create_tnerf(args, device=None):
+    """t_nerf/run_tnerf.py:238-345 (`create_nerf` of the T-NeRF runner): one TNeRF (width 128, skip_layer 4, depth
+    args.netdepth), the time encoder at args.multires, N_importance forced to 0.  fp32 only: `do_half_precision` is refused."""
+    if getattr(args, "do_half_precision", False):
+        raise NotImplementedError("swnerf.create_tnerf: do_half_precision (apex amp) is not built; the HIP path is fp32")
+    device = _device(device)
+    embed_fn, input_ch = get_embedder(args.multires, 3, args.i_embed)
+    embedtime_fn, input_ch_time = get_embedder(args.multires, 1, args.i_embed)
+    input_ch_views, embeddirs_fn = 0, None
+    if args.use_viewdirs:
+        embeddirs_fn, input_ch_views = get_embedder(args.multires_views, 3, args.i_embed)
+    model = TNeRF(depth=args.netdepth, in_feat=input_ch, dir_feat=input_ch_views, time_feat=input_ch_time, net_dim=128,
+                  skip_layer=4).to(device)
+    grad_vars = list(model.parameters())
+    netchunk, discr = args.netchunk, args.nerf_type != "temporal"
+    network_query_fn = lambda inputs, viewdirs, ts, network_fn: render_tnerf.run_network(
+        inputs, viewdirs, ts, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, embedtime_fn=embedtime_fn,
+        netchunk=netchunk, embd_time_discr=discr)
+    optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
+    start, _ = reload_latest(args.basedir, args.expname, model, None, optimizer, ft_path=args.ft_path,
+                             no_reload=args.no_reload, map_location=device)
+    kw = {
+        'network_query_fn': network_query_fn,
+        'perturb': args.perturb,
+        'N_importance': 0,
+        'network_fn': model,
+        'N_samples': args.N_samples,
+        'use_viewdirs': args.use_viewdirs,
+        'white_bkgd': args.white_bkgd,
+        'raw_noise_std': args.raw_noise_std,
+    }
+    if args.dataset_type != 'llff' or args.no_ndc:               # run_tnerf.py:336-338
+        kw['ndc'] = False
+        kw['lindisp'] = args.lindisp
+    test = {k: kw[k] for k in kw}
+    test['perturb'] = False
+    test['raw_noise_std'] = 0.
+    return kw, test, start, grad_vars, optimizer

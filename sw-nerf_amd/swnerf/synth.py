@@ -91,6 +91,27 @@ def dnerf_state_dict(seed, input_ch=63, input_ch_views=27, input_ch_time=21, alp
     return sd
 
 
+def tnerf_state_dict(seed, in_feat=63, dir_feat=27, time_feat=21, net_dim=128, density_bias=-0.2, bias_scale=0.1):
+    """Weights of one TNeRF (model.py:152-190, depth 8, skip_layer 4) as numpy arrays, keyed like its state_dict.
+    W ~ N(0, 2/fan_in) keeps the ELU trunk's activations of order one, so both signs reach every ELU and the colour
+    ReLU; `density.0.bias` shifts sigma so that the accumulated opacity of a lego-like ray spans roughly (0.1, 1)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    ins = [in_feat + time_feat] + [net_dim + in_feat + time_feat if i == 5 else net_dim for i in range(1, 8)]
+    for i, k in enumerate(ins):
+        sd[f"layers.{i}.0.weight"] = _he(rng, net_dim, k)
+        sd[f"layers.{i}.0.bias"] = (rng.standard_normal(net_dim) * bias_scale).astype(np.float32)
+    sd["density.0.weight"] = (_he(rng, 1, net_dim) * 0.5).astype(np.float32)
+    sd["density.0.bias"] = np.full((1,), density_bias, np.float32)
+    sd["feature.0.weight"] = _he(rng, net_dim, net_dim)
+    sd["feature.0.bias"] = (rng.standard_normal(net_dim) * bias_scale).astype(np.float32)
+    sd["layer_9.0.weight"] = _he(rng, net_dim // 2, net_dim + dir_feat)
+    sd["layer_9.0.bias"] = (rng.standard_normal(net_dim // 2) * bias_scale).astype(np.float32)
+    sd["color.0.weight"] = _he(rng, 3, net_dim // 2)
+    sd["color.0.bias"] = (rng.standard_normal(3) * bias_scale).astype(np.float32)
+    return sd
+
+
 def pose_spherical(theta_deg, phi_deg, radius):
     """c2w [4,4] float32 on a sphere looking at the origin (load_blender.py:11-35)."""
     th, ph = np.deg2rad(theta_deg), np.deg2rad(phi_deg)
