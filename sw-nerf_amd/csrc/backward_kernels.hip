@@ -11,7 +11,6 @@
 #include "wave_dpp.h"
 #include "host_util.h"
 #include <type_traits>
-#include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -269,9 +268,7 @@ __global__ void __launch_bounds__(512, 4) gemm_tn_kernel(GemmTN P) {
 // slab.  Wave w owns the 64 x 64 block o in [64(w&3), +64), i in [64(w>>2), +64) as 2 x 2 accumulator tiles:
 // 4 LDS reads per 4 MFMAs.
 #define GD_SLAB 32
-#ifndef GD_RIDER_UNR
 #define GD_RIDER_UNR 4                    // k-pairs unrolled in an item with a rider
-#endif
 #define GD_BUF_FLOATS (2 * GD_SLAB * 256)            // A slab then B slab
 #define GD_B2_FLOATS (GD_SLAB * 64)                  // optional second B operand, <= 64 columns
 #define GD_A2_FLOATS (GD_SLAB * 32)                  // optional second A operand, <= 32 columns (zero padded)
@@ -370,8 +367,6 @@ __device__ __forceinline__ void gemm_dma_body(const GemmFused& F, const int slic
     const int ot2 = 32 * (w & 7), it2 = 32 * (w >> 3);       // B2 rider: this wave's 32 x 32 tile of C2
     issue(0);
     if (HB2 || HA2) { rider_load(0); rider_store(0); }
-    // -DGEMM_EXP_* (tools/experiments/gemm/build.sh; timing experiments, WRONG results, never the shipped library):
-    // NOBARRIER no slab barrier | NODMA only the first two slabs are ever fetched | NOVALU no row masks / bias sums | NOEPI no atomics
     // The WHOLE slab loop once per bias role (the test in front of it, not inside: with two copies of the unrolled steps inside the
     // loop hipcc keeps accumulator tiles alive across both and spills 150+ registers at this kernel's 128-register budget - as in
     // narrow5_kernel).  Both copies execute the same barriers.
@@ -380,9 +375,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmFused& F, const int slic
 #pragma nounroll
     for (int sl = 0; sl < nslab; ++sl) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of slab sl has landed ...
-#ifndef GEMM_EXP_NOBARRIER
         __syncthreads();                                      // ... everyone's has; and everyone is done with slab sl-1
-#endif
         float* Abw = gd_lds + (sl & 1) * GD_BUF_FLOATS;
         const int valid = mlen - sl * GD_SLAB;                // rows of this slab inside the slice (>= 32: all)
         if (valid < GD_SLAB) {
@@ -409,11 +402,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmFused& F, const int slic
         if (HB2) asm("" : "+v"(e1o));
         if (HA2) asm("" : "+v"(f0o));
         __builtin_amdgcn_sched_barrier(0);
-#ifdef GEMM_EXP_NODMA
-        if (sl + 1 < 2) {
-#else
         if (sl + 1 < nslab) {
-#endif
             issue(sl + 1);
             if (HB2 || HA2) rider_load(sl + 1);
         }
@@ -437,9 +426,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmFused& F, const int slic
                     a = A2p[nr]; b = B2p[nr];
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef GEMM_EXP_NOVALU
                 if (BIAS) asm("v_pk_add_f32 %0, %0, %1" : "+v"(bs01) : "v"(c));    // (hipcc splits a two-float vector add into two v_add_f32)
-#endif
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(c[0], d[0], acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(c[0], d[1], acc[1], 0, 0, 0);
                 acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(c[1], d[0], acc[2], 0, 0, 0);
@@ -453,9 +440,6 @@ __device__ __forceinline__ void gemm_dma_body(const GemmFused& F, const int slic
     }
     };
     if (do_bias) slabs(std::true_type{}); else slabs(std::false_type{});   // wave-uniform: only the four waves of the first column block own bias entries
-#ifdef GEMM_EXP_NOEPI
-    if (acc[0][0] + acc[1][1] + acc[2][2] + acc[3][3] + accb[0] + acca[0] + bs01[0] + bs01[1] + bs3 != 12345.678f) return;
-#endif
     // C/D map: register r of lane (j = i, h = hp) of tile (oa, ib) is row o0 + 2 frow(r,h) + oa, column i0 + 2 j + ib (interleaved tiles)
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -710,7 +694,7 @@ extern "C" int swnerf_gemm_tn_group(const swnerf_gemm_item* items, int n_items, 
         if (q.B2 && (!q.C2 || q.Ni2 < 1 || q.Ni2 > 64 || q.ldb2 < q.Ni2 || q.ldc2 < q.Ni2)) return sw_fail(SWNERF_E_ARG, "gemm_tn_group: item %d: bad B2 rider", k);
         if (q.A2 && (!q.C3 || q.No2 < 1 || q.No2 > 32 || q.lda2 < q.No2 || q.ldc3 < 256)) return sw_fail(SWNERF_E_ARG, "gemm_tn_group: item %d: bad A2 rider", k);
         const bool aligned = (q.lda % 4 == 0) && (q.ldb % 4 == 0) && (((uintptr_t)q.A | (uintptr_t)q.B) % 16 == 0);
-        if (!aligned || M < 4096 || (q.B2 && q.A2) || G.n == GG_MAX || getenv("SWNERF_GEMM_GROUP_OFF") != nullptr) {
+        if (!aligned || M < 4096 || (q.B2 && q.A2) || G.n == GG_MAX) {
             int rc = single(q);
             if (rc) return rc;
             continue;
@@ -719,9 +703,7 @@ extern "C" int swnerf_gemm_tn_group(const swnerf_gemm_item* items, int n_items, 
         F.g.A = q.A; F.g.lda = q.lda; F.g.No = 256; F.g.B = q.B; F.g.ldb = q.ldb; F.g.Ni = 256; F.g.C = q.C; F.g.ldc = q.ldc; F.g.bias = q.bias; F.g.M = M;
         F.B2 = q.B2; F.ldb2 = q.ldb2; F.Ni2 = q.Ni2; F.C2 = q.C2; F.ldc2 = q.ldc2;
         F.A2 = q.A2; F.lda2 = q.lda2; F.No2 = q.No2; F.C3 = q.C3; F.ldc3 = q.ldc3; F.bias3 = q.bias3;
-        static const int rider_w = getenv("SWNERF_GG_RIDER_W") ? atoi(getenv("SWNERF_GG_RIDER_W")) : 12;
-        static const int plain_w = getenv("SWNERF_GG_PLAIN_W") ? atoi(getenv("SWNERF_GG_PLAIN_W")) : 8;
-        weight[G.n] = (q.B2 || q.A2) ? rider_w : plain_w;         // 5 MFMAs per 4 and a shorter unroll: 1.2-1.3x alone, 6 : 4 measured best in a group
+        weight[G.n] = (q.B2 || q.A2) ? 12 : 8;                  // 5 MFMAs per 4 and a shorter unroll: 1.2-1.3x alone, 6 : 4 measured best in a group
         any_b2 |= q.B2 != nullptr; any_a2 |= q.A2 != nullptr;
         ++G.n;
     }
@@ -766,7 +748,7 @@ extern "C" int swnerf_gemm_tn(const float* A, int lda, int No, const float* B, i
         return gemm_dma_launch(F, stream);
     }
     // skinny shapes with 16-byte aligned operands: the double-buffered LDS-DMA kernel with the wave grid that covers C
-    if (aligned && No % 4 == 0 && Ni % 4 == 0 && M >= 4096 && getenv("SWNERF_GEMM_NARROW_OLD") == nullptr) {
+    if (aligned && No % 4 == 0 && Ni % 4 == 0 && M >= 4096) {
         if (No <= 32 && Ni <= 128) return gemm_tiled_launch<1, 1, 1, 4>(P, stream);     // rgb_linear 4 x 128
         if (No <= 32 && Ni <= 256) return gemm_tiled_launch<1, 2, 1, 4>(P, stream);     // _time_out 4 x 256
         if (No <= 128 && Ni <= 32) return gemm_tiled_launch<1, 1, 4, 1>(P, stream);     // views_linears.0, gamma(d) slots 128 x 32
@@ -979,9 +961,7 @@ __global__ void __launch_bounds__(1024) narrow5_kernel(Narrow5 P) {
 #pragma nounroll
         for (int sl = 0; sl < nslab; ++sl) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of slab sl has landed ...
-#ifndef N5_EXP_NOBARRIER                                          // (-DN5_EXP_*: timing experiments, WRONG results - tools/probe_n5_exp.py)
             __syncthreads();                                      // ... everyone's has; and everyone is done with slab sl-1
-#endif
             const int valid = mlen - sl * N5_SLAB;
             const int buf = (sl & 1) * N5_BUF;
             if (valid < N5_SLAB) {
@@ -992,14 +972,8 @@ __global__ void __launch_bounds__(1024) narrow5_kernel(Narrow5 P) {
                 if (t < (N5_SLAB - valid) * 4) n5_lds[buf + N5_A2 + valid * 4 + t] = 0.f;
                 __syncthreads();
             }
-#ifdef N5_EXP_NODMA
-            if (sl + 1 < 2) issue(sl + 1);
-#else
             if (sl + 1 < nslab) issue(sl + 1);
-#endif
-#ifndef N5_EXP_NOMFMA
             n5_slab<AP, BP, NA, NB>(n5_lds, buf + asrc + i + hp * AP, buf + bsrc + i + hp * BP, acol, bcol, acc, bs0, bs2, bias);
-#endif
         }
     };
     using std::integral_constant;
@@ -1061,9 +1035,7 @@ extern "C" int swnerf_canon_narrow_grads(const float* grad, int ldg, const float
 // Measured (profiles/r04/narrow_plan.md): the deformation net's set 183 us per 196 608-row chunk in ONE launch on the main stream
 // against ~205 us for its three skinny GEMMs; the no-view net's set 304 us against 254 us - two padded products on 8 of 16 waves
 // are matrix-pipe bound there (16 + 8 tiles of 64-cycle MFMAs per row pair on four SIMDs) - so that net keeps its GEMMs.
-#ifndef NP_SLAB
 #define NP_SLAB 16                // rows per slab (32 fit the LDS for the plans below but measured 5-10 % slower: profiles/r04/narrow_plan.md)
-#endif
 #define NP_MAX_OPS 4
 #define NP_MAX_JOBS 5
 struct NpOp { const float* ptr; int ld; int width; int lds_off; int kib; };      // width: floats staged per row (multiple of 4); kib: 1-KiB pieces per slab image
@@ -1201,6 +1173,7 @@ struct NpBuilder {
         return n_ops++;
     }
     // shape: 1 = 256-wide A x xs, 2 x 2 block | 2 = 256-wide A x xs, 4 x 1 | 3 = 4-column A x 256-wide B, 1 x 4 | 4 = 8-column A x 256-wide B, 1 x 4
+    // (no plan uses shape 4 at present: it served the no-view net, which keeps its GEMMs)
     NpWave& wave(int w, int shape, int a_op, int b_op, float* C, int ldc, int rlim) {
         NpWave& R = P.wave[w];
         R.shape = (short)shape; R.a_op = (short)a_op; R.b_op = (short)b_op; R.C = C; R.ldc = ldc; R.rlim = (short)rlim;
@@ -1261,32 +1234,6 @@ extern "C" int swnerf_deform_narrow_grads(const float* grad_d, int ldg, const fl
         if (w == 6) { R.bias = b4; R.bias_mask = 0x1; R.bias_lim = 4; }
     }
     return B.launch("deform_narrow_grads launch", stream);
-}
-
-// The net without view directions (model.py:59-60), fused training pass:
-//   c0s [256, 64] += d pre_0^T . xs[:, :64]       pts_linears.0, gamma(x) slots      b_l0 [256] += column sums of d pre_0
-//   w8  [8, 256]  += d_raw8^T . h7                output_linear = rows 0..out_ch-1   b8 [8] += column sums of d_raw8
-// grad / act: [M, ld >= 2048 + ...] as above, xs [M, 96], d_raw8 [M, 8] (columns >= out_ch zero).
-extern "C" int swnerf_noview_narrow_grads(const float* grad, int ldg, const float* act, int lda, const float* xs, const float* d_raw8, int64_t M,
-                                          float* c0s, float* w8, float* b_l0, float* b8, void* stream) {
-    if (M == 0) return 0;
-    if (!grad || !act || !xs || !d_raw8 || !c0s || !w8 || M < 0 || ldg < SW_ACT_LD || lda < SW_ACT_LD)
-        return sw_fail(SWNERF_E_ARG, "noview_narrow_grads: NULL pointer, negative M or a leading dimension below %d", SW_ACT_LD);
-    if (!np_aligned(grad) || !np_aligned(act) || !np_aligned(xs) || !np_aligned(d_raw8) || ldg % 4 || lda % 4)
-        return sw_fail(SWNERF_E_ARG, "noview_narrow_grads: operands must be 16-byte aligned with leading dimensions that are multiples of 4");
-    NpBuilder B(M);
-    const int o_g = B.op(grad, ldg, 256), o_x = B.op(xs, SW_XS_LD, SW_XS_LD), o_h = B.op(act + 1792, lda, 256), o_d = B.op(d_raw8, 8, 8);
-    for (int w = 0; w < 4; ++w) {
-        NpWave& R = B.wave(w, 1, o_g, o_x, c0s, 64, 256);
-        for (int k = 0; k < 4; ++k) { R.acol[k] = (short)(64 * w + 32 * (k >> 1)); R.bcol[k] = (short)(32 * (k & 1)); }
-        R.bias = b_l0; R.bias_mask = 0x5;
-    }
-    for (int w = 4; w < 6; ++w) {                                                // output_linear: d raw (8 columns) x h7 tiles 4(w-4)..+3
-        NpWave& R = B.wave(w, 4, o_d, o_h, w8, 256, 8);
-        for (int k = 0; k < 4; ++k) { R.acol[k] = 0; R.bcol[k] = (short)(128 * (w - 4) + 32 * k); }
-        if (w == 4) { R.bias = b8; R.bias_mask = 0x1; R.bias_lim = 8; }
-    }
-    return B.launch("noview_narrow_grads launch", stream);
 }
 
 // ---------------------------------------------------------------------------------------------

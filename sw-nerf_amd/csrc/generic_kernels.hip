@@ -18,7 +18,6 @@
 #include "../../include/swnerf.h"
 #include "host_util.h"
 #include "elu.h"
-#include <cstdlib>
 #include <cstdint>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -248,7 +247,7 @@ static int generic_launch(const GenericGemm& P, bool bt, void* stream, const cha
     if (P.M == 0) return 0;
     if (!P.A || !P.B || !P.C || P.M < 0 || P.N < 1 || P.K < 1 || P.lda < P.K || P.ldc < P.N || P.ldb < (bt ? P.K : P.N))
         return sw_fail(SWNERF_E_ARG, "%s: bad arguments (M=%lld N=%d K=%d lda=%d ldb=%d ldc=%d)", what, (long long)P.M, P.N, P.K, P.lda, P.ldb, P.ldc);
-    if (P.N >= 64 && P.M >= 128 && getenv("SWNERF_GENERIC_GEMM_OLD") == nullptr) {
+    if (P.N >= 64 && P.M >= 128) {
         const int64_t gx2 = (P.M + 127) / 128, gy2 = (P.N + 127) / 128;
         if (gx2 > 0x7fffffffLL || gy2 > 65535) return sw_fail(SWNERF_E_UNSUPP, "%s: M %lld or N %d too large for one launch", what, (long long)P.M, P.N);
         const dim3 grid2((unsigned)gx2, (unsigned)gy2), block2(256);

@@ -27,21 +27,6 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// -DSW_PROBE builds (tools/probe_segments.py; never the shipped library): shader-clock stamps around the parts of a
-// tile, accumulated per wave in SGPRs and written, as raw 64-bit counters, into the ray's `weights` row.
-#ifdef SW_PROBE
-__device__ __forceinline__ unsigned long long sw_clock() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define SW_STAMP(var) const unsigned long long var = sw_clock()
-#else
-#define SW_STAMP(var)
-#endif
-
 // The weight ring lives in LDS and is filled by LDS-DMA (`global_load_lds_dwordx4`: global ->
 // LDS with no VGPR destination): each wave owns SW_RING slots of 1 KiB and keeps SW_RING-1
 // steps in flight.  Why not a register ring: hipcc (ROCm 7.2) sinks plain prefetch loads next
@@ -174,9 +159,7 @@ __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)
             if constexpr (S % every == every - 1 && S / every < total) {
                 constexpr int idx = S / every, n2 = idx / 4, g = idx % 4;
                 const f32x4 v = {kin[n2][4 * g], kin[n2][4 * g + 1], kin[n2][4 * g + 2], kin[n2][4 * g + 3]};
-#ifndef TRAIN_EXP_NOSTORE
                 *reinterpret_cast<f32x4*>(ss.sp + 32 * n2 + 8 * g) = v;
-#endif
             }
             if constexpr (S == 1) {
                 if (ss.mp) *reinterpret_cast<f32x4*>(ss.mp) = ss.mv;      // wave-uniform condition
@@ -215,9 +198,6 @@ __device__ __forceinline__ void seg_mfma(f32x16 (&out)[NT], const f32x16 (&kin)[
 template <int NT>
 __device__ __forceinline__ f32x4 relu_bits(const f32x16 (&t)[NT]) {
     unsigned m[4] = {0u, 0u, 0u, 0u};
-#ifdef TRAIN_EXP_NOBITS                                  // (timing experiment, WRONG gradients: tools/experiments/train/build.sh)
-    return f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -573,9 +553,7 @@ __device__ __forceinline__ void canon_tail_train(const f32x16 (&in)[8], const fl
     for (int n = 0; n < 4; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) hv[n][r] = relu1(hv[n][r]);
-#ifndef TRAIN_EXP_NOBURST                               // (timing experiment: tools/experiments/train/build.sh)
     tiles_store<4>(act_row + SW_ACT_HV, hv);
-#endif
     *reinterpret_cast<f32x4*>(mask_tile + 256 * 8) = relu_bits<4>(hv);
     head_valu<3, 4>(hv, ws, rgb);
     rgb[0] += hb_rgb[1]; rgb[1] += hb_rgb[2]; rgb[2] += hb_rgb[3];

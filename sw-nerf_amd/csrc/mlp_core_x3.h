@@ -27,9 +27,7 @@
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef X3_AHEAD
 #define X3_AHEAD 2        // A operands are read from LDS this many groups ahead of their MFMAs
-#endif
 #define X3_NSLOT 6
 #define X3_GROUP_BYTES 2048
 #define X3_CHUNK_GROUPS 8
@@ -47,17 +45,9 @@ struct XStream {
     const char* rd;          // LDS: ring_lane + rslot * X3_CHUNK_BYTES
     const char* rd_next;     // ... of the chunk after it
     u32x4 ahi, alo;          // A operands of the CURRENT group (already read from LDS)
-    u32x4 a2hi, a2lo;        // ... of the group after it (X3_AHEAD == 2)
+    u32x4 a2hi, a2lo;        // ... of the group after it
     const float* bias;       // LDS: this lane half's 16 accumulator-init values of the current output tile
-#ifdef SW_PROBE
-    unsigned long long pc[3];   // cycles in: MFMA segments | accumulator -> (hi, lo) splits + heads | gamma(x) evaluations
-#endif
 };
-#ifdef SW_PROBE
-#define X3_PROBE(i, t0) xs.pc[i] += sw_clock() - t0
-#else
-#define X3_PROBE(i, t0)
-#endif
 
 // One chunk = 4 DMA instructions per wave.  Back to back they stall the wave while the matrix pipe runs dry (each
 // waits for the address path), so in the steady state they go out ONE PER GROUP, each behind a group's MFMAs
@@ -70,9 +60,7 @@ __device__ __forceinline__ const char* x3_uniform(const char* p) {
     return reinterpret_cast<const char*>((size_t)(((unsigned long long)hi << 32) | lo));
 }
 __device__ __forceinline__ void x3_issue_part(XStream& xs, int i) {
-#ifndef X3_EXP_NODMA                             // timing experiment: only the priming chunks are ever loaded
     ws_dma(x3_uniform(xs.gnext) + i * 1024, xs.voff, __builtin_amdgcn_readfirstlane(xs.idst) + i * 1024);
-#endif
     if (i == 3) xs.gnext += X3_CHUNK_BYTES;
 }
 __device__ __forceinline__ void x3_issue_begin(XStream& xs) {
@@ -89,9 +77,7 @@ __device__ __forceinline__ void x3_issue(XStream& xs) {
 // the workgroup barrier alone: no fence, no drain of the DMA queue (which __syncthreads() would add)
 __device__ __forceinline__ void x3_barrier() {
     __builtin_amdgcn_sched_barrier(0);
-#ifndef X3_EXP_NOBARRIER                         // timing experiments only (tools/experiments/x3): results are then garbage
     asm volatile("s_barrier" ::: "memory");
-#endif
     __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -110,9 +96,6 @@ __device__ __forceinline__ void x3_start(XStream& xs, const char* w, const float
     xs.rd = xs.ring_lane;
     xs.rd_next = xs.ring_lane;
     xs.bias = lds_bias + (lane >> 5) * 16;
-#ifdef SW_PROBE
-    xs.pc[0] = xs.pc[1] = xs.pc[2] = 0ull;
-#endif
     // the steady state (x3_groups) begins the refill round of chunk q + X3_NSLOT - 1 at group 7 - X3_AHEAD of chunk q and
     // issues its 4 parts behind 4 consecutive groups, so a round straddles the chunk boundary: enter that state as if
     // chunk -1 had just begun the round of chunk X3_NSLOT - 2 and issued the parts that precede group 0
@@ -129,9 +112,7 @@ __device__ __forceinline__ void x3_start(XStream& xs, const char* w, const float
 
 // At group 6 of the chunk being read: publish the next chunk, free the previous one's slot and refill it.
 __device__ __forceinline__ void x3_advance(XStream& xs) {
-#ifndef X3_EXP_NOWAIT
     ws_wait<4 * (X3_NSLOT - 3)>();           // own quarter of the NEXT chunk has landed (the X3_NSLOT-3 behind it may fly)
-#endif
     x3_barrier();
     x3_issue_begin(xs);                      // the slot of the PREVIOUS chunk: every wave is past it (parts: x3_groups)
     const unsigned ns = (xs.rslot + 1 == X3_NSLOT) ? 0u : xs.rslot + 1;
@@ -152,18 +133,17 @@ __device__ __forceinline__ unsigned x3_cvt_pk(float a, float b) {       // [bf16
     return r;
 }
 
-// 16 fp32 values of a lane (one accumulator / embedding tile) -> two k-blocks of (hi, lo) B operands
 // `floor`: 0 for a ReLU layer, -inf for none (one v_max_f32 either way; see relu1 for why it is spelled in asm)
 __device__ __forceinline__ float x3_floor(float x, float floor) {
     float y;
     asm("v_max_f32_e32 %0, %1, %2" : "=v"(y) : "v"(floor), "v"(x));
     return y;
 }
-template <bool FLOOR>
-__device__ __forceinline__ void x3_split(const f32x16& v, u32x4& hi0, u32x4& lo0, u32x4& hi1, u32x4& lo1, float floor = 0.f) {
+// 16 fp32 values of a lane (one embedding tile) -> two k-blocks of (hi, lo) B operands
+__device__ __forceinline__ void x3_split(const f32x16& v, u32x4& hi0, u32x4& lo0, u32x4& hi1, u32x4& lo1) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-        const float a = FLOOR ? x3_floor(v[2 * q], floor) : v[2 * q], b = FLOOR ? x3_floor(v[2 * q + 1], floor) : v[2 * q + 1];
+        const float a = v[2 * q], b = v[2 * q + 1];
         const unsigned h2 = x3_cvt_pk(a, b);
         const float ra = a - __uint_as_float(h2 << 16), rb = b - __uint_as_float(h2 & 0xffff0000u);
         const unsigned l2 = x3_cvt_pk(ra, rb);
@@ -200,11 +180,7 @@ __device__ __forceinline__ void x3_groups(f32x16 (&acc)[NT], const u32x4 (&bhi)[
             }
         }
         if constexpr (g == X3_CHUNK_GROUPS - 1) xs.rd = xs.rd_next;
-#if X3_AHEAD == 2
         xs.ahi = xs.a2hi; xs.alo = xs.a2lo; xs.a2hi = nhi; xs.a2lo = nlo;
-#else
-        xs.ahi = nhi; xs.alo = nlo;
-#endif
         x3_groups<G + 1, NG, NT, KB0, TERMS, NB>(acc, bhi, blo, xs);
     }
 }
@@ -241,206 +217,8 @@ __device__ __forceinline__ float x3_head_part(const f32x16& x, const float* wt, 
     return acc;
 }
 
-// The canonical net on one 32-row tile at positions (px,py,pz); lds_dir: the parked gamma(d) tile of the ray.
-// On return sigma / rgb[3] = the raw outputs of row j on every lane (model.py:49-58).
-// Register budget (one wave per SIMD, 256 VGPR + 256 AGPR): 128 accumulators + 128 registers of (hi, lo) activations
-// are the floor; gamma(x) is therefore not kept for the skip layer but evaluated again in front of it (3 % of a
-// tile's VALU work, no LDS), and gamma(d) is fetched just before the view layer.
-template <int TERMS>
-__device__ __forceinline__ void x3_canon(float px, float py, float pz, int h, const float* lds_dir, int lane,
-                                         float& sigma, float (&rgb)[3], XStream& xs) {
-    u32x4 bhi[16], blo[16];
-    f32x16 acc[8];
-    {   // pts_linears[0] on gamma(x)
-        SW_STAMP(q1);
-        f32x16 emb[2];
-        pe_pos(px, py, pz, h, emb);
-        u32x4 ehi[4], elo[4];
-        x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-        x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
-        X3_PROBE(2, q1);
-        SW_STAMP(q2);
-        x3_seg<8, 0, 4, SEG_BIAS, TERMS>(acc, ehi, elo, xs);
-        X3_PROBE(0, q2);
-        SW_STAMP(q3);
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            x3_split<true>(acc[n], bhi[2 * n], blo[2 * n], bhi[2 * n + 1], blo[2 * n + 1], 0.f);
-            __builtin_amdgcn_sched_barrier(0);                  // tile by tile (register pressure)
-        }
-        X3_PROBE(1, q3);
-    }
-    const float* hb = nullptr;
-    // pts_linears[1..7] share ONE body: the accumulators then have one home in the register file (three differently shaped bodies
-    // in one loop made the compiler shuffle 48 of them through scratch).  feature_linear is folded into the view layer (round 4,
-    // swnerf_common.h SW_CANON_STEPS): the view layer below runs on the split of relu(h_7) with the folded weights.
-#pragma nounroll
-    for (int l = 1; l <= 7; ++l) {
-        SW_STAMP(q0);
-        x3_seg<8, 0, 16, SEG_BIAS, TERMS>(acc, bhi, blo, xs);
-        X3_PROBE(0, q0);
-        if (l == 5) {                                               // cat[input_pts, h] (model.py:45-46): ... then gamma(x),
-            SW_STAMP(q1);                                           // evaluated again HERE: hoisted it would sit in scratch
-            f32x16 emb[2];                                          // across layers 1..4 and a scratch reload drains the DMA ring
-            asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
-            pe_pos(px, py, pz, h, emb);
-            u32x4 ehi[4], elo[4];
-            x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-            x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
-            X3_PROBE(2, q1);
-            SW_STAMP(q2);
-            x3_seg<8, 0, 4, SEG_ACC, TERMS>(acc, ehi, elo, xs);
-            X3_PROBE(0, q2);
-        }
-        SW_STAMP(q3);
-        if (l == 7) {
-            // alpha_linear on relu(h_7) in fp32, before the split: 8 weight tiles, then the head-bias tile
-            float s = 0.f;
-#pragma unroll
-            for (int n = 0; n < 8; ++n) {
-                f32x16 t;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t[r] = relu1(acc[n][r]);
-                s = x3_head_part(t, xs.bias + n * SW_BIAS_TILE_FLOATS, s);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            s += __shfl_xor(s, 32, 64);
-            sigma = s + xs.bias[8 * SW_BIAS_TILE_FLOATS];
-            hb = xs.bias + 8 * SW_BIAS_TILE_FLOATS;                 // [b_alpha, b_r, b_g, b_b]
-            xs.bias += 9 * SW_BIAS_TILE_FLOATS;
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            x3_split<true>(acc[n], bhi[2 * n], blo[2 * n], bhi[2 * n + 1], blo[2 * n + 1], 0.f);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        X3_PROBE(1, q3);
-    }
-    f32x16 hv[4];
-    SW_STAMP(q6);
-    x3_seg<4, 0, 16, SEG_BIAS, TERMS>(hv, bhi, blo, xs);           // views_linears[0] . feature_linear (folded) on relu(h_7) ...
-    X3_PROBE(0, q6);
-    {
-        f32x16 demb;
-        tile_fetch(lds_dir, lane, demb);
-        u32x4 dhi[2], dlo[2];
-        x3_split<false>(demb, dhi[0], dlo[0], dhi[1], dlo[1]);
-        SW_STAMP(q7);
-        x3_seg<4, 0, 2, SEG_ACC, TERMS>(hv, dhi, dlo, xs);         // ... then gamma(d)
-        X3_PROBE(0, q7);
-    }
-    SW_STAMP(q8);
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        float s = 0.f;
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            f32x16 t;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t[r] = relu1(hv[n][r]);
-            s = x3_head_part(t, xs.bias + (o * 4 + n) * SW_BIAS_TILE_FLOATS, s);
-        }
-        rgb[o] = s + __shfl_xor(s, 32, 64) + hb[1 + o];
-    }
-    X3_PROBE(1, q8);
-}
-
-// DirectTemporalNeRF (model.py:128-151) on one 32-row tile: ONE body for both nets, like the fp32 kernel - `deform`
-// selects the deformation net (layer 0 also takes gamma(t); 7 more layers; head = _time_out, 3 outputs in head[]) or the
-// canonical net (as x3_canon; head[0] = sigma, rgb[]).  gamma(d) is evaluated here from the view direction (no LDS tile:
-// the two bias-tile sets need its room).
-template <int TERMS>
-__device__ __forceinline__ void x3_net_dn(float px, float py, float pz, float ft, bool deform, int h, float v0, float v1, float v2,
-                                          float (&head)[3], float (&rgb)[3], XStream& xs) {
-    u32x4 bhi[16], blo[16];
-    f32x16 acc[8];
-    {
-        f32x16 emb[2];
-        asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
-        pe_pos(px, py, pz, h, emb);
-        u32x4 ehi[6], elo[6];
-        x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-        x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
-        if (deform) {                                               // cat[new_pts, t] (model.py:129)
-            f32x16 te;
-            pe_time(ft, h, te);
-            x3_split<false>(te, ehi[4], elo[4], ehi[5], elo[5]);
-            x3_seg<8, 0, 6, SEG_BIAS, TERMS>(acc, ehi, elo, xs);
-        } else {
-            x3_seg<8, 0, 4, SEG_BIAS, TERMS>(acc, ehi, elo, xs);
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            x3_split<true>(acc[n], bhi[2 * n], blo[2 * n], bhi[2 * n + 1], blo[2 * n + 1], 0.f);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    const float* hb = nullptr;
-#pragma nounroll
-    for (int l = 1; l <= 7; ++l) {                                  // (feature_linear is folded into the canonical net's view layer)
-        x3_seg<8, 0, 16, SEG_BIAS, TERMS>(acc, bhi, blo, xs);
-        if (l == 5) {
-            f32x16 emb[2];
-            asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
-            pe_pos(px, py, pz, h, emb);
-            u32x4 ehi[4], elo[4];
-            x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-            x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
-            x3_seg<8, 0, 4, SEG_ACC, TERMS>(acc, ehi, elo, xs);
-        }
-        if (l == 7) {
-            // the head on relu(h_7) in fp32: alpha_linear (1 output) or _time_out (3), weight tiles then the head-bias tile
-            const int nout = deform ? 3 : 1;
-#pragma nounroll
-            for (int o = 0; o < nout; ++o) {
-                float s = 0.f;
-#pragma unroll
-                for (int n = 0; n < 8; ++n) {
-                    f32x16 t;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t[r] = relu1(acc[n][r]);
-                    s = x3_head_part(t, xs.bias + (o * 8 + n) * SW_BIAS_TILE_FLOATS, s);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                s += __shfl_xor(s, 32, 64);
-                const float v = s + xs.bias[nout * 8 * SW_BIAS_TILE_FLOATS + o];
-                if (o == 0) head[0] = v; else if (o == 1) head[1] = v; else head[2] = v;
-            }
-            hb = xs.bias + nout * 8 * SW_BIAS_TILE_FLOATS;           // canonical: [b_alpha, b_r, b_g, b_b]
-            xs.bias += (nout * 8 + 1) * SW_BIAS_TILE_FLOATS;
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            x3_split<true>(acc[n], bhi[2 * n], blo[2 * n], bhi[2 * n + 1], blo[2 * n + 1], 0.f);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if (deform) return;
-    f32x16 hv[4];
-    x3_seg<4, 0, 16, SEG_BIAS, TERMS>(hv, bhi, blo, xs);
-    {
-        f32x16 demb;
-        pe_dir(v0, v1, v2, h, demb);
-        u32x4 dhi[2], dlo[2];
-        x3_split<false>(demb, dhi[0], dlo[0], dhi[1], dlo[1]);
-        x3_seg<4, 0, 2, SEG_ACC, TERMS>(hv, dhi, dlo, xs);
-    }
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        float s = 0.f;
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            f32x16 t;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t[r] = relu1(hv[n][r]);
-            s = x3_head_part(t, xs.bias + (o * 4 + n) * SW_BIAS_TILE_FLOATS, s);
-        }
-        rgb[o] = s + __shfl_xor(s, 32, 64) + hb[1 + o];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// The same canonical net with the split phase HIDDEN under the matrix pipe (software pipeline across layers).
+// The canonical net with the split phase HIDDEN under the matrix pipe (software pipeline across layers).
 // With k-block-major order layer L+1 needs tile t of layer L's output (k-blocks 2t, 2t+1) only when it reaches them, so
 // the (hi, lo) split of tile t+1 - 8 pairs of values, ~10 VALU operations each - is spread over the 2*NT groups
 // (6*NT MFMAs) that consume tile t.  Layer L's accumulators therefore stay fp32 while layer L+1 runs: two accumulator
@@ -504,11 +282,7 @@ __device__ __forceinline__ void x3_pgroups(f32x16 (&dst)[NT], const f32x16 (&src
             }
         }
         if constexpr (g == X3_CHUNK_GROUPS - 1) xs.rd = xs.rd_next;
-#if X3_AHEAD == 2
         xs.ahi = xs.a2hi; xs.alo = xs.a2lo; xs.a2hi = nhi; xs.a2lo = nlo;
-#else
-        xs.ahi = nhi; xs.alo = nlo;
-#endif
         if constexpr (kb == 0 && n + 1 < NT) binit = bnext;
         if constexpr (j == 2 * NT - 1 && t + 1 < 8) cur = nxt;
         x3_pgroups<G + 1, NT, TERMS>(dst, src, floor, cur, nxt, binit, head_w, head_s, xs);
@@ -533,6 +307,8 @@ __device__ __forceinline__ void x3_player(f32x16 (&dst)[NT], const f32x16 (&src)
     xs.bias += NT * SW_BIAS_TILE_FLOATS;
 }
 
+// The canonical net on one 32-row tile at positions (px,py,pz); lds_dir: the parked gamma(d) tile of the ray.
+// On return sigma / rgb[3] = the raw outputs of row j on every lane (model.py:49-58).
 template <int TERMS>
 __device__ __forceinline__ void x3_canon_pipe(float px, float py, float pz, int h, const float* lds_dir, int lane,
                                               float& sigma, float (&rgb)[3], XStream& xs) {
@@ -542,8 +318,8 @@ __device__ __forceinline__ void x3_canon_pipe(float px, float py, float pz, int 
         f32x16 emb[2];
         pe_pos(px, py, pz, h, emb);
         u32x4 ehi[4], elo[4];
-        x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-        x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
+        x3_split(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
+        x3_split(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
         x3_seg<8, 0, 4, SEG_BIAS, TERMS>(A, ehi, elo, xs);
     }
     float hs = 0.f;
@@ -558,8 +334,8 @@ __device__ __forceinline__ void x3_canon_pipe(float px, float py, float pz, int 
             asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
             pe_pos(px, py, pz, h, emb);
             u32x4 ehi[4], elo[4];
-            x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-            x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
+            x3_split(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
+            x3_split(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
             x3_seg<8, 0, 4, SEG_ACC, TERMS>(B, ehi, elo, xs);
         }
         x3_player<8, TERMS>(A, B, 0.f, nullptr, dummy, 0, xs);
@@ -575,7 +351,7 @@ __device__ __forceinline__ void x3_canon_pipe(float px, float py, float pz, int 
         f32x16 demb;
         tile_fetch(lds_dir, lane, demb);
         u32x4 dhi[2], dlo[2];
-        x3_split<false>(demb, dhi[0], dlo[0], dhi[1], dlo[1]);
+        x3_split(demb, dhi[0], dlo[0], dhi[1], dlo[1]);
         x3_seg<4, 0, 2, SEG_ACC, TERMS>(hv, dhi, dlo, xs);                  // ... then gamma(d)
     }
 #pragma unroll
@@ -594,7 +370,8 @@ __device__ __forceinline__ void x3_canon_pipe(float px, float py, float pz, int 
 
 // DirectTemporalNeRF with the same software pipeline: `deform` selects the deformation net (layer 0 also takes gamma(t);
 // layers 1..7; head = _time_out on relu(h_7), computed on the spot - nothing follows to ride on) or the canonical net
-// (as x3_canon_pipe).  One body for both (see x3_net_dn).
+// (as x3_canon_pipe).  ONE body for both nets, like the fp32 kernel.  gamma(d) is evaluated here from the view direction
+// (no LDS tile: the two bias-tile sets need its room).
 template <int TERMS>
 __device__ __forceinline__ void x3_net_dn_pipe(float px, float py, float pz, float ft, bool deform, int h, float v0, float v1, float v2,
                                                float (&head)[3], float (&rgb)[3], XStream& xs) {
@@ -605,12 +382,12 @@ __device__ __forceinline__ void x3_net_dn_pipe(float px, float py, float pz, flo
         asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
         pe_pos(px, py, pz, h, emb);
         u32x4 ehi[6], elo[6];
-        x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-        x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
+        x3_split(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
+        x3_split(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
         if (deform) {
             f32x16 te;
             pe_time(ft, h, te);
-            x3_split<false>(te, ehi[4], elo[4], ehi[5], elo[5]);
+            x3_split(te, ehi[4], elo[4], ehi[5], elo[5]);
             x3_seg<8, 0, 6, SEG_BIAS, TERMS>(A, ehi, elo, xs);
         } else {
             x3_seg<8, 0, 4, SEG_BIAS, TERMS>(A, ehi, elo, xs);
@@ -625,8 +402,8 @@ __device__ __forceinline__ void x3_net_dn_pipe(float px, float py, float pz, flo
             asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
             pe_pos(px, py, pz, h, emb);
             u32x4 ehi[4], elo[4];
-            x3_split<false>(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
-            x3_split<false>(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
+            x3_split(emb[0], ehi[0], elo[0], ehi[1], elo[1]);
+            x3_split(emb[1], ehi[2], elo[2], ehi[3], elo[3]);
             x3_seg<8, 0, 4, SEG_ACC, TERMS>(B, ehi, elo, xs);
         }
         x3_player<8, TERMS>(A, B, 0.f, nullptr, dummy, 0, xs);
@@ -662,7 +439,7 @@ __device__ __forceinline__ void x3_net_dn_pipe(float px, float py, float pz, flo
         f32x16 demb;
         pe_dir(v0, v1, v2, h, demb);
         u32x4 dhi[2], dlo[2];
-        x3_split<false>(demb, dhi[0], dlo[0], dhi[1], dlo[1]);
+        x3_split(demb, dhi[0], dlo[0], dhi[1], dlo[1]);
         x3_seg<4, 0, 2, SEG_ACC, TERMS>(hv, dhi, dlo, xs);
     }
 #pragma unroll

@@ -123,7 +123,7 @@ template <bool DNERF, bool TRAIN> struct PassLds {
 };
 // PREC != 0 (bf16x3 / bf16 pass, mlp_core_x3.h): bias tiles | the workgroup's shared weight ring | per wave: gamma(d)
 // tile + depth slots | per wave: resampling scratch
-// (D-NeRF: both bias-tile sets, and no gamma(d) tile - x3_net_dn evaluates it - so that the resampling scratch still fits)
+// (D-NeRF: both bias-tile sets, and no gamma(d) tile - x3_net_dn_pipe evaluates it - so that the resampling scratch still fits)
 template <bool DNERF> struct X3Lds {
     static constexpr int BIAS = (DNERF ? SW_DEFORM_BIAS_TILES + SW_X3_CANON_BIAS_TILES : SW_X3_CANON_BIAS_TILES) * SW_BIAS_TILE_FLOATS;
     static constexpr int DIR = DNERF ? 0 : 16 * 64;
@@ -139,7 +139,6 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     static_assert(PREC == 0 || !TRAIN, "the bf16 paths cover the inference passes");
     static_assert(VIEWS || (!DNERF && PREC == 0), "the no-view-direction variant is a static fp32 pass (inference or TRAIN)");
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
-    SW_STAMP(probe_start);
     const swnerf_pass_args& a = P.a;
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -208,13 +207,8 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     float pr = 0.f, pg = 0.f, pb = 0.f, pd = 0.f, pa = 0.f;
     double Tc = 1.0;                              // transmittance carried across tiles
     const int ntiles = (S + 31) >> 5;
-#ifdef SW_PROBE
-    unsigned long long probe_acc[4] = {0ull, 0ull, 0ull, 0ull};
-    SW_STAMP(probe_loop0);
-#endif
 #pragma nounroll
     for (int tile = 0; tile < ntiles; ++tile) {
-        SW_STAMP(pt0);
         const int s = tile * 32 + j;
         const bool live = s < S && !ghost;
         const int sc = live ? s : S - 1;
@@ -240,7 +234,6 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         float head[3], rgb[3];
         float extra = 0.f;                          // VIEWS = false, out_ch == 5: the fifth channel of output_linear (only `raw` shows it)
         pe_pos(px, py, pz, h, emb);
-        SW_STAMP(pt1);
         if (DNERF && TRAIN) {
             // deformation net, then the canonical net on gamma(x + dx) (model.py:128-151); both save what their dX
             // chains and weight-gradient GEMMs need, as side stores (see the static branch below).  Always both passes:
@@ -281,11 +274,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             if constexpr (DNERF && PREC != 0) {
 #pragma nounroll
                 for (int pass = P.two_pass ? 0 : 1; pass < 2; ++pass) {
-#ifdef X3_NO_PIPE
-                    x3_net_dn<PREC>(px, py, pz, ft, pass == 0, h, v0, v1, v2, head, rgb, xs);
-#else
                     x3_net_dn_pipe<PREC>(px, py, pz, ft, pass == 0, h, v0, v1, v2, head, rgb, xs);
-#endif
                     if (pass == 0) {
                         const float ex = head[0], ey = head[1], ez = head[2];
                         if (a.dx && live && h == 0) {
@@ -353,11 +342,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             canon_tail_train(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws, act_row, mask_tile, mb);
         } else if constexpr (PREC != 0) {
             head[1] = 0.f; head[2] = 0.f;
-#ifdef X3_NO_PIPE                                   // the plain form (split phase between layers): experiments / reference
-            x3_canon<PREC>(px, py, pz, h, lds_dir, lane, head[0], rgb, xs);
-#else
             x3_canon_pipe<PREC>(px, py, pz, h, lds_dir, lane, head[0], rgb, xs);
-#endif
             x3_rewind(xs, SW_X3_CANON_CHUNKS, lds_bias, lane);
         } else if constexpr (!VIEWS) {
             trunk_pass<false, false, false, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws);
@@ -372,9 +357,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         } else {
             trunk_pass<false>(emb, lds_emb, 0.f, false, h, in, out, head, ws);
         }
-        SW_STAMP(pt2);
         if (!TRAIN && PREC == 0 && VIEWS) canon_tail(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws);
-        SW_STAMP(pt3);
         // back to the head of MAIN (behind the per-ray DIR prefix and its b_vf tiles)
         if constexpr (PREC == 0)                 // back to MAIN: behind the per-ray prefixes (DIR, and TIME with its 8 bias tiles)
             ws_rewind(ws, P.w0 + (P.dir_steps + P.time_steps) * SW_STEP_FLOATS,
@@ -419,12 +402,6 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         pb += w * (1.f / (1.f + expf(-c2)));
         pd += w * z;
         pa += w;
-#ifdef SW_PROBE
-        {
-            SW_STAMP(pt4);
-            probe_acc[0] += pt1 - pt0; probe_acc[1] += pt2 - pt1; probe_acc[2] += pt3 - pt2; probe_acc[3] += pt4 - pt3;
-        }
-#endif
     }
 
     pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
@@ -443,18 +420,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             a.disp_map[ray] = 1.f / ((q != q) ? q : fmaxf(1e-10f, q));
         }
     }
-#ifdef SW_PROBE
-    if (a.weights && lane == 0 && !ghost) {          // [sampling+encoding, trunk, tail, compositing, whole tile loop, prologue] cycles of this wave
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.weights + ray * S);
-        const unsigned long long pend = sw_clock();
-        o[0] = probe_acc[0]; o[1] = probe_acc[1]; o[2] = probe_acc[2]; o[3] = probe_acc[3]; o[4] = pend - probe_loop0; o[5] = probe_loop0 - probe_start;
-        if constexpr (PREC != 0) { o[6] = xs.pc[0]; o[7] = xs.pc[1]; o[8] = xs.pc[2]; }
-    }
-#endif
     if (!resample || ghost) return;
-#ifdef SW_PROBE
-    const unsigned long long probe_rs0 = sw_clock();
-#endif
 
     // ---- sample_pdf (ray.py:96-153) on bins = mid-points, weights[1:-1]; z_std; then sort (nerf/run.py:396-400, 416) as a rank
     // merge - the wave-level routines of resample.h, shared with the standalone op
@@ -466,11 +432,5 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         if (lane == 0) a.z_std[ray] = sd;
     }
     wave_rank_merge(zc, S, P.sort_s, srt, Ni, P.sort_n, a.z_fine + ray * (S + Ni), lane);
-#ifdef SW_PROBE
-    if (a.weights && lane == 0) {                    // [9] the resampling tail, [10] compositing epilogue .. its start
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(a.weights + ray * S);
-        o[9] = sw_clock() - probe_rs0;
-    }
-#endif
 }
 

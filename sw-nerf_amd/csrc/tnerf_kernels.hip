@@ -17,9 +17,7 @@
 #include "render_pass.h"
 #include "elu.h"
 
-#ifndef SW_TN_WAVES_PER_SIMD
 #define SW_TN_WAVES_PER_SIMD 2          // 4 accumulator tiles per activation: two waves per SIMD fit (DESIGN.md T-NeRF)
-#endif
 
 // LDS: the bias-style tiles | per wave: weight ring, parked gamma(x) (2 k-tiles), per-ray tiles T0 (4) T5 (4) DIR (2)
 #define SW_TN_WAVE_FLOATS (SW_RING * SW_STEP_FLOATS + 2 * 16 * 64 + SW_TN_PREFIX_BIAS_TILES * SW_BIAS_TILE_FLOATS)

@@ -58,7 +58,7 @@ class _NoBackward(torch.autograd.Function):
 
 
 # the weight-gradient machinery lives in wgrad.py; these names are part of what tests / tools reach through `model`
-from .wgrad import WeightGrads, _Fan, _Group, _gemm_tn, _gemm_tn_fused, _chunk_gemms, NARROW_FUSED, SW_ACT_HV  # noqa: E402,F401
+from .wgrad import WeightGrads, _Fan, _Group, _gemm_tn, _gemm_tn_fused, _chunk_gemms, SW_ACT_HV  # noqa: E402,F401
 
 
 class _MlpTrain(torch.autograd.Function):

@@ -119,7 +119,7 @@ class _FusedPassTrainDnerf(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_disp, g_acc, g_dx_up, _gz, g_raw):
-        from .wgrad import WeightGrads, _Fan, _chunk_gemms, NARROW_FUSED
+        from .wgrad import WeightGrads, _Fan, _chunk_gemms
         from . import render as _r
         rb, z, raw, dx, act, bits, xs, act_d, bits_d, xs_d, noise, *params = ctx.saved_tensors
         net, S = ctx.net, ctx.S
@@ -158,8 +158,7 @@ class _FusedPassTrainDnerf(torch.autograd.Function):
             a0, a1 = r0 * rows_per_ray, r1 * rows_per_ray
             _chunk_gemms(L, fan, m, [
                 lambda st_, part: wc.chunk(st_, m, grad[:m], act[a0:a1], xs[a0:a1], d_raw[:m], part=part),
-                lambda st_, part: wd.chunk(st_, m, grad_d[:m], act_d[a0:a1], xs_d[a0:a1], g_dx[:m], part=part)],
-                rest_on_main=[NARROW_FUSED, NARROW_FUSED])
+                lambda st_, part: wd.chunk(st_, m, grad_d[:m], act_d[a0:a1], xs_d[a0:a1], g_dx[:m], part=part)])
         g = wc.finish(st) + wd.finish(st)
         return (None,) * 8 + tuple(gi.to(p.dtype) for gi, p in zip(g, params))
 

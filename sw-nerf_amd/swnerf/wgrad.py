@@ -13,7 +13,6 @@ feature_linear: it has no activation (model.py:49-53) and every kernel runs it f
   d views_linears.0.weight[:, :256] = G W_f^T + db_hv (x) b_f,   d feature_linear.weight = Wv_f^T G,   d feature_linear.bias = Wv_f^T db_hv
 (swnerf_feature_finish; Wv_f = views_linears.0.weight[:, :256])."""
 import ctypes
-import os
 
 import torch
 
@@ -22,13 +21,7 @@ from . import _lib
 SW_ACT_HV = 2304          # csrc/swnerf_common.h: column of the view hidden layer in the act / grad rows
 SW_ACT_H7 = 1792          # ... of h7
 
-GEMM_STREAMS = int(os.environ.get("SWNERF_GEMM_STREAMS", "2"))    # side streams the weight-gradient GEMMs of a chunk fan out over (0/1: off)
-# SWNERF_GEMM_GROUP: 1 (default) = the 256 x 256 GEMMs of a chunk share a launch (_chunk_gemms); plain = the skip layer's GEMM
-# (gamma(x) rider: its workgroups run 1.2-1.3x longer) keeps its own launch; 0 = one launch per layer (profiles/r03/gemm_group.md)
-GEMM_GROUP = os.environ.get("SWNERF_GEMM_GROUP", "1") != "0"
-GROUP_RIDERS = os.environ.get("SWNERF_GEMM_GROUP", "1") != "plain"  # the skip layer's GEMM (gamma(x) rider) joins the group, at work weight 6 : 4
-NARROW_FUSED = os.environ.get("SWNERF_NARROW_FUSED", "1") != "0"     # a net's narrow weight-gradient products as one kernel
-NOVIEW_NARROW_FUSED = os.environ.get("SWNERF_NOVIEW_NARROW_FUSED", "0") == "1"
+GEMM_STREAMS = 2          # side streams the weight-gradient GEMMs of a chunk fan out over
 _SIDE_STREAMS = {}
 
 
@@ -43,23 +36,18 @@ class _Fan:
 
     def __init__(self, device):
         self.main = torch.cuda.current_stream(device)
-        n = GEMM_STREAMS if GEMM_STREAMS > 1 else 0
-        key = (device.index, n)
-        if key not in _SIDE_STREAMS:
-            _SIDE_STREAMS[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-        self.side = _SIDE_STREAMS[key]
+        if device.index not in _SIDE_STREAMS:
+            _SIDE_STREAMS[device.index] = [torch.cuda.Stream(device=device) for _ in range(GEMM_STREAMS)]
+        self.side = _SIDE_STREAMS[device.index]
         self.i = 0
 
     def fork(self):
-        if self.side:
-            ev = torch.cuda.Event()
-            ev.record(self.main)
-            for s in self.side:
-                s.wait_event(ev)
+        ev = torch.cuda.Event()
+        ev.record(self.main)
+        for s in self.side:
+            s.wait_event(ev)
 
     def next(self):
-        if not self.side:
-            return ctypes.c_void_p(self.main.cuda_stream)
         s = self.side[self.i % len(self.side)]
         self.i += 1
         return ctypes.c_void_p(s.cuda_stream)
@@ -115,32 +103,24 @@ def _gemm_tn_fused(L, st, M, A, a_col, B, b_col, C, c_col, bias, B2=None, b2_col
                                       off(A2, a2_col), ld(A2), No2, off(C3, 0), ld(C3), _lib.ptr(bias3), _st(st)), "gemm_tn_fused")
 
 
-def _chunk_gemms(L, fan, M, jobs, rest_on_main=False):
-    """The weight-gradient GEMMs of one row chunk.  jobs: callables job(st, part).  With SWNERF_GEMM_GROUP (default) the
-    rider-free 256 x 256 GEMMs of all jobs go out first as ONE launch on the main stream, alone on the chip (its workgroups
-    run ~2.5 ms each: next to another kernel they would start in rounds and finish in rounds, with half the chip idle in
-    between - measured +2.8 ms on the step without view directions), then the rest fans out over the side streams."""
-    if GEMM_GROUP:
-        grp = _Group(ctypes.c_void_p(fan.main.cuda_stream))
+def _chunk_gemms(L, fan, M, jobs, rest_on_main=True):
+    """The weight-gradient GEMMs of one row chunk.  jobs: callables job(st, part).  The 256 x 256 GEMMs of all jobs go out
+    first as ONE launch on the main stream, alone on the chip (its workgroups run ~2.5 ms each: next to another kernel they
+    would start in rounds and finish in rounds, with half the chip idle in between - measured +2.8 ms on the step without
+    view directions; grouping against one launch per layer: profiles/r03/gemm_group.md).  rest_on_main: the rest of every
+    job is ONE launch (the fused narrow kernels) and stays on the main stream, behind the group; otherwise the rest fans
+    out over the side streams."""
+    grp = _Group(ctypes.c_void_p(fan.main.cuda_stream))
+    for job in jobs:
+        job(grp, "plain")
+    grp.launch(L, M)
+    if rest_on_main:
         for job in jobs:
-            job(grp, "plain")
-        grp.launch(L, M)
-        # a job whose rest is ONE launch (the fused narrow kernels) keeps it on the main stream, behind the group; what is
-        # left fans out over the side streams
-        on_main = rest_on_main if isinstance(rest_on_main, (list, tuple)) else [rest_on_main] * len(jobs)
-        for job, m_ in zip(jobs, on_main):
-            if m_:
-                job(grp.st, "rest")
-        if all(on_main):
-            return
-        fan.fork()
-        for job, m_ in zip(jobs, on_main):
-            if not m_:
-                job(fan, "rest")
-    else:
-        fan.fork()
-        for job in jobs:
-            job(fan, "all")
+            job(grp.st, "rest")
+        return
+    fan.fork()
+    for job in jobs:
+        job(fan, "rest")
     fan.join()                                               # before the next chunk's backward kernel overwrites grad / d_raw
 
 
@@ -220,26 +200,22 @@ class WeightGrads:
 
     # -- one row chunk ---------------------------------------------------------------------------------------------------
     def chunk(self, st, M, grad, act, enc, draw, part="all", enc2=None):
-        """part: "plain" = the six rider-free 256 x 256 GEMMs only (for the chunk's grouped launch, _chunk_gemms), "rest" =
-        everything else, "all" = both."""
+        """part: "plain" = the seven 256 x 256 GEMMs only, the skip layer's with its gamma(x) rider (for the chunk's grouped
+        launch, _chunk_gemms), "rest" = everything else, "all" = both."""
         L, g, s, Cpos = self.L, self.g, self.s, self.Cpos
         e0 = 64 if self.fused else Cpos                          # width of the gamma(x) block of `enc`
         c5 = (s["c5s"], 0) if self.fused else (g[10], 0)         # where the skip layer's gamma(x) columns accumulate
-        l5 = lambda: _gemm_tn_fused(L, st, M, grad, 1280, act, 1024, g[10], Cpos, g[11], B2=enc, b2_col=0, Ni2=e0, C2=c5[0], c2_col=c5[1])
         if part != "rest":
             for l in (1, 2, 3, 4, 6, 7):
                 _gemm_tn(L, st, M, grad, 256 * l, 256, act, 256 * (l - 1), 256, g[2 * l], 0, g[2 * l + 1])
-            if part == "all" or GROUP_RIDERS:
-                l5()
+            _gemm_tn_fused(L, st, M, grad, 1280, act, 1024, g[10], Cpos, g[11], B2=enc, b2_col=0, Ni2=e0, C2=c5[0], c2_col=c5[1])
         if part == "plain":
             return
-        if part == "rest" and not GROUP_RIDERS:
-            l5()
         mm = lambda A, a_col, No, B, b_col, Ni, C, c_col, bias: _gemm_tn(L, st, M, A, a_col, No, B, b_col, Ni, C, c_col, bias)
         c0 = (s["c0s"], 0) if self.fused else (g[0], 0)
         aligned4 = draw.stride(0) == 4 and draw.data_ptr() % 16 == 0
         if self.kind == "canon":
-            if (self.fused and NARROW_FUSED and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
+            if (self.fused and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
                     and not (grad.data_ptr() | act.data_ptr() | enc.data_ptr()) % 16):
                 # the five narrow products below as ONE pass over the rows (csrc/backward_kernels.hip narrow5_kernel)
                 _lib.check(L.swnerf_canon_narrow_grads(_lib.ptr(grad), grad.stride(0), _lib.ptr(act), act.stride(0), _lib.ptr(enc), _lib.ptr(draw), M,
@@ -259,17 +235,12 @@ class WeightGrads:
                 mm(draw, 3, 1, act, SW_ACT_H7, 256, s["a4w"], 3 * 256, s["a4b"][3:])      # row 3 of the 4-row form
                 mm(draw, 0, 3, act, SW_ACT_HV, 128, s["rgb4w"], 0, s["rgb4b"])
         elif self.kind == "noview":
-            # (the fused kernel exists for this net too but measures slower than its two skinny GEMMs - 304 vs 254 us per 393 216-row
-            # chunk, profiles/r04/narrow_plan.md - so it is opt-in)
-            if (self.fused and NOVIEW_NARROW_FUSED and draw.stride(0) == 8 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
-                    and not (grad.data_ptr() | act.data_ptr() | enc.data_ptr() | draw.data_ptr()) % 16):
-                _lib.check(L.swnerf_noview_narrow_grads(_lib.ptr(grad), grad.stride(0), _lib.ptr(act), act.stride(0), _lib.ptr(enc), _lib.ptr(draw), M,
-                                                        _lib.ptr(s["c0s"]), _lib.ptr(s["w8"]), _lib.ptr(g[1]), _lib.ptr(s["b8"]), _st(st)), "noview_narrow_grads")
-                return
+            # (no fused kernel for this net: as one narrow_plan_kernel launch its two products measured slower than these two
+            # skinny GEMMs - 304 vs 254 us per 393 216-row chunk, profiles/r04/narrow_plan.md)
             mm(grad, 0, 256, enc, 0, e0, c0[0], c0[1], g[1])                               # pts_linears.0
             mm(draw, 0, 8, act, SW_ACT_H7, 256, s["w8"], 0, s["b8"])                       # output_linear (rows 0..out_ch-1)
         else:
-            if (self.fused and NARROW_FUSED and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
+            if (self.fused and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
                     and not (grad.data_ptr() | act.data_ptr() | enc.data_ptr()) % 16):
                 _lib.check(L.swnerf_deform_narrow_grads(_lib.ptr(grad), grad.stride(0), _lib.ptr(act), act.stride(0), _lib.ptr(enc), _lib.ptr(draw), M,
                                                         _lib.ptr(s["c0s"]), _lib.ptr(s["cts"]), _lib.ptr(s["w4"]), _lib.ptr(g[1]), _lib.ptr(s["b4"]), _st(st)),

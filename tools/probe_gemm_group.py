@@ -85,7 +85,7 @@ def timeit(name, f, flops):
     print(f"| {name} | {dt * 1e3:.3f} | {flops / dt / 1e12:.1f} |")
 
 
-print(f"M = {M} rows;  SWNERF_GG_RIDER_W={os.environ.get('SWNERF_GG_RIDER_W', '(5)')}")
+print(f"M = {M} rows")
 print("| what | ms | TFLOP/s (main 256x256 MFMA work only) |")
 print("|---|---|---|")
 timeit("one plain GEMM", lambda: plain(st, 1), FL)
