@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SWNERF_VERSION 111
+#define SWNERF_VERSION 112
 
 #define SWNERF_E_ARG      (-1)   /* bad size / NULL pointer / unsupported shape */
 #define SWNERF_E_UNSUPP   (-2)   /* valid in the reference, not built here (message says what) */
@@ -431,6 +431,31 @@ int swnerf_relu_mask(float* dy, const float* y, int64_t n, void* stream);
 int swnerf_linear_act(const float* x, int ldx, int64_t M, int K, const float* weight /*[N,K]*/, const float* bias /*[N]*/,
                       int N, int act, float* y, int ldy, void* stream);
 int swnerf_elu_grad(float* dy, const float* y, int64_t n, void* stream);
+
+/* ---- image-quality metrics (nerf/run.py calculate_metrics :49-61 = skimage.metrics PSNR / SSIM; d_nerf/metrics.ipynb
+ * MSE / PSNR / SSIM) --------------------------------------------------------------------------------------------------
+ * pred, gt: [n, h, w, 3] fp32 HWC RGB.  Per image: mse = mean((pred' - gt)^2) (squared fp32 differences summed in fp64),
+ * range = R, psnr = 10 log10(R^2 / mse), ssim = mean of the per-pixel S over every valid window position and the 3 channels
+ * (skimage's crop by 3 keeps exactly those pixels), with pred' = clip(pred, 0, 1) when clip_pred != 0.
+ *   SWNERF_SSIM_SKIMAGE  uniform 7x7 window, sample covariance (x 49/48)        structural_similarity(win_size=7, channel_axis=2)
+ *   SWNERF_SSIM_GAUSS11  11x11 Gaussian (sigma 1.5, normalised), population cov  metrics.ipynb SSIM
+ * C1 = (0.01 R)^2, C2 = (0.03 R)^2; R from range_mode:
+ *   SWNERF_RANGE_FIXED      fixed_range
+ *   SWNERF_RANGE_GT         per image gt.max() - gt.min() (a float32 difference, as in the reference)
+ *   SWNERF_RANGE_PRED_RULE  over the whole batch of pred': (max > 128 ? 255 : 1) - (min < -0.5 ? -1 : 0)
+ * NaN propagates like np.max / np.mean; R = 0 gives the IEEE values of the formulas.  h or w below the window is
+ * SWNERF_E_ARG.  ssim_map (may be NULL): [n, h-win+1, w-win+1, 3] the per-pixel S.  mse / psnr / range / ssim: DEVICE double [n].
+ * workspace: DEVICE, swnerf_metrics_workspace_bytes(n, h, w, mode) bytes (0 for arguments the call refuses).
+ * Four launches, no host synchronisation, no atomics: bit-identical from run to run. */
+#define SWNERF_SSIM_SKIMAGE 0
+#define SWNERF_SSIM_GAUSS11 1
+#define SWNERF_RANGE_FIXED     0
+#define SWNERF_RANGE_GT        1
+#define SWNERF_RANGE_PRED_RULE 2
+size_t swnerf_metrics_workspace_bytes(int64_t n, int64_t h, int64_t w, int mode);
+int swnerf_image_metrics(const float* pred, const float* gt, int64_t n, int64_t h, int64_t w, int mode, int range_mode,
+                         double fixed_range, int clip_pred, void* workspace, double* mse, double* psnr, double* range,
+                         double* ssim, float* ssim_map /* may be NULL */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,8 @@ LIB_PATH = os.path.join(_HERE, "libswnerf_hip.so")
 
 NET_CANON, NET_DNERF, NET_NOVIEW, NET_TNERF = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
+SSIM_SKIMAGE, SSIM_GAUSS11 = 0, 1
+RANGE_FIXED, RANGE_GT, RANGE_PRED_RULE = 0, 1, 2
 
 EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swnerf_pack_net", "swnerf_pack_net_noview", "swnerf_mlp_forward_noview",
            "swnerf_get_rays", "swnerf_ndc_rays", "swnerf_pack_ray_batch", "swnerf_raw2outputs", "swnerf_raw2outputs_backward",
@@ -25,7 +27,8 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_packed_x3_floats", "swnerf_pack_net_x3", "swnerf_render_pass_x3",
            "swnerf_packed_x3_floats_kind", "swnerf_pack_net_x3_kind",
            "swnerf_mc_workspace_bytes", "swnerf_mc_count", "swnerf_mc_emit",
-           "swnerf_linear_act", "swnerf_elu_grad"]
+           "swnerf_linear_act", "swnerf_elu_grad",
+           "swnerf_metrics_workspace_bytes", "swnerf_image_metrics"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -148,13 +151,17 @@ def lib():
     L.swnerf_mc_emit.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float,
                                  POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p, c_int64, c_int64,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.swnerf_metrics_workspace_bytes.restype = c_size_t
+    L.swnerf_metrics_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int]
+    L.swnerf_image_metrics.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_double, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
                         "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",
-                        "swnerf_mc_workspace_bytes"):
+                        "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes"):
             getattr(L, name).restype = c_int
-    if L.swnerf_version() != 111:
-        raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 111 - rebuild it "
+    if L.swnerf_version() != 112:
+        raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 112 - rebuild it "
                            "(python __graft_entry__.py)")
     _lib = L
     return L

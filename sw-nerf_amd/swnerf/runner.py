@@ -3,10 +3,17 @@ the render path - embedders, the network(s), the `network_query_fn` closure, Ada
 (render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer) exactly as the reference does, so a `train()`
 written against the reference only swaps its imports.  `args` is any object with the reference's option names
 (utils.py config_parser / run_dnerf.py config_parser); the closure is built inside the function, which is how
-`render.fused_plan` finds the encoders and sends `render_rays` to the fused HIP pass."""
+`render.fused_plan` finds the encoders and sends `render_rays` to the fused HIP pass.
+`render_test` and `evaluate_dir` are what follows the render path: the reference's scoring of test renders
+(nerf/run.py:557-596 with calculate_metrics :49-61, and the last cell of d_nerf/metrics.ipynb) on the GPU metrics."""
+import json
+import os
+
+import numpy as np
 import torch
 
-from . import render, render_dnerf, render_tnerf
+from . import metrics, render, render_dnerf, render_tnerf
+from .png import read_png
 from .checkpoint import reload_latest
 from .embedder import get_embedder
 from .model import vallina_NeRF, NeRF, TNeRF
@@ -140,3 +147,42 @@ def create_tnerf(args, device=None):
     test['perturb'] = False
     test['raw_noise_std'] = 0.
     return kw, test, start, grad_vars, optimizer
+
+
+def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, render_factor=0):
+    """nerf/run.py:557-596 (`--render_only --render_test`): render.render_path, then calculate_metrics(gt, pred) of every
+    frame (pred clipped to [0, 1], data_range = gt.max() - gt.min(), skimage's PSNR and 7x7 SSIM), all frames in one
+    batched GPU call.  Writes savedir/metrics.json = {"psnr": [...], "ssim": [...]} (indent 4; no "lpips": LPIPS is not
+    computed) and returns (rgbs, metrics).  The reference's video.mp4 is not written."""
+    os.makedirs(savedir, exist_ok=True)
+    rgbs, _ = render.render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=gt_imgs, savedir=savedir,
+                                 render_factor=render_factor)
+    gts = gt_imgs.cpu().numpy() if isinstance(gt_imgs, torch.Tensor) else np.asarray(gt_imgs)
+    psnr, ssim = metrics.batch_metrics(gts, rgbs)
+    out = {"psnr": psnr, "ssim": ssim}
+    with open(os.path.join(savedir, "metrics.json"), "w") as f:
+        json.dump(out, f, indent=4)
+    return rgbs, out
+
+
+def _read_images_in_dir(imgs_dir):
+    """metrics.ipynb read_images_in_dir: every file in sorted order but 000.png (the canonical space), / 255 as float32,
+    NCHW"""
+    names = sorted(os.listdir(imgs_dir))
+    imgs = [np.transpose((read_png(os.path.join(imgs_dir, f)) / 255.).astype(np.float32), (2, 0, 1))
+            for f in names if f != "000.png"]
+    if not imgs:
+        raise ValueError(f"swnerf.runner.evaluate_dir: no frames to score in {imgs_dir}")
+    return np.stack(imgs)
+
+
+def evaluate_dir(files_dir):
+    """The last cell of d_nerf/metrics.ipynb for a D-NeRF or T-NeRF render directory (render_path(..., save_also_gt=True)
+    wrote files_dir/estim and files_dir/gt): estim_error of the two batches, written to files_dir/metrics.txt as str(dict).
+    -> {'mse', 'psnr', 'ssim'} (no 'lpips': LPIPS is not computed)."""
+    estim = _read_images_in_dir(os.path.join(files_dir, "estim"))
+    gt = _read_images_in_dir(os.path.join(files_dir, "gt"))
+    errors = metrics.estim_error(estim, gt)
+    with open(os.path.join(files_dir, "metrics.txt"), "w") as f:
+        f.write(str(errors))
+    return errors
