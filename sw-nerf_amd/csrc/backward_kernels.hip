@@ -9,21 +9,16 @@
 #include "swnerf_common.h"
 #include "lds_dma.h"
 #include "wave_dpp.h"
+#include "composite.h"
 #include "host_util.h"
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
-// raw2outputs backward, one wave per ray.  With c = sigmoid(rgb), e = exp(-relu(sigma)*dist),
-// a = 1-e, p = 1-a+1e-10, T_i = prod_{j<i} p_j, w = a*T:
-//   G_i   = dL/dw_i = g_rgb.c_i + gA + gD*z_i + g_w_i
-//   dL/da_i = G_i*T_i - (sum_{k>i} G_k*w_k)/p_i ,   da/dsigma = dist*e*[sigma>0]
-//   dL/drgb_i = w_i * g_rgb * c_i*(1-c_i)
-// gA folds d(acc_map), the white-background term (rgb_map += 1-acc) and disp = 1/max(1e-10, D/A);
-// gD folds d(depth_map) and disp.  Prefix products and suffix sums run in double like the forward.
+// raw2outputs backward, one wave per ray: the arithmetic and its derivation are composite.h's.  Prefix products and suffix
+// sums run in double like the forward.
 // Both scans run on the DPP path (wave_dpp.h; the kernel is VALU-issue bound).  The suffix sums of pass 2 become PREFIX sums
 // over lanes by handing the samples of a 64-sample chunk to the lanes in REVERSE order (lane L owns sample 64 ch + 63 - L): the
 // loads stay one contiguous 1 KiB / 256 B block per wave instruction.  T and w of pass 1 wait in the wave's 2 x S floats of LDS.
@@ -38,7 +33,8 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(const float* raw, 
     float* T_ = r2b_lds + wv * 2 * Sp; float* W_ = T_ + Sp;
     const float dx = rd[ray * 3], dy = rd[ray * 3 + 1], dz = rd[ray * 3 + 2];
     const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-    const float gr = g_rgb ? g_rgb[ray * 3] : 0.f, gg = g_rgb ? g_rgb[ray * 3 + 1] : 0.f, gb = g_rgb ? g_rgb[ray * 3 + 2] : 0.f;
+    CompGrads g = {g_rgb ? g_rgb[ray * 3] : 0.f, g_rgb ? g_rgb[ray * 3 + 1] : 0.f, g_rgb ? g_rgb[ray * 3 + 2] : 0.f,
+                   g_acc ? g_acc[ray] : 0.f, g_depth ? g_depth[ray] : 0.f};
     const float* zr = zv + ray * S;
     const float4* rr = reinterpret_cast<const float4*>(raw) + ray * S;
     const float* nr = noise ? noise + ray * S : nullptr;
@@ -52,26 +48,17 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(const float* raw, 
         const float z = zr[sc];
         const float z_edge = (lane == 63 && s + 1 < S) ? zr[s + 1] : 0.f;
         const float zn = wave_from_above_f32(z, z_edge);          // a cross-lane read: never under a lane-dependent branch
-        float dist = (s + 1 < S) ? (zn - z) : 1e10f;
-        dist *= dnorm;
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
         float sg = rr[sc].w;
         if (nr) sg += nr[sc];
-        float alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-        if (!live) alpha = 0.f;
-        const double ps = wave_incl_prod_f64((double)(1.f - alpha + 1e-10f));
-        const float T = (float)(Tc * wave_from_below_f64(ps, 1.0));
-        Tc *= wave_last_f64(ps);
+        const float alpha = comp_alpha(sg, dist, live);
+        const float T = comp_transmittance(excl_cumprod_dpp64(comp_survival(alpha)), Tc);
         const float w = alpha * T;
         if (live) { T_[s] = T; W_[s] = w; }
         pa += w; pd += w * z;
     }
     pa = __shfl(wave_sum_to_last_f32(pa), 63, 64); pd = __shfl(wave_sum_to_last_f32(pd), 63, 64);
-    float gA = g_acc ? g_acc[ray] : 0.f, gD = g_depth ? g_depth[ray] : 0.f;
-    if (white) gA -= (gr + gg + gb);
-    if (g_disp) {
-        const float q = pd / pa;                       // disp = 1/max(1e-10, q); no gradient on the clamped / NaN branch
-        if (q > 1e-10f) { const float gq = -g_disp[ray] / (q * q); gD += gq / pa; gA -= gq * pd / (pa * pa); }
-    }
+    comp_bwd_fold(g, white, g_disp ? g_disp + ray : nullptr, pd, pa);
     // pass 2: G_i, then the suffix sums of G*w from the last chunk to the first
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -83,9 +70,9 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(const float* raw, 
         const int sc = live ? s : S - 1;
         const float4 r4 = rr[sc];
         const float z = zr[sc];
-        const float c0 = 1.f / (1.f + expf(-r4.x)), c1 = 1.f / (1.f + expf(-r4.y)), c2 = 1.f / (1.f + expf(-r4.z));
+        const float c0 = comp_sigmoid(r4.x), c1 = comp_sigmoid(r4.y), c2 = comp_sigmoid(r4.z);
         const float w = live ? W_[sc] : 0.f, T = live ? T_[sc] : 0.f;
-        float G = gr * c0 + gg * c1 + gb * c2 + gA + gD * z;
+        float G = comp_bwd_G(g, c0, c1, c2, z);
         if (g_w) G += g_w[ray * S + sc];
         // inclusive sum of G*w over the lanes <= this one = the samples >= s of the chunk, in double
         const double v = live ? (double)G * (double)w : 0.0;
@@ -94,18 +81,11 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(const float* raw, 
         carry += wave_last_f64(incl);
         const float z_edge = (lane == 0 && s + 1 < S) ? zr[s + 1] : 0.f;      // sample s+1 sits one lane BELOW
         const float zn = dpp_f32<SW_DPP_WAVE_SHR1>(z_edge, z);    // (cross-lane: outside the lane-dependent select)
-        float dist = (s + 1 < S) ? (zn - z) : 1e10f;
-        dist *= dnorm;
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
         float sg = r4.w;
         if (nr) sg += nr[sc];
-        const float e = expf(-fmaxf(sg, 0.f) * dist);
-        const float p = 1.f - (1.f - e) + 1e-10f;
-        const float dLda = G * T - (float)(R / (double)p);
-        const float dsig = (sg > 0.f) ? dLda * dist * e : 0.f;
-        if (live) {
-            f32x4 o4 = {w * gr * c0 * (1.f - c0), w * gg * c1 * (1.f - c1), w * gb * c2 * (1.f - c2), dsig};
-            *reinterpret_cast<f32x4*>(d_raw + (ray * S + s) * 4) = o4;
-        }
+        const f32x4 o4 = comp_bwd_sample(g, G, T, w, R, sg, dist, c0, c1, c2);
+        if (live) *reinterpret_cast<f32x4*>(d_raw + (ray * S + s) * 4) = o4;
     }
 }
 

@@ -6,6 +6,7 @@
 #include "swnerf_common.h"
 #include "host_util.h"
 #include "resample.h"
+#include "composite.h"
 
 static thread_local char g_err[SW_ERRBUF_LEN] = "";
 char* sw_errbuf() { return g_err; }
@@ -198,35 +199,18 @@ __global__ void __launch_bounds__(256) raw2outputs_kernel(const float* raw, cons
         const float4 r4 = rr[sc];
         const float z = zr[sc];
         const float z_edge = (lane == 63 && s + 1 < S) ? zr[s + 1] : 0.f;
-        const float zn = wave_from_above_f32(z, z_edge);
-        float dist = (s + 1 < S) ? (zn - z) : 1e10f;
-        dist = dist * dnorm;
+        const float zn = wave_from_above_f32(z, z_edge);          // a cross-lane read: never under a lane-dependent branch
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
         float sg = r4.w;
         if (nr) sg += nr[sc];
-        float alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-        if (!live) alpha = 0.f;
-        const double ps = wave_incl_prod_f64((double)(1.f - alpha + 1e-10f));
-        const double ex = wave_from_below_f64(ps, 1.0);
-        const float w = alpha * (float)(Tc * ex);
-        Tc *= wave_last_f64(ps);
+        const float alpha = comp_alpha(sg, dist, live);
+        const float w = alpha * comp_transmittance(excl_cumprod_dpp64(comp_survival(alpha)), Tc);
         if (live && wr) wr[s] = w;
-        pr += w * (1.f / (1.f + expf(-r4.x)));
-        pg += w * (1.f / (1.f + expf(-r4.y)));
-        pb += w * (1.f / (1.f + expf(-r4.z)));
-        pd += w * z;
-        pa += w;
+        comp_accumulate(w, r4.x, r4.y, r4.z, z, pr, pg, pb, pd, pa);
     }
     pr = wave_sum_to_last_f32(pr); pg = wave_sum_to_last_f32(pg); pb = wave_sum_to_last_f32(pb);
     pd = wave_sum_to_last_f32(pd); pa = wave_sum_to_last_f32(pa);
-    if (lane == 63) {
-        if (rgb_map) {
-            const float bg = white ? (1.f - pa) : 0.f;
-            rgb_map[ray * 3] = pr + bg; rgb_map[ray * 3 + 1] = pg + bg; rgb_map[ray * 3 + 2] = pb + bg;
-        }
-        if (depth) depth[ray] = pd;
-        if (acc) acc[ray] = pa;
-        if (disp) { const float q = pd / pa; disp[ray] = 1.f / ((q != q) ? q : fmaxf(1e-10f, q)); }
-    }
+    if (lane == 63) comp_write_maps(pr, pg, pb, pd, pa, white, ray, rgb_map, disp, acc, depth);
 }
 
 extern "C" int swnerf_raw2outputs(const float* raw, const float* z_vals, const float* rays_d, const float* noise, int64_t N, int S,

@@ -14,6 +14,7 @@
 #include "mlp_kernels.h"
 #include "mlp_core_x3.h"
 #include "resample.h"
+#include "composite.h"
 
 #define SW_LDS_SC 256                    // max coarse samples when resampling
 #define SW_LDS_SORT 1024                 // max S + n_importance (padded to a power of two)
@@ -363,8 +364,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             ws_rewind(ws, P.w0 + (P.dir_steps + P.time_steps) * SW_STEP_FLOATS,
                       lds_bias + ((P.dir_steps ? SW_DIR_BIAS_TILES : 0) + (P.time_steps ? 8 : 0)) * SW_BIAS_TILE_FLOATS, lane);
 
-        // ---- raw2outputs on this tile (ray.py:155-198); both lane halves mirror each other
-        // (TWIN: tnerf_kernels.hip repeats this scan and the map writes below for the T-NeRF pass; change both together)
+        // ---- raw2outputs on this tile (composite.h); both lane halves mirror each other
         const float c0 = rgb[0], c1 = rgb[1], c2 = rgb[2];
         float sg = head[0];
         if (a.raw && live && h == 0) {
@@ -377,49 +377,19 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             }
         }
         if (a.noise) sg += a.noise[ray * S + sc];
-        float dist = (s + 1 < S) ? (zn - z) : 1e10f;
-        dist = dist * dnorm;
-        float alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-        if (!live) alpha = 0.f;
-        double ps = (double)(1.f - alpha + 1e-10f);
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            const double up = __shfl_up(ps, o, 32);
-            if (j >= o) ps *= up;
-        }
-        double ex = __shfl_up(ps, 1, 32);
-        if (j == 0) ex = 1.0;
-        const float T = (float)(Tc * ex);                                    // exclusive cumprod (ray.py:188)
-        Tc *= __shfl(ps, 31, 32);
-        const float w = alpha * T;
+        const float alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live);
+        const float w = alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
         if (live) {
             if (a.weights && h == 0) a.weights[ray * S + s] = w;
             if (a.z_out && h == 0) a.z_out[ray * S + s] = z;
             if (resample && h == 0) { zc[s] = z; wc[s] = w; }
         }
-        pr += w * (1.f / (1.f + expf(-c0)));
-        pg += w * (1.f / (1.f + expf(-c1)));
-        pb += w * (1.f / (1.f + expf(-c2)));
-        pd += w * z;
-        pa += w;
+        comp_accumulate(w, c0, c1, c2, z, pr, pg, pb, pd, pa);
     }
 
     pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
     pd = wave32_sum(pd); pa = wave32_sum(pa);
-    if (lane == 0 && !ghost) {
-        if (a.rgb_map) {
-            const float bg = a.white_bkgd ? (1.f - pa) : 0.f;                // ray.py:195-196
-            a.rgb_map[ray * 3 + 0] = pr + bg;
-            a.rgb_map[ray * 3 + 1] = pg + bg;
-            a.rgb_map[ray * 3 + 2] = pb + bg;
-        }
-        if (a.depth_map) a.depth_map[ray] = pd;
-        if (a.acc_map) a.acc_map[ray] = pa;
-        if (a.disp_map) {
-            const float q = pd / pa;                                         // NaN when acc == 0, kept (ray.py:192)
-            a.disp_map[ray] = 1.f / ((q != q) ? q : fmaxf(1e-10f, q));
-        }
-    }
+    if (lane == 0 && !ghost) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
     if (!resample || ghost) return;
 
     // ---- sample_pdf (ray.py:96-153) on bins = mid-points, weights[1:-1]; z_std; then sort (nerf/run.py:396-400, 416) as a rank

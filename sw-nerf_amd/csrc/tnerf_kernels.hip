@@ -147,57 +147,24 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_render_kernel
         const float c0 = relu1(c3[0] + hb[1]), c1 = relu1(c3[1] + hb[2]), c2 = relu1(c3[2] + hb[3]);
         ws_rewind(ws, main_w, main_b, lane);     // the ring already holds MAIN's head (the blob's tail copy)
 
-        // ---- raw2outputs on this tile (run_tnerf.py:349-393); both lane halves mirror each other.
-        // TWIN: this scan and the map writes after the loop are the same arithmetic as render_pass.h (render_pass_kernel, the block
-        // "raw2outputs on this tile" and its epilogue) - kept as a copy so that render_pass_kernel's code stays as audited
-        // (tests/test_isa_audit.py).  A change to either (NaN disparity, cumprod precision, white background) goes into both.
+        // ---- raw2outputs on this tile (composite.h; run_tnerf.py:349-393); both lane halves mirror each other
         if (a.raw && live && h == 0) {
             f32x4 r4 = {c0, c1, c2, sg};
             *reinterpret_cast<f32x4*>(a.raw + (ray * S + s) * 4) = r4;
         }
         if (a.noise) sg += a.noise[ray * S + sc];
-        float dist = (s + 1 < S) ? (zn - z) : 1e10f;
-        dist = dist * dnorm;
-        float alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-        if (!live) alpha = 0.f;
-        double ps = (double)(1.f - alpha + 1e-10f);
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-            const double up = __shfl_up(ps, o, 32);
-            if (j >= o) ps *= up;
-        }
-        double ex = __shfl_up(ps, 1, 32);
-        if (j == 0) ex = 1.0;
-        const float T = (float)(Tc * ex);                                    // exclusive cumprod (run_tnerf.py:381)
-        Tc *= __shfl(ps, 31, 32);
-        const float w = alpha * T;
+        const float alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live);
+        const float w = alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
         if (live && h == 0) {
             if (a.weights) a.weights[ray * S + s] = w;
             if (a.z_out) a.z_out[ray * S + s] = z;
         }
-        pr += w * (1.f / (1.f + expf(-c0)));
-        pg += w * (1.f / (1.f + expf(-c1)));
-        pb += w * (1.f / (1.f + expf(-c2)));
-        pd += w * z;
-        pa += w;
+        comp_accumulate(w, c0, c1, c2, z, pr, pg, pb, pd, pa);
     }
 
     pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
     pd = wave32_sum(pd); pa = wave32_sum(pa);
-    if (lane == 0) {
-        if (a.rgb_map) {
-            const float bg = a.white_bkgd ? (1.f - pa) : 0.f;                // run_tnerf.py:389-390
-            a.rgb_map[ray * 3 + 0] = pr + bg;
-            a.rgb_map[ray * 3 + 1] = pg + bg;
-            a.rgb_map[ray * 3 + 2] = pb + bg;
-        }
-        if (a.depth_map) a.depth_map[ray] = pd;
-        if (a.acc_map) a.acc_map[ray] = pa;
-        if (a.disp_map) {
-            const float q = pd / pa;                                         // NaN when acc == 0, kept (run_tnerf.py:386)
-            a.disp_map[ray] = 1.f / ((q != q) ? q : fmaxf(1e-10f, q));
-        }
-    }
+    if (lane == 0) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
 }
 
 // Called by swnerf_render_pass (render_kernels.hip) for kind SWNERF_NET_TNERF after its generic checks; the T-NeRF ones are here.

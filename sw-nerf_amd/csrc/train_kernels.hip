@@ -264,8 +264,9 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
     WStream ws;
     ws_start(ws, P.w0, lds_all, lds_ring, lane);      // the weight ring fills while the compositing backward runs
 
-    // ---- 1. compositing backward (the arithmetic of raw2outputs_bwd_kernel, backward_kernels.hip)
-    const float gr = P.g_rgb ? P.g_rgb[ray * 3] : 0.f, gg = P.g_rgb ? P.g_rgb[ray * 3 + 1] : 0.f, gb = P.g_rgb ? P.g_rgb[ray * 3 + 2] : 0.f;
+    // ---- 1. compositing backward (composite.h; no d(depth_map) and no d(weights) reach the fused step)
+    CompGrads g = {P.g_rgb ? P.g_rgb[ray * 3] : 0.f, P.g_rgb ? P.g_rgb[ray * 3 + 1] : 0.f, P.g_rgb ? P.g_rgb[ray * 3 + 2] : 0.f,
+                   P.g_acc ? P.g_acc[ray] : 0.f, 0.f};
     double Tc = 1.0;
     float pa = 0.f, pd = 0.f;
     for (int base = 0; base < S; base += 64) {
@@ -273,31 +274,19 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
         const bool live = s < S;
         const int sc = live ? s : S - 1;
         const float z = zv[sc];
-        float dist = (s + 1 < S) ? (zv[s + 1] - z) : 1e10f;
-        dist *= dnorm;
+        const float zn = (s + 1 < S) ? zv[s + 1] : z;
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
         float sg = raw[sc * oc + 3];
         if (P.noise) sg += P.noise[ray * S + sc];
-        float alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-        if (!live) alpha = 0.f;
-        double ps = (double)(1.f - alpha + 1e-10f);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const double up = __shfl_up(ps, o, 64); if (lane >= o) ps *= up; }
-        double ex = __shfl_up(ps, 1, 64);
-        if (lane == 0) ex = 1.0;
-        const float T = (float)(Tc * ex);
-        Tc *= __shfl(ps, 63, 64);
+        const float alpha = comp_alpha(sg, dist, live);
+        const float T = comp_transmittance(excl_cumprod_shfl<64>(comp_survival(alpha), lane), Tc);
         const float w = alpha * T;
         if (live) { T_[s] = T; W_[s] = w; }
         pa += w; pd += w * z;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { pa += __shfl_xor(pa, o, 64); pd += __shfl_xor(pd, o, 64); }
-    float gA = P.g_acc ? P.g_acc[ray] : 0.f, gD = 0.f;
-    if (P.white) gA -= (gr + gg + gb);
-    if (P.g_disp) {
-        const float q = pd / pa;                       // disp = 1/max(1e-10, q); no gradient on the clamped / NaN branch
-        if (q > 1e-10f) { const float gq = -P.g_disp[ray] / (q * q); gD += gq / pa; gA -= gq * pd / (pa * pa); }
-    }
+    comp_bwd_fold(g, P.white, P.g_disp ? P.g_disp + ray : nullptr, pd, pa);
     wave_lds_sync();
     double carry = 0.0;
     const int nch = (S + 63) / 64;
@@ -309,9 +298,9 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
         if (NOVIEW) { r4[0] = raw[sc * oc]; r4[1] = raw[sc * oc + 1]; r4[2] = raw[sc * oc + 2]; r4[3] = raw[sc * oc + 3]; }   // rows of 5 floats are not 16-byte aligned
         else r4 = *reinterpret_cast<const f32x4*>(raw + sc * 4);
         const float z = zv[sc];
-        const float c0 = 1.f / (1.f + expf(-r4[0])), c1 = 1.f / (1.f + expf(-r4[1])), c2 = 1.f / (1.f + expf(-r4[2]));
+        const float c0 = comp_sigmoid(r4[0]), c1 = comp_sigmoid(r4[1]), c2 = comp_sigmoid(r4[2]);
         const float w = live ? W_[sc] : 0.f, T = live ? T_[sc] : 0.f;
-        const float G = gr * c0 + gg * c1 + gb * c2 + gA + gD * z;
+        const float G = comp_bwd_G(g, c0, c1, c2, z);
         double v = live ? (double)G * (double)w : 0.0;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const double dn = __shfl_down(v, o, 64); if (lane + o < 64) v += dn; }
@@ -319,18 +308,12 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
         if (lane == 63) after = 0.0;
         const double R = carry + after;
         carry += __shfl(v, 0, 64);
-        float dist = (s + 1 < S) ? (zv[s + 1] - z) : 1e10f;
-        dist *= dnorm;
+        const float zn = (s + 1 < S) ? zv[s + 1] : z;
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
         float sg = r4[3];
         if (P.noise) sg += P.noise[ray * S + sc];
-        const float e = expf(-fmaxf(sg, 0.f) * dist);
-        const float p = 1.f - (1.f - e) + 1e-10f;
-        const float dLda = G * T - (float)(R / (double)p);
-        const float dsig = (sg > 0.f) ? dLda * dist * e : 0.f;
-        if (live) {
-            f32x4 o4 = {w * gr * c0 * (1.f - c0), w * gg * c1 * (1.f - c1), w * gb * c2 * (1.f - c2), dsig};
-            *reinterpret_cast<f32x4*>(dR + 4 * s) = o4;
-        }
+        const f32x4 o4 = comp_bwd_sample(g, G, T, w, R, sg, dist, c0, c1, c2);
+        if (live) *reinterpret_cast<f32x4*>(dR + 4 * s) = o4;
     }
     wave_lds_sync();
 

@@ -92,3 +92,13 @@ def test_embed_kernel_multiply_shift_divisions_are_exact():
             pslot = np.arange(max(d * L, 1), dtype=np.uint64)
             assert int(pslot[-1]) * d_magic < 2 ** 32
             assert np.array_equal((pslot * np.uint64(d_magic)) >> np.uint64(24), pslot // np.uint64(d)), (d, L)
+
+
+def test_compositing_arithmetic_is_defined_once():
+    """raw2outputs' arithmetic (ray.py:155-198) lives in csrc/composite.h alone: the literals that mark it - the 1e10 last
+    interval and the 1e-10 of the survival factor, the disparity clamp and the backward's branch - appear in no other file of
+    csrc/, so a kernel cannot grow a written-out copy of its own again."""
+    csrc = os.path.join(ROOT, "sw-nerf_amd", "csrc")
+    found = {lit: sorted(f for f in os.listdir(csrc) if lit in open(os.path.join(csrc, f), errors="replace").read())
+             for lit in ("1e10f", "1e-10f")}
+    assert found == {"1e10f": ["composite.h"], "1e-10f": ["composite.h"]}, found
