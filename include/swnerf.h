@@ -135,7 +135,10 @@ int swnerf_sample_pdf(const float* bins, const float* weights, int64_t N, int nb
 
 /* ---- embedder.py --------------------------------------------------------------------- */
 
-/* Embedder.embed (embedder.py:33-42): x [M,d] -> [M, d*(1+2L)], frequency-major, sin before cos. */
+/* Embedder.embed (embedder.py:33-42): x [M,d] -> [M, d*(1+2L)], frequency-major, sin before cos.
+ * 1 <= d <= 16, 0 <= L <= 24 (else SWNERF_E_ARG).  Every sin / cos within 1.2e-7 of the exact value of the float x * 2^k for
+ * |x * 2^k| < 3e9 (all 24 bands at |x| <= 6 are tested: |y| <= 5.1e7): bands k < 10 are the float arithmetic of the fused
+ * passes, bit for bit; bands k >= 10 reduce their argument in double. */
 int swnerf_embed(const float* x, int64_t M, int d, int L, float* out, void* stream);
 
 /* ---- model.py ------------------------------------------------------------------------ */

@@ -128,10 +128,15 @@ extern "C" int swnerf_pack_ray_batch(const float* rays_o, const float* rays_d, i
 // out[row] = [x, sin(2^0 x), cos(2^0 x), ..., sin(2^(L-1) x), cos(2^(L-1) x)], blocks d wide.  VALU-issue bound, not HBM
 // bound, once the stores are coalesced: what counts is instructions per output float.  A workgroup builds the image of
 // EMB_ROWS output rows in LDS - one job per (row, band, component) evaluates the sine AND the cosine of its argument with one
-// reduction (sw_sincos_pair: the bits of sw_sin_or_cos), one job per (row, component) copies x - and the image, contiguous in
+// reduction (sw_embed_sincos: the bits of sw_sin_or_cos for the bands k < 10 the fused kernels have, the reduction in double for
+// the bands above, where the float one fails - all 24 accepted bands within 1.2e-7 of libm at |x| <= 6, tests/test_host_math.py
+// and tests/test_gpu_op_domain.py), one job per (row, component) copies x - and the image, contiguous in
 // the output and 16-byte aligned, leaves as float4 stores.  Job -> (row, slot) by a multiply-shift (q_magic = ceil(2^24 / Q),
 // exact for the jobs of a block - checked on the host for every accepted (d, L); the 64-bit division per element of the round 1-3 kernel cost more than the sin/cos).
+// WIDE = some band k >= SW_SINCOS_F32_BANDS (L > 10): only that instantiation carries the double reduction; L <= 10 - every
+// embedder the reference builds - runs the float-only kernel, instruction for instruction what it was before the bands above 10 were fixed.
 #define EMB_ROWS 64
+template <bool WIDE>
 __global__ void __launch_bounds__(256) embed_kernel(const float* x, int64_t M, int d, int L, int R, unsigned q_magic, unsigned d_magic, float* out) {
     extern __shared__ __attribute__((aligned(16))) float emb_img[];           // [rows][C]
     const int C = d * (1 + 2 * L), Q = d * (1 + L);                             // jobs per row: d copies + d * L (sin, cos) pairs
@@ -146,7 +151,8 @@ __global__ void __launch_bounds__(256) embed_kernel(const float* x, int64_t M, i
         } else {
             const unsigned p = q - d, k = (p * d_magic) >> 24, c = p - k * (unsigned)d;
             float sv, cv;
-            sw_sincos_pair(xb[row * d + c] * (float)(1 << k), &sv, &cv);    // x * 2^k is exact (embedder.py:29,36)
+            if (WIDE) sw_embed_sincos(xb[row * d + c], (int)k, &sv, &cv);   // bands >= 10 reduce in double (swnerf_common.h)
+            else sw_sincos_pair(xb[row * d + c] * (float)(1 << k), &sv, &cv);   // = sw_embed_sincos for k < 10; x * 2^k is exact (embedder.py:29,36)
             o[d + 2 * k * d + c] = sv;
             o[d + 2 * k * d + d + c] = cv;
         }
@@ -168,8 +174,12 @@ extern "C" int swnerf_embed(const float* x, int64_t M, int d, int L, float* out,
     const unsigned q_magic = ((1u << 24) + Q - 1) / Q, d_magic = ((1u << 24) + d - 1) / d;   // floor(n / Q) = (n * q_magic) >> 24 for n * Q < 2^24
     int R = EMB_ROWS;
     while (R > 1 && (size_t)R * C * sizeof(float) > 64 * 1024) R >>= 1;
-    hipLaunchKernelGGL(embed_kernel, dim3(nblocks(M, R)), dim3(256), (size_t)R * C * sizeof(float), (hipStream_t)stream,
-                       x, M, d, L, R, q_magic, d_magic, out);
+    if (L > SW_SINCOS_F32_BANDS)
+        hipLaunchKernelGGL(embed_kernel<true>, dim3(nblocks(M, R)), dim3(256), (size_t)R * C * sizeof(float), (hipStream_t)stream,
+                           x, M, d, L, R, q_magic, d_magic, out);
+    else
+        hipLaunchKernelGGL(embed_kernel<false>, dim3(nblocks(M, R)), dim3(256), (size_t)R * C * sizeof(float), (hipStream_t)stream,
+                           x, M, d, L, R, q_magic, d_magic, out);
     return sw_check(hipGetLastError(), "embed launch");
 }
 

@@ -177,10 +177,13 @@ SW_HD int sw_xs_col(int f /*0..95*/, int Lp, int Ld) {
 }
 
 // ---- sin / cos -------------------------------------------------------------------------
-// sin(y) for want_cos==0, cos(y) for want_cos==1, |y| up to ~1e5 (the top positional band is
-// 512*x).  Three-term Cody-Waite reduction by pi/2 with FMAs, then the Cephes float minimax
-// polynomials on [-pi/4, pi/4]; cos(y) = sin(y + pi/2) is a quadrant shift, so both lane
-// halves run the same instruction stream.  Max abs error vs double libm ~1.2e-7 (test_host_math).
+// sin(y) for want_cos==0, cos(y) for want_cos==1, for the arguments of the fused kernels: bands k < SW_SINCOS_F32_BANDS,
+// |y| = |x| * 2^k <= 3072 at |x| <= 6 (the top positional band is 512*x).  Three-term Cody-Waite reduction by pi/2 with
+// FMAs, then the Cephes float minimax polynomials on [-pi/4, pi/4]; cos(y) = sin(y + pi/2) is a quadrant shift, so both lane
+// halves run the same instruction stream.  Max abs error vs double libm < 1.2e-7 there (test_host_math).  The quotient n
+// is a float: the reduction loses accuracy from |y| ~ 2e6 on (6e-7 in band 19, 0.2 in band 23), so the standalone
+// embedder, which accepts 24 bands, takes sw_sincos_pair_wide above this range (sw_embed_sincos below).
+#define SW_SINCOS_F32_BANDS 10
 SW_HD float sw_sin_or_cos(float y, int want_cos) {
     const float n = rintf(y * 0.63661977236758134f);
     float r = fmaf(-n, 1.57079637050628662e+00f, y);
@@ -216,6 +219,35 @@ SW_HD void sw_sincos_pair(float y, float* s_out, float* c_out) {
     const float sv = (q & 1) ? pc : ps, cv = ((q + 1) & 1) ? pc : ps;
     *s_out = (q & 2) ? -sv : sv;
     *c_out = ((q + 1) & 2) ? -cv : cv;
+}
+
+// sin(y) AND cos(y) for large arguments: the reduction by pi/2 in double (quotient, two-term pi/2, FMAs: |error| < 3e-16
+// while the quotient fits an int, |y| < 3e9), then the polynomials of sw_sincos_pair on the rounded remainder.  Not the bits
+// of sw_sincos_pair (the remainder is rounded once from double instead of three times in float); same error bound.
+SW_HD void sw_sincos_pair_wide(float y, float* s_out, float* c_out) {
+    const double n = rint((double)y * 0.63661977236758134308);
+    double rd = fma(-n, 1.57079632679489655800e+00, (double)y);
+    rd = fma(-n, 6.12323399573676603587e-17, rd);
+    const float r = (float)rd;
+    const int q = (int)n;
+    const float z = r * r;
+    float ps = fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
+    ps = fmaf(ps, z, -1.6666654611e-1f);
+    ps = fmaf(ps * z, r, r);
+    float pc = fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
+    pc = fmaf(pc, z, 4.166664568298827e-2f);
+    pc = fmaf(pc * z, z, fmaf(-0.5f, z, 1.0f));
+    const float sv = (q & 1) ? pc : ps, cv = ((q + 1) & 1) ? pc : ps;
+    *s_out = (q & 2) ? -sv : sv;
+    *c_out = ((q + 1) & 2) ? -cv : cv;
+}
+
+// what the standalone embedder (misc_kernels.hip embed_kernel) evaluates for band k of x: the bands the fused kernels
+// have (k < SW_SINCOS_F32_BANDS) with their instructions, bit for bit; the bands above them with the double reduction
+SW_HD void sw_embed_sincos(float x, int k, float* s_out, float* c_out) {
+    const float y = x * (float)(1 << k);                       // x * 2^k is exact (embedder.py:29,36)
+    if (k < SW_SINCOS_F32_BANDS) sw_sincos_pair(y, s_out, c_out);
+    else sw_sincos_pair_wide(y, s_out, c_out);
 }
 
 // torch.linspace(start, end, steps)[i] in float32 as the ATen CPU kernel computes it:

@@ -29,7 +29,9 @@ def _embed_hip(x, multires):
 
 class Embedder:
     """embedder.py:12-42.  Only the configuration the reference ever builds is accelerated:
-    include_input, log_sampling, periodic_fns=[sin, cos], max_freq_log2 = num_freqs-1."""
+    include_input, log_sampling, periodic_fns=[sin, cos], max_freq_log2 = num_freqs-1, with num_freqs <= 24 and
+    input_dims <= 16 (the kernel's limits).  All 24 bands are within 1.2e-7 of the exact sin / cos of the float32
+    product x * 2^k (tested at |x| <= 6): the bands above the 10 of the fused passes reduce their argument in double."""
 
     def __init__(self, **kwargs):
         self.kwargs = kwargs

@@ -28,6 +28,23 @@ int main() {
   for (int f = 0; f < SW_XS_LD; ++f) printf("%d ", sw_xs_col(f, 10, 4)); printf("\n");
   for (int f = 0; f < SW_XS_LD; ++f) printf("%d ", sw_xs_col(f, 6, 2)); printf("\n");
   printf("%d %d %d\n", SW_BWD_IG_STEPS, SW_BWD_DN_STEPS, SW_XS_LD);
+  // every band swnerf_embed accepts, through the function embed_kernel calls (sw_embed_sincos), and that function's two halves
+  // against each other: the bands below SW_SINCOS_F32_BANDS are sw_sincos_pair = sw_sin_or_cos bit for bit
+  int same = 1;
+  for (int k = 0; k < 24; ++k) {
+    double w = 0;
+    for (int it = 0; it < 400002; ++it) {
+      float x = it < 400000 ? ((float)rand() / RAND_MAX * 2 - 1) * 6.0f : (it & 1 ? 6.0f : -6.0f);
+      float y = x * (float)(1 << k), s, c;
+      sw_embed_sincos(x, k, &s, &c);
+      double es = fabs((double)s - sin((double)y)), ec = fabs((double)c - cos((double)y));
+      if (es > w) w = es;
+      if (ec > w) w = ec;
+      if (k < SW_SINCOS_F32_BANDS && (s != sw_sin_or_cos(y, 0) || c != sw_sin_or_cos(y, 1))) same = 0;
+    }
+    printf("%.6e ", w);
+  }
+  printf("\n%d %d\n", same, SW_SINCOS_F32_BANDS);
   return 0;
 }
 '''
@@ -72,6 +89,14 @@ def test_common_header_on_host(tmp_path):
         assert sorted(c for c in cols[64:] if c >= 0) == list(range(3 * (1 + 2 * Ld)))
     ig, dn, xld = (int(x) for x in lines[k + 5].split())
     assert dn == ig + 7 * 256 and dn % 16 == 0 and xld == 96
+    # the standalone embedder's sin/cos, per band k = 0 .. 23 (swnerf_embed accepts L <= 24), |x| <= 6, |y| <= 5.1e7: the same
+    # bound as the fused kernels' range above; the float reduction alone gives 6e-7 in band 19 and 0.2 in band 23
+    band = [float(v) for v in lines[k + 6].split()]
+    assert len(band) == 24
+    for kb, e in enumerate(band):
+        assert e < 1.2e-7, f"band {kb}: max |err| {e:.3e} (all bands: {band})"
+    same, nf32 = (int(x) for x in lines[k + 7].split())
+    assert same == 1 and nf32 == 10                                   # L_pos, L_time <= 10 in the fused kernels: their bits
 
 
 def test_embed_kernel_multiply_shift_divisions_are_exact():

@@ -165,3 +165,22 @@ def test_x3_kernels_isa(tmp_path):
         m = re.search(rf"\.amdhsa_kernel {name}.*?\.end_amdhsa_kernel", text, re.S)
         assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(0)).group(1)) == 0
     assert seen == 4
+
+
+def test_embed_kernel_isa(tmp_path):
+    """misc_kernels.hip embed_kernel: no scratch in either instantiation (the kernel is VALU-issue bound).  <true> (L > 10) holds
+    the double-precision argument reduction of the bands k >= 10 (swnerf_common.h sw_sincos_pair_wide) inline; <false> (L <= 10:
+    every embedder the reference builds, and what the fused path must agree with bit for bit) holds no double instruction."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    out = tmp_path / "misc.s"
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
+                    os.path.join(ROOT, "sw-nerf_amd", "csrc", "misc_kernels.hip")], check=True, stderr=subprocess.DEVNULL)
+    asm = out.read_text()
+    found = {m.group(1): m.group(2) for m in re.finditer(r"\.amdhsa_kernel (\S*embed_kernel\S*)(.*?)\.end_amdhsa_kernel", asm, re.S)}
+    assert sorted("ILb1E" in n for n in found) == [False, True], list(found)
+    for name, desc in found.items():
+        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, name
+        body = asm[asm.index("\n" + name + ":"):]
+        body = body[:body.index(".Lfunc_end")]
+        assert "scratch_" not in body and "s_swappc" not in body, name
+        assert ("v_rndne_f64" in body) == ("ILb1E" in name) and ("_f64" in body) == ("ILb1E" in name), name
