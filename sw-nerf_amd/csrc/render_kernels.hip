@@ -73,46 +73,25 @@ __global__ void __launch_bounds__(256, 1) query_points_kernel(QueryDev P) {
 int sw_tnerf_render_launch(const swnerf_pass_args& a, hipStream_t st);     // tnerf_kernels.hip
 
 extern "C" int swnerf_render_pass(const swnerf_pass_args* args, void* stream) {
+    static const PassAccepts accepts = {"render_pass", {SW_COLS(11) | SW_COLS(12), SW_COLS(11) | SW_COLS(12), SW_COLS(8), ~0u /* checked by its launch */},
+        SWNERF_E_ARG, "%s: ray_batch must have 11 or 12 columns (use_viewdirs) or 8 (SWNERF_NET_NOVIEW), got %d for kind %d", true, 0};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass: NULL args");
     const swnerf_pass_args& a = *args;
-    if (!a.packed || (!a.ray_batch && a.n_rays != 0)) return sw_fail(SWNERF_E_ARG, "render_pass: NULL ray_batch/packed");
-    if (a.n_rays < 0 || a.n_samples < 2) return sw_fail(SWNERF_E_ARG, "render_pass: n_rays %lld, n_samples %d", (long long)a.n_rays, a.n_samples);
-    if (a.kind == SWNERF_NET_TNERF) {            // the T-NeRF pass lives in its own translation unit (tnerf_kernels.hip)
-        if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4 || a.L_time < 0 || a.L_time > 10)
-            return sw_fail(SWNERF_E_UNSUPP, "render_pass: embedder bands (%d,%d,%d) exceed (10,4,10)", a.L_pos, a.L_dir, a.L_time);
-        if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "render_pass: t_rand only applies to coarse sampling");
-        return sw_tnerf_render_launch(a, (hipStream_t)stream);
-    }
+    if (a.kind < 0 || a.kind > SWNERF_NET_TNERF) return sw_fail(SWNERF_E_ARG, "unknown net kind %d", a.kind);
+    int rc = pass_check(accepts, a);
+    if (rc) return rc;
+    if (a.kind == SWNERF_NET_TNERF) return sw_tnerf_render_launch(a, (hipStream_t)stream);      // its own translation unit (tnerf_kernels.hip)
     const bool noview = a.kind == SWNERF_NET_NOVIEW;
-    if (noview ? a.cols != 8 : (a.cols != 11 && a.cols != 12))
-        return sw_fail(SWNERF_E_ARG, "render_pass: ray_batch must have 11 or 12 columns (use_viewdirs) or 8 (SWNERF_NET_NOVIEW), got %d for kind %d", a.cols, a.kind);
     if (a.kind == SWNERF_NET_DNERF && a.cols != 12) return sw_fail(SWNERF_E_ARG, "render_pass: D-NeRF needs the frame_time column");
     if (noview && a.dx) return sw_fail(SWNERF_E_ARG, "render_pass: a static net has no position_delta output here");
-    if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4 || a.L_time < 0 || a.L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "render_pass: embedder bands (%d,%d,%d) exceed (10,4,10)", a.L_pos, a.L_dir, a.L_time);
-    if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "render_pass: t_rand only applies to coarse sampling");
-    PassDev P;
-    P.a = a;
-    int rc = noview ? stream_ptrs_noview(a.packed, a.out_ch, &P.w0, &P.b0, &P.nbias, &P.two_pass)
-                    : stream_ptrs(a.kind, a.packed, a.run_deform, &P.w0, &P.b0, &P.nbias, &P.two_pass);
+    PassDev P = pass_dev(a);
+    rc = noview ? stream_ptrs_noview(a.packed, a.out_ch, &P.w0, &P.b0, &P.nbias, &P.two_pass)
+                : stream_ptrs(a.kind, a.packed, a.run_deform, &P.w0, &P.b0, &P.nbias, &P.two_pass);
     if (rc) return rc;
-    P.sort_n = 0; P.sort_s = 0;
     P.dir_steps = noview ? 0 : SW_STEPS_DIR;
     P.time_steps = (a.kind == SWNERF_NET_DNERF && P.two_pass) ? SW_STEPS_TIME : 0;
-    P.tb_off = 0;
     size_t lds = SW_LDS_FIXED_FLOATS * sizeof(float);
-    if (a.n_importance > 0) {
-        if (!a.z_fine && a.n_rays != 0) return sw_fail(SWNERF_E_ARG, "render_pass: n_importance>0 needs z_fine");
-        if (a.n_samples < 3 || a.n_samples > SW_LDS_SC || a.n_samples + a.n_importance > SW_LDS_SORT)
-            return sw_fail(SWNERF_E_UNSUPP, "render_pass: resampling supports 3<=N_samples<=%d and N_samples+N_importance<=%d", SW_LDS_SC, SW_LDS_SORT);
-        int p2 = 2;                              // fallback sort of an unsorted sample list: power of two >= n_importance
-        while (p2 < a.n_importance) p2 <<= 1;
-        P.sort_n = p2;
-        p2 = 2;
-        while (p2 < a.n_samples) p2 <<= 1;
-        P.sort_s = p2;
-        lds += 4 * SW_LDS_WAVE_FLOATS * sizeof(float);
-    }
+    if ((rc = pass_resampling(accepts.name, a, P, lds))) return rc;
     if (a.n_rays == 0) return 0;
     if (P.time_steps) {                          // the four waves' per-ray TIME tiles, behind everything else
         P.tb_off = (int)(lds / sizeof(float));

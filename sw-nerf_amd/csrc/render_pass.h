@@ -111,6 +111,51 @@ static inline void pass_startup_args(PassDev& P, unsigned grid_x, int steps) {
     P.skew_unit = 4;
 }
 
+// ---- host side: what every entry point of the pass checks and sets up (the per-variant checks stay with the entry point) ----
+// What one entry point accepts.
+struct PassAccepts {
+    const char* name;           // prefix of every message
+    unsigned cols[4];           // per net kind (SWNERF_NET_*): bit c set = a ray batch of c columns is accepted; 0 = kind refused
+    int shape_code;             // a kind / column count outside `cols` is refused with this code ...
+    const char* shape_msg;      // ... and this message (printf arguments: name, cols, kind)
+    bool time_band;             // L_time is checked (and named) with L_pos / L_dir
+    int smax;                   // training passes: n_samples <= smax; 0 = inference, no cap
+};
+#define SW_COLS(c) (1u << (c))
+
+static inline int pass_check(const PassAccepts& e, const swnerf_pass_args& a) {
+    if (!a.packed || (!a.ray_batch && a.n_rays != 0)) return sw_fail(SWNERF_E_ARG, e.smax ? "%s: NULL pointer" : "%s: NULL ray_batch/packed", e.name);
+    if (a.kind < 0 || a.kind > 3 || a.cols < 0 || a.cols > 31 || !(e.cols[a.kind] >> a.cols & 1u)) return sw_fail(e.shape_code, e.shape_msg, e.name, a.cols, a.kind);
+    if (e.smax && (a.n_rays < 0 || a.n_samples < 2 || a.n_samples > e.smax))
+        return sw_fail(SWNERF_E_UNSUPP, "%s: 2 <= n_samples <= %d (got %d)", e.name, e.smax, a.n_samples);
+    if (a.n_rays < 0 || a.n_samples < 2) return sw_fail(SWNERF_E_ARG, "%s: n_rays %lld, n_samples %d", e.name, (long long)a.n_rays, a.n_samples);
+    if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4 || (e.time_band && (a.L_time < 0 || a.L_time > 10)))
+        return e.time_band ? sw_fail(SWNERF_E_UNSUPP, "%s: embedder bands (%d,%d,%d) exceed (10,4,10)", e.name, a.L_pos, a.L_dir, a.L_time)
+                           : sw_fail(SWNERF_E_UNSUPP, "%s: embedder bands (%d,%d) exceed (10,4)", e.name, a.L_pos, a.L_dir);
+    if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "%s: t_rand only applies to coarse sampling", e.name);
+    return 0;
+}
+
+// every launch starts from this: no member is left indeterminate
+static inline PassDev pass_dev(const swnerf_pass_args& a) {
+    PassDev P = {};
+    P.a = a;
+    return P;
+}
+
+// n_importance > 0: the limits of the in-LDS resampling, the two sort sizes, and its scratch behind the `lds` bytes so far
+static inline int pass_resampling(const char* name, const swnerf_pass_args& a, PassDev& P, size_t& lds) {
+    if (a.n_importance <= 0) return 0;
+    if (!a.z_fine && a.n_rays != 0) return sw_fail(SWNERF_E_ARG, "%s: n_importance>0 needs z_fine", name);
+    if (a.n_samples < 3 || a.n_samples > SW_LDS_SC || a.n_samples + a.n_importance > SW_LDS_SORT)
+        return sw_fail(SWNERF_E_UNSUPP, "%s: resampling supports 3<=N_samples<=%d and N_samples+N_importance<=%d", name, SW_LDS_SC, SW_LDS_SORT);
+    P.sort_n = P.sort_s = 2;                     // fallback sort of an unsorted sample list: powers of two >= n_importance / n_samples
+    while (P.sort_n < a.n_importance) P.sort_n <<= 1;
+    while (P.sort_s < a.n_samples) P.sort_s <<= 1;
+    lds += 4 * SW_LDS_WAVE_FLOATS * sizeof(float);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // TRAIN, static net: the LDS bias region holds the canonical tiles alone (the deformation tiles' 11 KB are what lets the
 // 16-deep ring of the training translation unit AND the resampling scratch fit into 160 KB).  TRAIN + DNERF keeps both

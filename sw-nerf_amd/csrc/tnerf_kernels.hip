@@ -167,21 +167,17 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_render_kernel
     if (lane == 0) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
 }
 
-// Called by swnerf_render_pass (render_kernels.hip) for kind SWNERF_NET_TNERF after its generic checks; the T-NeRF ones are here.
+// Called by swnerf_render_pass (render_kernels.hip) for kind SWNERF_NET_TNERF after the common checks (render_pass.h pass_check); the T-NeRF ones are here.
 int sw_tnerf_render_launch(const swnerf_pass_args& a, hipStream_t st) {
     if (a.n_importance > 0)
         return sw_fail(SWNERF_E_ARG, "render_pass: T-NeRF has no hierarchical resampling (run_tnerf.py forces N_importance = 0), got n_importance %d", a.n_importance);
     if (a.cols != 12) return sw_fail(SWNERF_E_ARG, "render_pass: T-NeRF needs the 12-column ray batch [o, d, near, far, t, viewdirs], got %d", a.cols);
     if (a.L_dir == 0) return sw_fail(SWNERF_E_UNSUPP, "render_pass: T-NeRF needs view directions (L_dir >= 1; TNeRF.forward reads vdir)");
     if (a.dx) return sw_fail(SWNERF_E_ARG, "render_pass: T-NeRF has no position_delta output");
-    PassDev P;
-    P.a = a;
+    PassDev P = pass_dev(a);
     P.w0 = a.packed;
     P.b0 = a.packed + SW_TN_W_FLOATS;
     P.nbias = SW_TN_BIAS_TILES * SW_BIAS_TILE_FLOATS;
-    P.two_pass = 0; P.sort_n = 0; P.sort_s = 0;
-    P.dir_steps = 0; P.time_steps = 0; P.tb_off = 0;
-    P.act = nullptr; P.bits = nullptr; P.xs = nullptr; P.act_d = nullptr; P.bits_d = nullptr; P.xs_d = nullptr;
     if (a.n_rays == 0) return 0;
     const dim3 grid((unsigned)((a.n_rays + 3) / 4)), block(256);
     pass_startup_args(P, grid.x, SW_TN_STEPS);

@@ -544,41 +544,25 @@ extern "C" int64_t swnerf_train_rows(int64_t n_rays, int n_samples) { return n_r
 extern "C" int swnerf_xs_floats_per_row(void) { return SW_XS_LD; }
 
 extern "C" int swnerf_render_pass_train(const swnerf_pass_args* args, float* act, float* bits, float* xs, void* stream) {
+    static const PassAccepts accepts = {"render_pass_train", {SW_COLS(11) | SW_COLS(12), 0, SW_COLS(8), 0}, SWNERF_E_UNSUPP,
+        "%s: the static net (SWNERF_NET_CANON, 11- or 12-column ray batch) or the one without view directions (SWNERF_NET_NOVIEW, 8 columns)", false, PB_SMAX};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass_train: NULL args");
     const swnerf_pass_args& a = *args;
     if (a.n_rays == 0 && a.packed) return 0;
-    if (!a.packed || !a.ray_batch || !act || !bits || !xs) return sw_fail(SWNERF_E_ARG, "render_pass_train: NULL pointer");
-    const bool noview = a.kind == SWNERF_NET_NOVIEW;
-    if (noview ? a.cols != 8 : (a.kind != SWNERF_NET_CANON || (a.cols != 11 && a.cols != 12)))
-        return sw_fail(SWNERF_E_UNSUPP, "render_pass_train: the static net (SWNERF_NET_CANON, 11- or 12-column ray batch) or the one without view directions (SWNERF_NET_NOVIEW, 8 columns)");
-    if (a.n_rays < 0 || a.n_samples < 2 || a.n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "render_pass_train: 2 <= n_samples <= %d (got %d)", PB_SMAX, a.n_samples);
-    if (!a.raw || !(a.z_vals || a.z_out)) return sw_fail(SWNERF_E_ARG, "render_pass_train: the backward needs raw and the depths (z_vals given or z_out)");
-    if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4) return sw_fail(SWNERF_E_UNSUPP, "render_pass_train: embedder bands (%d,%d) exceed (10,4)", a.L_pos, a.L_dir);
-    if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "render_pass_train: t_rand only applies to coarse sampling");
-    if (a.dx) return sw_fail(SWNERF_E_ARG, "render_pass_train: no dx output (static net)");
-    PassDev P;
-    P.a = a;
-    int rc = noview ? stream_ptrs_noview(a.packed, a.out_ch, &P.w0, &P.b0, &P.nbias, &P.two_pass)
-                    : stream_ptrs(a.kind, a.packed, 0, &P.w0, &P.b0, &P.nbias, &P.two_pass);
+    if (!act || !bits || !xs) return sw_fail(SWNERF_E_ARG, "render_pass_train: NULL pointer");
+    int rc = pass_check(accepts, a);
     if (rc) return rc;
-    P.act = act; P.bits = bits; P.xs = xs; P.act_d = nullptr; P.bits_d = nullptr; P.xs_d = nullptr;
-    P.sort_n = 0; P.sort_s = 0;
+    if (!a.raw || !(a.z_vals || a.z_out)) return sw_fail(SWNERF_E_ARG, "render_pass_train: the backward needs raw and the depths (z_vals given or z_out)");
+    if (a.dx) return sw_fail(SWNERF_E_ARG, "render_pass_train: no dx output (static net)");
+    const bool noview = a.kind == SWNERF_NET_NOVIEW;
+    PassDev P = pass_dev(a);
+    rc = noview ? stream_ptrs_noview(a.packed, a.out_ch, &P.w0, &P.b0, &P.nbias, &P.two_pass)
+                : stream_ptrs(a.kind, a.packed, 0, &P.w0, &P.b0, &P.nbias, &P.two_pass);
+    if (rc) return rc;
+    P.act = act; P.bits = bits; P.xs = xs;
     P.dir_steps = noview ? 0 : SW_STEPS_DIR;
-    P.time_steps = 0; P.tb_off = 0;
-    P.warm_steps = 0; P.warm_blocks = 0; P.skew_mode = 0; P.skew_unit = 0;
     size_t lds = PassLds<false, true>::FIXED * sizeof(float);
-    if (a.n_importance > 0) {
-        if (!a.z_fine) return sw_fail(SWNERF_E_ARG, "render_pass_train: n_importance>0 needs z_fine");
-        if (a.n_samples < 3 || a.n_samples > SW_LDS_SC || a.n_samples + a.n_importance > SW_LDS_SORT)
-            return sw_fail(SWNERF_E_UNSUPP, "render_pass_train: resampling supports 3<=N_samples<=%d and N_samples+N_importance<=%d", SW_LDS_SC, SW_LDS_SORT);
-        int p2 = 2;
-        while (p2 < a.n_importance) p2 <<= 1;
-        P.sort_n = p2;
-        p2 = 2;
-        while (p2 < a.n_samples) p2 <<= 1;
-        P.sort_s = p2;
-        lds += 4 * SW_LDS_WAVE_FLOATS * sizeof(float);
-    }
+    if ((rc = pass_resampling(accepts.name, a, P, lds))) return rc;
     const dim3 grid((unsigned)((a.n_rays + 3) / 4)), block(256);
     pass_startup_args(P, grid.x, noview ? SW_NOVIEW_STEPS : SW_CANON_STEPS);
     if (noview) hipLaunchKernelGGL((render_pass_kernel<false, true, 0, false>), grid, block, lds, (hipStream_t)stream, P);
@@ -586,25 +570,42 @@ extern "C" int swnerf_render_pass_train(const swnerf_pass_args* args, float* act
     return sw_check(hipGetLastError(), "render_pass_train launch");
 }
 
+// What the three backward entry points share: the checks (`ptrs`: every pointer this variant requires is there), the
+// PassBwdDev they start from (w_floats: where the bias tiles follow the stream; D-NeRF members null, out_ch 4) and the launch.
+static int pass_bwd_check(const char* name, bool ptrs, int64_t n_rays, int n_samples) {
+    if (!ptrs || n_rays < 0) return sw_fail(SWNERF_E_ARG, "%s: NULL pointer or negative n_rays", name);
+    if (n_samples < 2 || n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "%s: 2 <= n_samples <= %d (got %d)", name, PB_SMAX, n_samples);
+    return 0;
+}
+
+static PassBwdDev pass_bwd_dev(const float* packed_bwd, size_t w_floats, const float* bits, const float* raw, const float* z_vals,
+                               const float* ray_batch, int cols, const float* noise, int64_t n_rays, int n_samples, int white_bkgd,
+                               const float* g_rgb, const float* g_disp, const float* g_acc, const float* g_raw, float* grad, float* d_raw) {
+    PassBwdDev P = {};
+    P.w0 = packed_bwd; P.b0 = packed_bwd + w_floats; P.bits = bits; P.raw = raw; P.z = z_vals; P.ray_batch = ray_batch;
+    P.cols = cols; P.noise = noise; P.n_rays = n_rays; P.S = n_samples; P.white = white_bkgd;
+    P.g_rgb = g_rgb; P.g_disp = g_disp; P.g_acc = g_acc; P.g_raw = g_raw; P.grad = grad; P.d_raw = d_raw;
+    P.out_ch = 4;
+    return P;
+}
+
+template <int MODE>
+static int pass_bwd_launch(const char* what, const PassBwdDev& P, int bias_tiles, void* stream) {
+    const size_t lds = (bias_tiles * SW_BIAS_TILE_FLOATS + 4 * SW_LDS_RING_FLOATS + 4 * PB_WAVE_FLOATS) * sizeof(float);
+    hipLaunchKernelGGL(render_pass_backward_kernel<MODE>, dim3((unsigned)((P.n_rays + 3) / 4)), dim3(256), lds, (hipStream_t)stream, P);
+    return sw_check(hipGetLastError(), what);
+}
+
 extern "C" int swnerf_render_pass_backward(const float* packed_bwd, const float* bits, const float* raw, const float* z_vals,
                                            const float* ray_batch, int cols, const float* noise, int64_t n_rays, int n_samples,
                                            int white_bkgd, const float* g_rgb, const float* g_disp, const float* g_acc,
                                            const float* g_raw, float* grad, float* d_raw, void* stream) {
     if (n_rays == 0 && packed_bwd) return 0;
-    if (!packed_bwd || !bits || !raw || !z_vals || !ray_batch || !grad || !d_raw || n_rays < 0)
-        return sw_fail(SWNERF_E_ARG, "render_pass_backward: NULL pointer or negative n_rays");
-    if (n_samples < 2 || n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "render_pass_backward: 2 <= n_samples <= %d (got %d)", PB_SMAX, n_samples);
+    if (int rc = pass_bwd_check("render_pass_backward", packed_bwd && bits && raw && z_vals && ray_batch && grad && d_raw, n_rays, n_samples)) return rc;
     if (cols < 8) return sw_fail(SWNERF_E_ARG, "render_pass_backward: ray_batch needs >= 8 columns");
-    PassBwdDev P;
-    P.w0 = packed_bwd; P.b0 = packed_bwd + SW_BWD_W_FLOATS; P.bits = bits; P.raw = raw; P.z = z_vals; P.ray_batch = ray_batch;
-    P.cols = cols; P.noise = noise; P.n_rays = n_rays; P.S = n_samples; P.white = white_bkgd;
-    P.g_rgb = g_rgb; P.g_disp = g_disp; P.g_acc = g_acc; P.g_raw = g_raw; P.grad = grad; P.d_raw = d_raw;
-    const size_t lds = (SW_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS + 4 * SW_LDS_RING_FLOATS + 4 * PB_WAVE_FLOATS) * sizeof(float);
-    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-    P.bits_d = nullptr; P.dx = nullptr; P.g_pd = nullptr; P.Lp = 0; P.grad_d = nullptr; P.g_dx = nullptr;
-    P.out_ch = 4;
-    hipLaunchKernelGGL(render_pass_backward_kernel<0>, grid, block, lds, (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "render_pass_backward launch");
+    const PassBwdDev P = pass_bwd_dev(packed_bwd, SW_BWD_W_FLOATS, bits, raw, z_vals, ray_batch, cols, noise, n_rays, n_samples, white_bkgd,
+                                      g_rgb, g_disp, g_acc, g_raw, grad, d_raw);
+    return pass_bwd_launch<0>("render_pass_backward launch", P, SW_BWD_BIAS_TILES, stream);
 }
 
 // ... and for the net without view directions (SWNERF_NET_NOVIEW): raw / g_raw [N,S,out_ch], d_raw [rows, 8] (columns
@@ -614,47 +615,34 @@ extern "C" int swnerf_render_pass_backward_noview(const float* packed_bwd, const
                                                   int white_bkgd, int out_ch, const float* g_rgb, const float* g_disp, const float* g_acc,
                                                   const float* g_raw, float* grad, float* d_raw8, void* stream) {
     if (n_rays == 0 && packed_bwd) return 0;
-    if (!packed_bwd || !bits || !raw || !z_vals || !ray_batch || !grad || !d_raw8 || n_rays < 0)
-        return sw_fail(SWNERF_E_ARG, "render_pass_backward_noview: NULL pointer or negative n_rays");
-    if (n_samples < 2 || n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "render_pass_backward_noview: 2 <= n_samples <= %d (got %d)", PB_SMAX, n_samples);
+    if (int rc = pass_bwd_check("render_pass_backward_noview", packed_bwd && bits && raw && z_vals && ray_batch && grad && d_raw8, n_rays, n_samples)) return rc;
     if (cols < 8 || out_ch < 4 || out_ch > SW_NOVIEW_MAX_OUT) return sw_fail(SWNERF_E_ARG, "render_pass_backward_noview: cols %d / out_ch %d", cols, out_ch);
-    PassBwdDev P;
-    P.w0 = packed_bwd; P.b0 = packed_bwd + SW_DBWD_W_FLOATS; P.bits = bits; P.raw = raw; P.z = z_vals; P.ray_batch = ray_batch;
-    P.cols = cols; P.noise = noise; P.n_rays = n_rays; P.S = n_samples; P.white = white_bkgd;
-    P.g_rgb = g_rgb; P.g_disp = g_disp; P.g_acc = g_acc; P.g_raw = g_raw; P.grad = grad; P.d_raw = d_raw8;
-    P.bits_d = nullptr; P.dx = nullptr; P.g_pd = nullptr; P.Lp = 0; P.grad_d = nullptr; P.g_dx = nullptr;
+    PassBwdDev P = pass_bwd_dev(packed_bwd, SW_DBWD_W_FLOATS, bits, raw, z_vals, ray_batch, cols, noise, n_rays, n_samples, white_bkgd,
+                                g_rgb, g_disp, g_acc, g_raw, grad, d_raw8);
     P.out_ch = out_ch;
-    const size_t lds = (SW_NVBWD_BIAS_TILES * SW_BIAS_TILE_FLOATS + 4 * SW_LDS_RING_FLOATS + 4 * PB_WAVE_FLOATS) * sizeof(float);
-    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-    hipLaunchKernelGGL(render_pass_backward_kernel<2>, grid, block, lds, (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "render_pass_backward_noview launch");
+    return pass_bwd_launch<2>("render_pass_backward_noview launch", P, SW_NVBWD_BIAS_TILES, stream);
 }
 
 // ---- the same for DirectTemporalNeRF at t != 0 (model.py:128-151; loss of d_nerf/run_dnerf.py:690-725) ----------------
 extern "C" int swnerf_render_pass_train_dnerf(const swnerf_pass_args* args, float* act, float* bits, float* xs,
                                               float* act_d, float* bits_d, float* xs_d, void* stream) {
+    static const PassAccepts accepts = {"render_pass_train_dnerf", {0, SW_COLS(12), 0, 0}, SWNERF_E_UNSUPP,
+        "%s: DirectTemporalNeRF with the deformation pass (t != 0) and a 12-column ray batch", true, PB_SMAX};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass_train_dnerf: NULL args");
     const swnerf_pass_args& a = *args;
     if (a.n_rays == 0 && a.packed) return 0;
-    if (!a.packed || !a.ray_batch || !act || !bits || !xs || !act_d || !bits_d || !xs_d) return sw_fail(SWNERF_E_ARG, "render_pass_train_dnerf: NULL pointer");
-    if (a.kind != SWNERF_NET_DNERF || a.cols != 12 || !a.run_deform)
-        return sw_fail(SWNERF_E_UNSUPP, "render_pass_train_dnerf: DirectTemporalNeRF with the deformation pass (t != 0) and a 12-column ray batch");
-    if (a.n_rays < 0 || a.n_samples < 2 || a.n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "render_pass_train_dnerf: 2 <= n_samples <= %d (got %d)", PB_SMAX, a.n_samples);
+    if (!act || !bits || !xs || !act_d || !bits_d || !xs_d) return sw_fail(SWNERF_E_ARG, "render_pass_train_dnerf: NULL pointer");
+    int rc = pass_check(accepts, a);
+    if (rc) return rc;
+    if (!a.run_deform) return sw_fail(accepts.shape_code, accepts.shape_msg, accepts.name);
     if (a.n_importance != 0) return sw_fail(SWNERF_E_UNSUPP, "render_pass_train_dnerf: no resampling in the training pass (give the depths)");
     if (!a.raw || !a.dx || !(a.z_vals || a.z_out)) return sw_fail(SWNERF_E_ARG, "render_pass_train_dnerf: the backward needs raw, dx and the depths (z_vals given or z_out)");
-    if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4 || a.L_time < 0 || a.L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "render_pass_train_dnerf: embedder bands (%d,%d,%d) exceed (10,4,10)", a.L_pos, a.L_dir, a.L_time);
-    if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "render_pass_train_dnerf: t_rand only applies to coarse sampling");
-    PassDev P;
-    P.a = a;
-    int rc = stream_ptrs(a.kind, a.packed, 1, &P.w0, &P.b0, &P.nbias, &P.two_pass);
-    if (rc) return rc;
+    PassDev P = pass_dev(a);
+    if ((rc = stream_ptrs(a.kind, a.packed, 1, &P.w0, &P.b0, &P.nbias, &P.two_pass))) return rc;
     P.act = act; P.bits = bits; P.xs = xs; P.act_d = act_d; P.bits_d = bits_d; P.xs_d = xs_d;
-    P.sort_n = 0; P.sort_s = 0;
     P.dir_steps = SW_STEPS_DIR;
     P.time_steps = SW_STEPS_TIME;
     P.tb_off = PassLds<true, true>::FIXED;       // the four waves' per-ray TIME tiles, behind everything else
-    P.warm_steps = 0; P.warm_blocks = 0; P.skew_mode = 0; P.skew_unit = 0;
     const size_t lds = (PassLds<true, true>::FIXED + 4 * SW_TB_LDS_FLOATS) * sizeof(float);
     const dim3 grid((unsigned)((a.n_rays + 3) / 4)), block(256);
     pass_startup_args(P, grid.x, SW_DEFORM_STEPS + SW_CANON_STEPS);
@@ -668,18 +656,11 @@ extern "C" int swnerf_render_pass_backward_dnerf(const float* packed_bwd_fused, 
                                                  int white_bkgd, int L_pos, const float* g_rgb, const float* g_disp, const float* g_acc,
                                                  const float* g_raw, float* grad, float* grad_d, float* d_raw, float* g_dx, void* stream) {
     if (n_rays == 0 && packed_bwd_fused) return 0;
-    if (!packed_bwd_fused || !bits || !bits_d || !raw || !z_vals || !ray_batch || !dx || !grad || !grad_d || !d_raw || !g_dx || n_rays < 0)
-        return sw_fail(SWNERF_E_ARG, "render_pass_backward_dnerf: NULL pointer or negative n_rays");
-    if (n_samples < 2 || n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "render_pass_backward_dnerf: 2 <= n_samples <= %d (got %d)", PB_SMAX, n_samples);
+    if (int rc = pass_bwd_check("render_pass_backward_dnerf", packed_bwd_fused && bits && bits_d && raw && z_vals && ray_batch && dx && grad && grad_d && d_raw && g_dx,
+                                n_rays, n_samples)) return rc;
     if (cols < 8 || L_pos < 0 || L_pos > 10) return sw_fail(SWNERF_E_ARG, "render_pass_backward_dnerf: cols %d / L_pos %d", cols, L_pos);
-    PassBwdDev P;
-    P.w0 = packed_bwd_fused; P.b0 = packed_bwd_fused + SW_BWD_DN_W_FLOATS; P.bits = bits; P.raw = raw; P.z = z_vals; P.ray_batch = ray_batch;
-    P.cols = cols; P.noise = noise; P.n_rays = n_rays; P.S = n_samples; P.white = white_bkgd;
-    P.g_rgb = g_rgb; P.g_disp = g_disp; P.g_acc = g_acc; P.g_raw = g_raw; P.grad = grad; P.d_raw = d_raw;
+    PassBwdDev P = pass_bwd_dev(packed_bwd_fused, SW_BWD_DN_W_FLOATS, bits, raw, z_vals, ray_batch, cols, noise, n_rays, n_samples, white_bkgd,
+                                g_rgb, g_disp, g_acc, g_raw, grad, d_raw);
     P.bits_d = bits_d; P.dx = dx; P.g_pd = g_position_delta; P.Lp = L_pos; P.grad_d = grad_d; P.g_dx = g_dx;
-    const size_t lds = ((SW_BWD_BIAS_TILES + SW_DBWD_BIAS_TILES) * SW_BIAS_TILE_FLOATS + 4 * SW_LDS_RING_FLOATS + 4 * PB_WAVE_FLOATS) * sizeof(float);
-    const dim3 grid((unsigned)((n_rays + 3) / 4)), block(256);
-    P.out_ch = 4;
-    hipLaunchKernelGGL(render_pass_backward_kernel<1>, grid, block, lds, (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "render_pass_backward_dnerf launch");
+    return pass_bwd_launch<1>("render_pass_backward_dnerf launch", P, SW_BWD_BIAS_TILES + SW_DBWD_BIAS_TILES, stream);
 }

@@ -146,43 +146,26 @@ extern "C" int swnerf_pack_net_x3(const float* const* params, int L_pos, int L_d
 }
 
 extern "C" int swnerf_render_pass_x3(const swnerf_pass_args* args, int terms, void* stream) {
+    static const PassAccepts accepts = {"render_pass_x3", {SW_COLS(11) | SW_COLS(12), SW_COLS(11) | SW_COLS(12), 0, 0},
+        SWNERF_E_ARG, "%s: ray_batch must have 11 or 12 columns, got %d", true, 0};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass_x3: NULL args");
     const swnerf_pass_args& a = *args;
     if (terms != 1 && terms != 3) return sw_fail(SWNERF_E_ARG, "render_pass_x3: terms must be 3 (bf16x3) or 1 (plain bf16), got %d", terms);
-    if (!a.packed || (!a.ray_batch && a.n_rays != 0)) return sw_fail(SWNERF_E_ARG, "render_pass_x3: NULL ray_batch/packed");
     if (a.kind != SWNERF_NET_CANON && a.kind != SWNERF_NET_DNERF) return sw_fail(SWNERF_E_ARG, "render_pass_x3: unknown net kind %d", a.kind);
-    if (a.n_rays < 0 || a.n_samples < 2) return sw_fail(SWNERF_E_ARG, "render_pass_x3: n_rays %lld, n_samples %d", (long long)a.n_rays, a.n_samples);
-    if (a.cols != 11 && a.cols != 12) return sw_fail(SWNERF_E_ARG, "render_pass_x3: ray_batch must have 11 or 12 columns, got %d", a.cols);
+    int rc = pass_check(accepts, a);
+    if (rc) return rc;
     if (a.kind == SWNERF_NET_DNERF && a.cols != 12) return sw_fail(SWNERF_E_ARG, "render_pass_x3: D-NeRF needs the frame_time column");
-    if (a.L_pos < 0 || a.L_pos > 10 || a.L_dir < 0 || a.L_dir > 4 || a.L_time < 0 || a.L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "render_pass_x3: embedder bands (%d,%d,%d) exceed (10,4,10)", a.L_pos, a.L_dir, a.L_time);
-    if (a.z_vals && a.t_rand) return sw_fail(SWNERF_E_ARG, "render_pass_x3: t_rand only applies to coarse sampling");
     const bool dn = a.kind == SWNERF_NET_DNERF;
-    PassDev P = {};
-    P.a = a;
+    PassDev P = pass_dev(a);
     P.nbias = SW_X3_CANON_BIAS_TILES * SW_BIAS_TILE_FLOATS;
     if (!dn) { P.w0 = a.packed; P.b0 = a.packed + SW_X3_W_FLOATS; }
     else if (a.run_deform) { P.w0 = a.packed; P.b0 = a.packed + SW_X3_DNERF_W_FLOATS; P.two_pass = 1; P.nbias = (SW_DEFORM_BIAS_TILES + SW_X3_CANON_BIAS_TILES) * SW_BIAS_TILE_FLOATS; }
     else { const float* c = a.packed + SW_X3_DNERF_A_FLOATS; P.w0 = c; P.b0 = c + SW_X3_W_FLOATS; }
     size_t lds = (size_t)(dn ? X3Lds<true>::FIXED : X3Lds<false>::FIXED) * sizeof(float);
-    if (a.n_importance > 0) {
-        if (!a.z_fine && a.n_rays != 0) return sw_fail(SWNERF_E_ARG, "render_pass_x3: n_importance>0 needs z_fine");
-        if (a.n_samples < 3 || a.n_samples > SW_LDS_SC || a.n_samples + a.n_importance > SW_LDS_SORT)
-            return sw_fail(SWNERF_E_UNSUPP, "render_pass_x3: resampling supports 3<=N_samples<=%d and N_samples+N_importance<=%d", SW_LDS_SC, SW_LDS_SORT);
-        int p2 = 2;
-        while (p2 < a.n_importance) p2 <<= 1;
-        P.sort_n = p2;
-        p2 = 2;
-        while (p2 < a.n_samples) p2 <<= 1;
-        P.sort_s = p2;
-        lds += 4 * SW_LDS_WAVE_FLOATS * sizeof(float);
-    }
+    if ((rc = pass_resampling(accepts.name, a, P, lds))) return rc;
     if (a.n_rays == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (!dn && a.dx) {
-        int rc = sw_check(hipMemsetAsync(a.dx, 0, (size_t)a.n_rays * a.n_samples * 3 * sizeof(float), st), "render_pass_x3 dx fill");
-        if (rc) return rc;
-    }
+    if (!dn && a.dx && (rc = sw_check(hipMemsetAsync(a.dx, 0, (size_t)a.n_rays * a.n_samples * 3 * sizeof(float), st), "render_pass_x3 dx fill"))) return rc;
     const dim3 grid((unsigned)((a.n_rays + 3) / 4)), block(256);
     if (dn) {
         if (terms == 3) hipLaunchKernelGGL((render_pass_kernel<true, false, 3>), grid, block, lds, st, P);

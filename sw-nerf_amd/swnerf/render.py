@@ -160,6 +160,33 @@ def prepack(*nets):
                 net.packed_x3()
 
 
+def pass_args(rb, kind, packed, bands, S, out_ch, run_deform, inputs, outputs, n_importance=0, *, lindisp=False,
+              white_bkgd=False, who="render_pass"):
+    """The `swnerf_pass_args` of one launch (include/swnerf.h), for every entry point of the fused pass.  inputs: the
+    optional [N, S] operands z_vals / t_rand / noise (and u [N, n_importance]) by name, None = absent; outputs: names of
+    the outputs to allocate (plus z_fine / z_std when n_importance > 0).  -> (args, outputs, tensors to keep alive)."""
+    N, cols = rb.shape
+    Ni = int(n_importance)
+    a = _lib.PassArgs()
+    a.ray_batch, a.n_rays, a.cols, a.kind, a.packed = rb.data_ptr(), N, cols, kind, packed.data_ptr()
+    a.run_deform, (a.L_pos, a.L_dir, a.L_time), a.n_samples, a.out_ch = int(bool(run_deform)), bands, S, out_ch
+    a.lindisp, a.white_bkgd, a.n_importance = int(bool(lindisp)), int(bool(white_bkgd)), Ni
+    keep = [rb, packed]
+    for name, t in inputs.items():
+        if t is not None:
+            t = _lib.dev_f32(t, name, Ni if name == "u" else S)
+            if t.shape[0] != N:
+                raise ValueError(f"swnerf.{who}: {name} must have {N} rows, got {tuple(t.shape)}")
+            keep.append(t)
+            setattr(a, name, t.data_ptr())
+    shapes = {"rgb_map": (N, 3), "disp_map": (N,), "acc_map": (N,), "depth_map": (N,), "weights": (N, S), "raw": (N, S, out_ch),
+              "dx": (N, S, 3), "z_out": (N, S), "z_fine": (N, S + Ni), "z_std": (N,)}
+    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=rb.device) for k in list(outputs) + (["z_fine", "z_std"] if Ni > 0 else [])}
+    for k, t in out.items():
+        setattr(a, k, t.data_ptr())
+    return a, out, keep
+
+
 def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand=None, noise=None, white_bkgd=False,
                 want=("rgb_map", "disp_map", "acc_map"), n_importance=0, u=None, run_deform=True, precision=None):
     """One launch of `swnerf_render_pass` (include/swnerf.h).  Returns a dict of the requested
@@ -184,33 +211,9 @@ def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand
         if terms:
             packed, _, _ = net.packed_x3()
     rb = _lib.dev_f32(ray_batch, "ray_batch")
-    N, cols = rb.shape
-    S = int(n_samples)
-    dev = rb.device
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    shapes = {"rgb_map": (N, 3), "disp_map": (N,), "acc_map": (N,), "depth_map": (N,), "weights": (N, S),
-              "raw": (N, S, out_ch), "dx": (N, S, 3), "z_out": (N, S)}
-    out = {k: new(*shapes[k]) for k in want}
-    a = _lib.PassArgs()
-    a.ray_batch, a.n_rays, a.cols, a.kind, a.packed = rb.data_ptr(), N, cols, kind, packed.data_ptr()
-    a.run_deform, a.L_pos, a.L_dir, a.L_time, a.n_samples = int(bool(run_deform)), Lp, Ld, Lt, S
-    a.out_ch = out_ch
-    keep = [rb, packed]
-    for name, t, last in (("z_vals", z_vals, S), ("t_rand", t_rand, S), ("noise", noise, S), ("u", u, int(n_importance))):
-        if t is not None:
-            t = _lib.dev_f32(t, name, last)
-            if t.shape[0] != N:
-                raise ValueError(f"swnerf.render_pass: {name} must have {N} rows, got {tuple(t.shape)}")
-            keep.append(t)
-            setattr(a, name, t.data_ptr())
-    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
-    for k, t in out.items():
-        setattr(a, k, t.data_ptr())
-    a.n_importance = int(n_importance)
-    if n_importance > 0:
-        out["z_fine"] = new(N, S + int(n_importance))
-        out["z_std"] = new(N)
-        a.z_fine, a.z_std = out["z_fine"].data_ptr(), out["z_std"].data_ptr()
+    N, S = rb.shape[0], int(n_samples)
+    a, out, _keep = pass_args(rb, kind, packed, (Lp, Ld, Lt), S, out_ch, run_deform, dict(z_vals=z_vals, t_rand=t_rand, noise=noise, u=u),
+                              want, n_importance, lindisp=lindisp, white_bkgd=white_bkgd)
     if PASS_HOOK is not None:
         PASS_HOOK("begin", N, S)
     if terms:
@@ -220,6 +223,36 @@ def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand
     if PASS_HOOK is not None:
         PASS_HOOK("end", N, S)
     return out
+
+
+def chunked_backward(rb, act_rows, div, widths, launch, gemm_jobs, rest_on_main=True):
+    """The backward of a fused training pass, per CHUNK of rays.  The gradient buffer [rows, 2432] is as large as the saved
+    activations; the dX chain and the GEMMs that consume it run per chunk, so only one chunk of it is ever alive (GEMMs
+    accumulate: C += A^T.B).  A chunk is TRAIN_BWD_CHUNK_ROWS // div rows (393 216 at the C2 shape: large enough for the
+    split-K GEMMs to fill the chip), whole rays, a multiple of 4.  widths: columns of the buffers a chunk holds;
+    launch(r0, r1, bufs) runs the backward kernel on rays r0:r1; gemm_jobs(a0, a1, m, bufs) -> the jobs of wgrad._chunk_gemms
+    on the rows a0:a1 of the saved tensors (m = a1 - a0 rows of every buffer), which fan out over side streams (wgrad._Fan)."""
+    from .wgrad import _Fan, _chunk_gemms
+    N = rb.shape[0]
+    rows_per_ray = act_rows // N
+    chunk = max(4, (TRAIN_BWD_CHUNK_ROWS // div // rows_per_ray) // 4 * 4)
+    bufs = [torch.empty((min(N, chunk) * rows_per_ray, w), dtype=torch.float32, device=rb.device) for w in widths]
+    fan = _Fan(rb.device)
+    for r0 in range(0, N, chunk):
+        r1 = min(N, r0 + chunk)
+        launch(r0, r1, bufs)
+        _chunk_gemms(_lib.lib(), fan, (r1 - r0) * rows_per_ray, gemm_jobs(r0 * rows_per_ray, r1 * rows_per_ray, (r1 - r0) * rows_per_ray, bufs),
+                     rest_on_main=rest_on_main)
+
+
+def f32_grads(*gs):
+    """Upstream gradients as the kernels read them (an output the loss does not use arrives as None and stays None)."""
+    return [None if g is None else g.contiguous().float() for g in gs]
+
+
+def ray_ptrs(r0, r1, *ts, per_ray=1):
+    """Pointers to the rows of rays r0:r1 of each tensor (None stays NULL)."""
+    return [_lib.ptr(None if t is None else t[r0 * per_ray:r1 * per_ray]) for t in ts]
 
 
 class _FusedPassTrain(torch.autograd.Function):
@@ -240,33 +273,15 @@ class _FusedPassTrain(torch.autograd.Function):
         else:
             kind, packed, Lp, Ld, _ = net.packed()
         L = _lib.lib()
-        N, cols = rb.shape
-        dev = rb.device
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        N = rb.shape[0]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
         rows = L.swnerf_train_rows(N, S)
         act, bits, xs = new(rows, L.swnerf_act_floats_per_row()), new(L.swnerf_mask_floats(rows)), new(rows, L.swnerf_xs_floats_per_row())
-        raw, rgb, disp, acc = new(N, S, out_ch), new(N, 3), new(N), new(N)
-        a = _lib.PassArgs()
-        a.ray_batch, a.n_rays, a.cols, a.kind, a.packed = rb.data_ptr(), N, cols, kind, packed.data_ptr()
-        a.out_ch = out_ch
-        a.run_deform, a.L_pos, a.L_dir, a.L_time, a.n_samples = 0, Lp, Ld, 0, S
-        a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
-        a.rgb_map, a.disp_map, a.acc_map, a.raw = rgb.data_ptr(), disp.data_ptr(), acc.data_ptr(), raw.data_ptr()
-        if z_vals is not None:
-            z = z_vals
-            a.z_vals = z.data_ptr()
-        else:
-            z = new(N, S)
-            a.z_out = z.data_ptr()
-        for name, t in (("t_rand", t_rand), ("noise", noise), ("u", u)):
-            if t is not None:
-                setattr(a, name, t.data_ptr())
-        a.n_importance = int(n_importance)
-        if n_importance > 0:
-            z_fine, z_std = new(N, S + int(n_importance)), new(N)
-            a.z_fine, a.z_std = z_fine.data_ptr(), z_std.data_ptr()
-        else:
-            z_fine, z_std = new(0), new(0)
+        a, o, _keep = pass_args(rb, kind, packed, (Lp, Ld, 0), S, out_ch, 0, dict(z_vals=z_vals, t_rand=t_rand, noise=noise, u=u),
+                                ["rgb_map", "disp_map", "acc_map", "raw"] + ([] if z_vals is not None else ["z_out"]), n_importance,
+                                lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_train")
+        z = z_vals if z_vals is not None else o["z_out"]
+        z_fine, z_std = (o["z_fine"], o["z_std"]) if n_importance > 0 else (new(0), new(0))
         if PASS_HOOK is not None:
             PASS_HOOK("begin", N, S)
         _lib.check(L.swnerf_render_pass_train(a, _lib.ptr(act), _lib.ptr(bits), _lib.ptr(xs), _lib.stream_of(rb)), "render_pass_train")
@@ -274,51 +289,34 @@ class _FusedPassTrain(torch.autograd.Function):
             PASS_HOOK("end", N, S)
         ctx.net, ctx.S, ctx.white, ctx.bands = net, S, bool(white_bkgd), (Lp, Ld)
         ctx.has_noise, ctx.noview, ctx.out_ch = noise is not None, noview, out_ch
-        ctx.save_for_backward(rb, z, raw, act, bits, xs, noise if noise is not None else new(0), *params)
+        ctx.save_for_backward(rb, z, o["raw"], act, bits, xs, noise if noise is not None else new(0), *params)
         ctx.mark_non_differentiable(z_fine, z_std)
         ctx.set_materialize_grads(False)       # an output the loss does not use arrives as None (no zero fill, no read of zeros in the kernel)
         # raw is an output as well (retraw=True is what the reference's train() passes, nerf/run.py:685): a gradient
         # arriving on it is added to d raw in the backward kernel
-        return rgb, disp, acc, z_fine, z_std, raw
+        return o["rgb_map"], o["disp_map"], o["acc_map"], z_fine, z_std, o["raw"]
 
     @staticmethod
-    def backward(ctx, g_rgb, g_disp, g_acc, _gz, _gs, g_raw):
-        from .wgrad import WeightGrads, _Fan, _chunk_gemms
+    def backward(ctx, *grads_out):
+        from .wgrad import WeightGrads
         rb, z, raw, act, bits, xs, noise, *params = ctx.saved_tensors
-        net, S = ctx.net, ctx.S
+        net, S, nv = ctx.net, ctx.S, ctx.noview
         Lp, Ld = ctx.bands
         L = _lib.lib()
         N, cols = rb.shape
         st = _lib.stream_of(rb)
-        c = lambda g: None if g is None else g.contiguous().float()
-        g_rgb, g_disp, g_acc, g_raw = c(g_rgb), c(g_disp), c(g_acc), c(g_raw)
-        nv = ctx.noview
+        g_rgb, g_disp, g_acc, _gz, _gs, g_raw = f32_grads(*grads_out)
         wg = WeightGrads(L, "noview" if nv else "canon", params, fused=True, Cpos=net.input_ch, Cdir=0 if nv else net.input_ch_views, bands=(Lp, Ld, 0))
-        # The gradient buffer [rows, 2432] is as large as the saved activations; the dX chain and the GEMMs that consume
-        # it run per CHUNK of rays, so only one chunk of it is ever alive (GEMMs accumulate: C += A^T.B).  A chunk is
-        # 393 216 rows at the C2 shape - large enough for the split-K GEMMs to fill the chip.
-        rows_per_ray = act.shape[0] // N
-        chunk = max(4, (TRAIN_BWD_CHUNK_ROWS // rows_per_ray) // 4 * 4)
         packed_bwd = net.packed_bwd_noview() if nv else net.packed_bwd()
-        mask_per_ray = bits.numel() // N
-        sl = lambda t, r0, r1: None if t is None else t[r0:r1]
-        grad = torch.empty((min(N, chunk) * rows_per_ray, act.shape[1]), dtype=torch.float32, device=rb.device)
-        d_raw = torch.empty((min(N, chunk) * rows_per_ray, 8 if nv else 4), dtype=torch.float32, device=rb.device)
-        fan = _Fan(rb.device)                                    # the GEMMs of a chunk fan out over side streams (wgrad._Fan)
-        for r0 in range(0, N, chunk):
-            r1 = min(N, r0 + chunk)
-            n, m = r1 - r0, (r1 - r0) * rows_per_ray
-            common = (_lib.ptr(packed_bwd), _lib.ptr(bits[r0 * mask_per_ray:r1 * mask_per_ray]), _lib.ptr(raw[r0:r1]), _lib.ptr(z[r0:r1]),
-                      _lib.ptr(rb[r0:r1]), cols, _lib.ptr(noise[r0:r1]) if ctx.has_noise else None, n, S, int(ctx.white))
-            grads_in = (_lib.ptr(sl(g_rgb, r0, r1)), _lib.ptr(sl(g_disp, r0, r1)), _lib.ptr(sl(g_acc, r0, r1)), _lib.ptr(sl(g_raw, r0, r1)),
-                        _lib.ptr(grad), _lib.ptr(d_raw), st)
-            if nv:
-                _lib.check(L.swnerf_render_pass_backward_noview(*common, ctx.out_ch, *grads_in), "render_pass_backward_noview")
-            else:
-                _lib.check(L.swnerf_render_pass_backward(*common, *grads_in), "render_pass_backward")
-            a0, a1 = r0 * rows_per_ray, r1 * rows_per_ray
-            job = lambda st_, part: wg.chunk(st_, m, grad[:m], act[a0:a1], xs[a0:a1], d_raw[:m], part=part)
-            _chunk_gemms(L, fan, m, [job], rest_on_main=not nv)      # (the no-view net has no fused narrow kernel)
+        fn, what = (L.swnerf_render_pass_backward_noview, "render_pass_backward_noview") if nv else (L.swnerf_render_pass_backward, "render_pass_backward")
+
+        def launch(r0, r1, bufs):
+            _lib.check(fn(_lib.ptr(packed_bwd), *ray_ptrs(r0, r1, bits, per_ray=bits.numel() // N), *ray_ptrs(r0, r1, raw, z, rb), cols,
+                          *ray_ptrs(r0, r1, noise if ctx.has_noise else None), r1 - r0, S, int(ctx.white), *([ctx.out_ch] if nv else []),
+                          *ray_ptrs(r0, r1, g_rgb, g_disp, g_acc, g_raw), _lib.ptr(bufs[0]), _lib.ptr(bufs[1]), st), what)
+
+        jobs = lambda a0, a1, m, bufs: [lambda st_, part: wg.chunk(st_, m, bufs[0][:m], act[a0:a1], xs[a0:a1], bufs[1][:m], part=part)]
+        chunked_backward(rb, act.shape[0], 1, (act.shape[1], 8 if nv else 4), launch, jobs, rest_on_main=not nv)   # (the no-view net has no fused narrow kernel)
         return (None,) * 10 + tuple(gi.to(p.dtype) for gi, p in zip(wg.finish(st), params))
 
 
@@ -327,12 +325,9 @@ def render_pass_train(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, 
     """One differentiable fused pass (`_FusedPassTrain`): dict with rgb_map disp_map acc_map raw (+ z_fine z_std)."""
     from .model import _CANON_ORDER, _NOVIEW_ORDER
     rb = _lib.dev_f32(ray_batch.detach(), "ray_batch")
-    N, S = rb.shape[0], int(n_samples)
+    S = int(n_samples)
     chk = lambda t, name, last: None if t is None else _lib.dev_f32(t.detach(), name, last)
     z_vals, t_rand, noise, u = chk(z_vals, "z_vals", S), chk(t_rand, "t_rand", S), chk(noise, "noise", S), chk(u, "u", int(n_importance))
-    for name, t in (("z_vals", z_vals), ("t_rand", t_rand), ("noise", noise), ("u", u)):
-        if t is not None and t.shape[0] != N:
-            raise ValueError(f"swnerf.render_pass_train: {name} must have {N} rows, got {tuple(t.shape)}")
     sd = dict(net.named_parameters())
     rgb, disp, acc, z_fine, z_std, raw = _FusedPassTrain.apply(net, rb, z_vals, S, bool(lindisp), t_rand, noise, bool(white_bkgd),
                                                                int(n_importance), u,
@@ -381,19 +376,25 @@ TRAIN_FUSED_MAX_SAMPLES = 256      # include/swnerf.h: swnerf_render_pass_train
 TRAIN_BWD_CHUNK_ROWS = int(os.environ.get("SWNERF_TRAIN_BWD_CHUNK_ROWS", "393216"))
 
 
+def _draw_t_rand(N, N_samples, perturb, pytest, dev):
+    """The stratified-sampling draw (nerf/run.py:375-381), None when perturb is off."""
+    if not perturb > 0.:
+        return None
+    t_rand = torch.rand((N, N_samples), device=dev)
+    if pytest:
+        np.random.seed(0)
+        t_rand = torch.Tensor(np.random.rand(N, N_samples)).to(dev)
+    return t_rand
+
+
 def _rng_inputs(N, N_samples, N_importance, perturb, raw_noise_std, pytest, dev):
     """The three random tensors of render_rays (nerf/run.py:375-381, ray.py:117-132, :176-184)."""
-    t_rand = u = None
-    if perturb > 0.:
-        t_rand = torch.rand((N, N_samples), device=dev)
+    t_rand, u = _draw_t_rand(N, N_samples, perturb, pytest, dev), None
+    if perturb > 0. and N_importance > 0:
+        u = torch.rand((N, N_importance), device=dev)
         if pytest:
             np.random.seed(0)
-            t_rand = torch.Tensor(np.random.rand(N, N_samples)).to(dev)
-        if N_importance > 0:
-            u = torch.rand((N, N_importance), device=dev)
-            if pytest:
-                np.random.seed(0)
-                u = torch.Tensor(np.random.rand(N, N_importance)).to(dev)
+            u = torch.Tensor(np.random.rand(N, N_importance)).to(dev)
 
     def noise(S):
         if not raw_noise_std > 0.:
@@ -425,43 +426,44 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                     N_importance, network_fine, white_bkgd, raw_noise_std, pytest)
     N = ray_batch.shape[0]
     t_rand, u, noise = _rng_inputs(N, N_samples, N_importance, perturb, raw_noise_std, pytest, ray_batch.device)
+    S1 = N_samples + N_importance
+    run_fn = network_fn if network_fine is None else network_fine
     if training:
         p0 = render_pass_train(ray_batch, network_fn, N_samples, lindisp=lindisp, t_rand=t_rand, noise=noise(N_samples),
                                white_bkgd=white_bkgd, n_importance=max(0, N_importance), u=u)
         if N_importance <= 0:
-            ret = {'rgb_map': p0["rgb_map"], 'disp_map': p0["disp_map"], 'acc_map': p0["acc_map"]}
-            if retraw:
-                ret['raw'] = p0["raw"]
-            return ret
-        S1 = N_samples + N_importance
-        run_fn = network_fn if network_fine is None else network_fine
+            return result_dict(p0, retraw)
         p1 = render_pass_train(ray_batch, run_fn, S1, z_vals=p0["z_fine"], noise=noise(S1), white_bkgd=white_bkgd)
-        ret = {'rgb_map': p1["rgb_map"], 'disp_map': p1["disp_map"], 'acc_map': p1["acc_map"]}
-        if retraw:
-            ret['raw'] = p1["raw"]
-        ret.update({'rgb0': p0["rgb_map"], 'disp0': p0["disp_map"], 'acc0': p0["acc_map"], 'z_std': p0["z_std"]})
-        return ret
+        return result_dict(p1, retraw, p0, z_std=p0["z_std"])
     want = ["rgb_map", "disp_map", "acc_map"] + (["raw"] if (retraw and N_importance <= 0) else [])
     if N_importance <= 0:
-        p0 = render_pass(ray_batch, network_fn, N_samples, lindisp=lindisp, t_rand=t_rand, noise=noise(N_samples),
-                         white_bkgd=white_bkgd, want=want)
-        ret = {'rgb_map': p0["rgb_map"], 'disp_map': p0["disp_map"], 'acc_map': p0["acc_map"]}
-        if retraw:
-            ret['raw'] = p0["raw"]
-        return ret
+        return result_dict(render_pass(ray_batch, network_fn, N_samples, lindisp=lindisp, t_rand=t_rand, noise=noise(N_samples),
+                                       white_bkgd=white_bkgd, want=want), retraw)
     p0 = coarse_pass_resampled(ray_batch, network_fn, N_samples, N_importance, want=want, u=u, lindisp=lindisp, t_rand=t_rand,
                                noise=noise(N_samples), white_bkgd=white_bkgd)
-    S1 = N_samples + N_importance
     if Z_TAP is not None:
         Z_TAP["fused"] = p0["z_fine"]
-    run_fn = network_fn if network_fine is None else network_fine
     p1 = render_pass(ray_batch, run_fn, S1, z_vals=p0["z_fine"], noise=noise(S1), white_bkgd=white_bkgd,
                      want=["rgb_map", "disp_map", "acc_map"] + (["raw"] if retraw else []))
-    ret = {'rgb_map': p1["rgb_map"], 'disp_map': p1["disp_map"], 'acc_map': p1["acc_map"]}
+    return result_dict(p1, retraw, p0, z_std=p0["z_std"])
+
+
+def result_dict(p, retraw, p0=None, **more):
+    """What render_rays returns (nerf/run.py:402-413), in the reference's key order: the three maps of the final pass `p`
+    (a dict of rgb_map disp_map acc_map [raw]), `more` (the D-NeRF runners' z_vals / position_delta), raw when asked, then
+    the coarse pass's maps as rgb0 / disp0 / acc0; entries of `more` that are None are left out."""
+    ret = {'rgb_map': p["rgb_map"], 'disp_map': p["disp_map"], 'acc_map': p["acc_map"]}
+    z_std = more.pop("z_std", None)
+    pd0 = more.pop("position_delta_0", None)
+    ret.update({k: v for k, v in more.items() if v is not None})
     if retraw:
-        ret['raw'] = p1["raw"]
-    ret['rgb0'], ret['disp0'], ret['acc0'] = p0["rgb_map"], p0["disp_map"], p0["acc_map"]
-    ret['z_std'] = p0["z_std"]
+        ret['raw'] = p["raw"]
+    if p0 is not None:
+        ret['rgb0'], ret['disp0'], ret['acc0'] = p0["rgb_map"], p0["disp_map"], p0["acc_map"]
+    if pd0 is not None:
+        ret['position_delta_0'] = pd0
+    if z_std is not None:
+        ret['z_std'] = z_std
     return ret
 
 
@@ -480,12 +482,7 @@ def sample_coarse(ray_batch, N_samples, lindisp=False, t_rand=None, want_pts=Fal
 def _coarse_z(near, far, N_rays, N_samples, lindisp, perturb, pytest, ray_batch=None):
     """nerf/run.py:361-383 (unfused path only): the HIP op when the ray batch is at hand, else torch ops."""
     dev = near.device
-    t_rand = None
-    if perturb > 0.:
-        t_rand = torch.rand((N_rays, N_samples), device=dev)
-        if pytest:
-            np.random.seed(0)
-            t_rand = torch.Tensor(np.random.rand(N_rays, N_samples)).to(dev)
+    t_rand = _draw_t_rand(N_rays, N_samples, perturb, pytest, dev)
     if ray_batch is not None and ray_batch.is_cuda:
         return sample_coarse(ray_batch.detach(), N_samples, lindisp, t_rand)
     t_vals = torch.linspace(0., 1., steps=N_samples, device=dev)
@@ -523,17 +520,15 @@ def _render_rays_unfused(ray_batch, network_fn, network_query_fn, N_samples, ret
         run_fn = network_fn if network_fine is None else network_fine
         raw = network_query_fn(pts, viewdirs, run_fn)
         rgb_map, disp_map, acc_map, weights, depth_map = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd, pytest=pytest)
-    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map}
-    if retraw:
-        ret['raw'] = raw
-    if N_importance > 0:
-        ret['rgb0'], ret['disp0'], ret['acc0'] = rgb_map_0, disp_map_0, acc_map_0
-        ret['z_std'] = torch.std(z_samples, dim=-1, unbiased=False)
-    return ret
+    final = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map, 'raw': raw}
+    if N_importance <= 0:
+        return result_dict(final, retraw)
+    return result_dict(final, retraw, {'rgb_map': rgb_map_0, 'disp_map': disp_map_0, 'acc_map': acc_map_0},
+                       z_std=torch.std(z_samples, dim=-1, unbiased=False))
 
 
-def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
-    """nerf/run.py:90-102.  (The fused pass needs no chunking for memory - activations never
+def batchify_rays_with(render_rays, rays_flat, chunk, **kwargs):
+    """nerf/run.py:90-102 over the given render_rays.  (The fused pass needs no chunking for memory - activations never
     reach HBM - but `chunk` is honoured so results are laid out the same way.)"""
     all_ret = {}
     for i in range(0, rays_flat.shape[0], chunk):
@@ -541,6 +536,19 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
         for k in ret:
             all_ret.setdefault(k, []).append(ret[k])
     return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in all_ret.items()}
+
+
+def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
+    """nerf/run.py:90-102 (this module's render_rays, looked up per call)."""
+    return batchify_rays_with(render_rays, rays_flat, chunk, **kwargs)
+
+
+def image_outputs(all_ret, sh):
+    """The tail of render() (nerf/run.py:160-169): every entry back in the image shape `sh[:-1]`, then
+    [rgb_map, disp_map, acc_map, {the rest}]."""
+    all_ret = {k: torch.reshape(v, list(sh[:-1]) + list(v.shape[1:])) for k, v in all_ret.items()}
+    k_extract = ['rgb_map', 'disp_map', 'acc_map']
+    return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
 
 
 def pack_ray_batch(rays_o, rays_d, near, far, frame_time=None, ndc=False, H=0, W=0, focal=1.):
@@ -581,11 +589,7 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
         rb = pack_ray_batch(rays_o, rays_d, near, far, ndc=ndc, H=H, W=W, focal=K[0][0])
     if not use_viewdirs:
         rb = rb[:, :8].contiguous()          # rays = cat[o, d, near, far] without view directions (nerf/run.py:152-157)
-    all_ret = batchify_rays(rb, chunk, **kwargs)
-    for k in all_ret:
-        all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
-    k_extract = ['rgb_map', 'disp_map', 'acc_map']
-    return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
+    return image_outputs(batchify_rays(rb, chunk, **kwargs), sh)
 
 
 def pipelined_frames(frames, consume):

@@ -11,8 +11,10 @@ from . import _lib
 from .embedder import to8b
 from .png import write_png
 from .ray import get_rays, sample_pdf, raw2outputs
-from .render import fused_plan, render_pass, pack_ray_batch, _rng_inputs, _coarse_z, coarse_pass_resampled, pipelined_frames
-from .model import DirectTemporalNeRF
+from .render import (fused_plan, render_pass, render_pass_train, pack_ray_batch, _rng_inputs, _coarse_z, coarse_pass_resampled,
+                     pipelined_frames, sample_coarse, wants_grad, result_dict, batchify_rays_with, image_outputs, pass_args,
+                     chunked_backward, f32_grads, ray_ptrs, TRAIN_FUSED_MAX_SAMPLES)
+from .model import DirectTemporalNeRF, NeRFOriginal
 
 DEBUG = False
 DNERF_CHUNK_DIV = int(os.environ.get("SWNERF_DNERF_CHUNK_DIV", "2"))   # the D-NeRF backward holds two gradient buffers per chunk
@@ -73,6 +75,12 @@ def _single_time(ray_batch):
     return lo
 
 
+def runs_deform(net, t0):
+    """Whether `net` evaluates its deformation net at time t0: a DirectTemporalNeRF, except at t == 0 with zero_canonical
+    (model.py:143-145), where it is its canonical net alone."""
+    return isinstance(net, DirectTemporalNeRF) and not (t0 == 0. and net.zero_canonical)
+
+
 class _FusedPassTrainDnerf(torch.autograd.Function):
     """The fused D-NeRF pass under autograd (DirectTemporalNeRF at t != 0, model.py:128-151; the loss of
     d_nerf/run_dnerf.py:690-725 puts gradients on the image and on position_delta).  forward =
@@ -86,79 +94,58 @@ class _FusedPassTrainDnerf(torch.autograd.Function):
     def forward(ctx, net, rb, z_vals, S, lindisp, t_rand, noise, white_bkgd, *params):
         kind, packed, Lp, Ld, Lt = net.packed()
         L = _lib.lib()
-        N, cols = rb.shape
-        dev = rb.device
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        N = rb.shape[0]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
         rows = L.swnerf_train_rows(N, S)
         nact, nxs, nbits = L.swnerf_act_floats_per_row(), L.swnerf_xs_floats_per_row(), L.swnerf_mask_floats(rows)
         act, bits, xs = new(rows, nact), new(nbits), new(rows, nxs)
         act_d, bits_d, xs_d = new(rows, nact), new(nbits), new(rows, nxs)
-        raw, rgb, disp, acc, dx = new(N, S, 4), new(N, 3), new(N), new(N), new(N, S, 3)
-        a = _lib.PassArgs()
-        a.ray_batch, a.n_rays, a.cols, a.kind, a.packed = rb.data_ptr(), N, cols, kind, packed.data_ptr()
-        a.run_deform, a.L_pos, a.L_dir, a.L_time, a.n_samples = 1, Lp, Ld, Lt, S
-        a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
-        a.rgb_map, a.disp_map, a.acc_map, a.raw, a.dx = rgb.data_ptr(), disp.data_ptr(), acc.data_ptr(), raw.data_ptr(), dx.data_ptr()
-        if z_vals is not None:
-            z = z_vals
-            a.z_vals = z.data_ptr()
-        else:
-            z = new(N, S)
-            a.z_out = z.data_ptr()
-        for name, t in (("t_rand", t_rand), ("noise", noise)):
-            if t is not None:
-                setattr(a, name, t.data_ptr())
+        a, o, _keep = pass_args(rb, kind, packed, (Lp, Ld, Lt), S, 4, 1, dict(z_vals=z_vals, t_rand=t_rand, noise=noise),
+                                ["rgb_map", "disp_map", "acc_map", "raw", "dx"] + ([] if z_vals is not None else ["z_out"]),
+                                lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_train_dnerf")
+        z = z_vals if z_vals is not None else o["z_out"]
         _lib.check(L.swnerf_render_pass_train_dnerf(a, _lib.ptr(act), _lib.ptr(bits), _lib.ptr(xs), _lib.ptr(act_d), _lib.ptr(bits_d),
                                                     _lib.ptr(xs_d), _lib.stream_of(rb)), "render_pass_train_dnerf")
         ctx.net, ctx.S, ctx.white, ctx.bands = net, S, bool(white_bkgd), (Lp, Ld, Lt)
         ctx.has_noise = noise is not None
-        ctx.save_for_backward(rb, z, raw, dx, act, bits, xs, act_d, bits_d, xs_d, noise if noise is not None else new(0), *params)
+        ctx.save_for_backward(rb, z, o["raw"], o["dx"], act, bits, xs, act_d, bits_d, xs_d, noise if noise is not None else new(0), *params)
         ctx.mark_non_differentiable(z)
         ctx.set_materialize_grads(False)       # an output the loss does not use arrives as None (no zero fill, no read of zeros in the kernel)
-        return rgb, disp, acc, dx, z, raw
+        return o["rgb_map"], o["disp_map"], o["acc_map"], o["dx"], z, o["raw"]
 
     @staticmethod
-    def backward(ctx, g_rgb, g_disp, g_acc, g_dx_up, _gz, g_raw):
-        from .wgrad import WeightGrads, _Fan, _chunk_gemms
-        from . import render as _r
+    def backward(ctx, *grads_out):
+        from .wgrad import WeightGrads
         rb, z, raw, dx, act, bits, xs, act_d, bits_d, xs_d, noise, *params = ctx.saved_tensors
         net, S = ctx.net, ctx.S
         Lp, Ld, Lt = ctx.bands
         L = _lib.lib()
         N, cols = rb.shape
         st = _lib.stream_of(rb)
-        c = lambda g: None if g is None else g.contiguous().float()
-        g_rgb, g_disp, g_acc, g_dx_up, g_raw = c(g_rgb), c(g_disp), c(g_acc), c(g_dx_up), c(g_raw)
+        g_rgb, g_disp, g_acc, g_dx_up, _gz, g_raw = f32_grads(*grads_out)
         Cpos, Cdir = net.input_ch, net.input_ch_views
         wc = WeightGrads(L, "canon", params[:24], fused=True, Cpos=Cpos, Cdir=Cdir, bands=(Lp, Ld, Lt))       # the 24 `_occ` tensors
         wd = WeightGrads(L, "deform", params[24:], fused=True, Cpos=Cpos, bands=(Lp, Ld, Lt))                 # the 18 `_time` / `_time_out`
-        rows_per_ray = act.shape[0] // N
+        packed_bwd = net.packed_bwd(_lib.BWD_DNERF_FUSED)
+
+        def launch(r0, r1, bufs):
+            grad, grad_d, d_raw, g_dx = bufs
+            _lib.check(L.swnerf_render_pass_backward_dnerf(
+                _lib.ptr(packed_bwd), *ray_ptrs(r0, r1, bits, bits_d, per_ray=bits.numel() // N), *ray_ptrs(r0, r1, raw, z, rb), cols,
+                *ray_ptrs(r0, r1, noise if ctx.has_noise else None, dx, g_dx_up), r1 - r0, S, int(ctx.white), Lp,
+                *ray_ptrs(r0, r1, g_rgb, g_disp, g_acc, g_raw), _lib.ptr(grad), _lib.ptr(grad_d), _lib.ptr(d_raw), _lib.ptr(g_dx), st),
+                "render_pass_backward_dnerf")
+
+        def jobs(a0, a1, m, bufs):
+            grad, grad_d, d_raw, g_dx = bufs
+            return [lambda st_, part: wc.chunk(st_, m, grad[:m], act[a0:a1], xs[a0:a1], d_raw[:m], part=part),
+                    lambda st_, part: wd.chunk(st_, m, grad_d[:m], act_d[a0:a1], xs_d[a0:a1], g_dx[:m], part=part)]
+
         # two gradient buffers (canonical + deformation net) per chunk: half of TRAIN_BWD_CHUNK_ROWS rows each, so that a chunk
-        # holds the 3.8 GB the static backward's chunk does; the GEMMs of a chunk fan out over side streams (model._Fan), which
+        # holds the 3.8 GB the static backward's chunk does; the GEMMs of a chunk fan out over side streams (wgrad._Fan), which
         # hides most of what an extra chunk used to cost (one atomic epilogue per GEMM).  Round 2 held the whole fine pass in
         # one chunk: 15 GB of gradients, 29.6 GiB peak for a 4096-ray step.
-        chunk = max(4, (_r.TRAIN_BWD_CHUNK_ROWS // DNERF_CHUNK_DIV // rows_per_ray) // 4 * 4)
-        packed_bwd = net.packed_bwd(_lib.BWD_DNERF_FUSED)
-        mask_per_ray = bits.numel() // N
-        sl = lambda t, r0, r1: None if t is None else t[r0:r1]
-        nrow = min(N, chunk) * rows_per_ray
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
-        grad, grad_d, d_raw, g_dx = new(nrow, act.shape[1]), new(nrow, act.shape[1]), new(nrow, 4), new(nrow, 4)
-        fan = _Fan(rb.device)
-        for r0 in range(0, N, chunk):
-            r1 = min(N, r0 + chunk)
-            n, m = r1 - r0, (r1 - r0) * rows_per_ray
-            b0, b1 = r0 * mask_per_ray, r1 * mask_per_ray
-            _lib.check(L.swnerf_render_pass_backward_dnerf(
-                _lib.ptr(packed_bwd), _lib.ptr(bits[b0:b1]), _lib.ptr(bits_d[b0:b1]), _lib.ptr(raw[r0:r1]), _lib.ptr(z[r0:r1]),
-                _lib.ptr(rb[r0:r1]), cols, _lib.ptr(noise[r0:r1]) if ctx.has_noise else None, _lib.ptr(dx[r0:r1]),
-                _lib.ptr(sl(g_dx_up, r0, r1)), n, S, int(ctx.white), Lp, _lib.ptr(sl(g_rgb, r0, r1)), _lib.ptr(sl(g_disp, r0, r1)),
-                _lib.ptr(sl(g_acc, r0, r1)), _lib.ptr(sl(g_raw, r0, r1)), _lib.ptr(grad), _lib.ptr(grad_d), _lib.ptr(d_raw), _lib.ptr(g_dx), st),
-                "render_pass_backward_dnerf")
-            a0, a1 = r0 * rows_per_ray, r1 * rows_per_ray
-            _chunk_gemms(L, fan, m, [
-                lambda st_, part: wc.chunk(st_, m, grad[:m], act[a0:a1], xs[a0:a1], d_raw[:m], part=part),
-                lambda st_, part: wd.chunk(st_, m, grad_d[:m], act_d[a0:a1], xs_d[a0:a1], g_dx[:m], part=part)])
+        chunked_backward(rb, act.shape[0], DNERF_CHUNK_DIV, (act.shape[1], act.shape[1], 4, 4), launch, jobs)
         g = wc.finish(st) + wd.finish(st)
         return (None,) * 8 + tuple(gi.to(p.dtype) for gi, p in zip(g, params))
 
@@ -185,8 +172,6 @@ def _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples,
     shipped one-model configuration (run_dnerf.py:417-421), and with use_two_models_for_fine the coarse net's OWN
     training pass (for rgb0 / position_delta_0, run_dnerf.py:410-416) runs next to it on the same depths - one extra
     64-sample inference pass instead of a training kernel that would have to hold the resampling scratch as well."""
-    from .render import render_pass_train, TRAIN_FUSED_MAX_SAMPLES, wants_grad
-    from .model import NeRFOriginal
     run_fn = network_fn if network_fine is None else network_fine
     N = ray_batch.shape[0]
     nets = [network_fn, run_fn]
@@ -197,19 +182,18 @@ def _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples,
     if S1 > TRAIN_FUSED_MAX_SAMPLES or N_samples > TRAIN_FUSED_MAX_SAMPLES:
         return None
     t0 = _single_time(ray_batch)
-    deform = lambda net: isinstance(net, DirectTemporalNeRF) and not (t0 == 0. and net.zero_canonical)
     t_rand, u, noise = _rng_inputs(N, N_samples, N_importance, perturb, raw_noise_std, pytest, ray_batch.device)
 
     def train_pass(net, S, z_in, tr, nz):
         """-> (dict with rgb_map disp_map acc_map raw, depths, position_delta) of one differentiable pass of `net`"""
-        if deform(net):
+        if runs_deform(net, t0):
             p = _render_pass_train_dnerf(ray_batch, net, S, z_vals=z_in, lindisp=lindisp, t_rand=tr, noise=nz, white_bkgd=white_bkgd)
             return p, p["z"], p["dx"]
         canon = net._occ if isinstance(net, DirectTemporalNeRF) else net
         p = render_pass_train(ray_batch, canon, S, z_vals=z_in, lindisp=lindisp, t_rand=tr, noise=nz, white_bkgd=white_bkgd)
         if z_in is None:
             with torch.no_grad():
-                z_in = sample_coarse_z(ray_batch, S, lindisp, tr)
+                z_in = sample_coarse(ray_batch.detach(), S, lindisp, tr)
         return p, z_in, torch.zeros((N, S, 3), dtype=torch.float32, device=ray_batch.device)
 
     z_std = p0t = pd0 = None
@@ -217,7 +201,7 @@ def _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples,
         nz0 = noise(N_samples)                                   # ONE draw for the coarse evaluation, whichever kernels run it
         with torch.no_grad():                                    # the resampling: inference kernel on the coarse net
             p0 = render_pass(ray_batch.detach(), network_fn, N_samples, lindisp=lindisp, t_rand=t_rand, noise=nz0,
-                             white_bkgd=white_bkgd, want=[], n_importance=N_importance, u=u, run_deform=deform(network_fn))
+                             white_bkgd=white_bkgd, want=[], n_importance=N_importance, u=u, run_deform=runs_deform(network_fn, t0))
         if use_two_models_for_fine:                              # ... and the coarse net's own differentiable outputs
             p0t, _, pd0 = train_pass(network_fn, N_samples, None, t_rand, nz0)
         z_in, z_std, t_rand = p0["z_fine"], p0["z_std"], None
@@ -226,20 +210,7 @@ def _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples,
         if z_in is not None:
             t_rand = None
     p1, z_final, pd = train_pass(run_fn, S1, z_in, t_rand, noise(S1))
-    ret = {'rgb_map': p1["rgb_map"], 'disp_map': p1["disp_map"], 'acc_map': p1["acc_map"], 'z_vals': z_final, 'position_delta': pd}
-    if retraw:
-        ret['raw'] = p1["raw"]
-    if N_importance > 0:
-        if p0t is not None:
-            ret['rgb0'], ret['disp0'], ret['acc0'], ret['position_delta_0'] = p0t["rgb_map"], p0t["disp_map"], p0t["acc_map"], pd0
-        if z_std is not None:
-            ret['z_std'] = z_std
-    return ret
-
-
-def sample_coarse_z(ray_batch, S, lindisp, t_rand):
-    from .render import sample_coarse
-    return sample_coarse(ray_batch.detach(), S, lindisp, t_rand)
+    return result_dict(p1, retraw, p0t, z_vals=z_final, position_delta=pd, position_delta_0=pd0, z_std=z_std)
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
@@ -248,8 +219,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     """d_nerf/run_dnerf.py:354-480."""
     plan = None
     if ray_batch.shape[-1] == 12:
-        plan = fused_plan(network_query_fn, [network_fn, network_fine], need_time=True)
-        if plan is None and fused_plan(network_query_fn, [network_fn, network_fine], need_time=True, allow_train=True) is not None:
+        plan = fused_plan(network_query_fn, [network_fn, network_fine], need_time=True, allow_train=True)
+        if plan is not None and wants_grad([network_fn, network_fine]):        # under autograd: the training passes, or the op path
+            plan = None
             ret = _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples, retraw, lindisp, perturb, N_importance,
                                            network_fine, white_bkgd, raw_noise_std, pytest, z_vals, use_two_models_for_fine)
             if ret is not None:
@@ -260,7 +232,6 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                     use_two_models_for_fine)
     N = ray_batch.shape[0]
     t0 = _single_time(ray_batch)
-    deform = lambda net: isinstance(net, DirectTemporalNeRF) and not (t0 == 0. and net.zero_canonical)
     t_rand, u, noise = _rng_inputs(N, N_samples, N_importance, perturb, raw_noise_std, pytest, ray_batch.device)
     run_fn = network_fn if network_fine is None else network_fine
     full = ["rgb_map", "disp_map", "acc_map", "dx"]
@@ -271,12 +242,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             # (the reference evaluates the net twice here with identical results, run_dnerf.py:434-436,455-458)
             p1 = render_pass(ray_batch, run_fn, N_samples, lindisp=lindisp, t_rand=t_rand, noise=noise(N_samples),
                              white_bkgd=white_bkgd, want=full + ["z_out"] + (["raw"] if retraw else []),
-                             run_deform=deform(run_fn))
+                             run_deform=runs_deform(run_fn, t0))
             z_final = p1["z_out"]
         else:
             want0 = ["rgb_map", "disp_map", "acc_map", "dx"] if use_two_models_for_fine else []
             p0 = coarse_pass_resampled(ray_batch, network_fn, N_samples, N_importance, want=want0, u=u, lindisp=lindisp,
-                                       t_rand=t_rand, noise=noise(N_samples), white_bkgd=white_bkgd, run_deform=deform(network_fn))
+                                       t_rand=t_rand, noise=noise(N_samples), white_bkgd=white_bkgd, run_deform=runs_deform(network_fn, t0))
             z_final, z_std = p0["z_fine"], p0["z_std"]
             p1 = None
     else:
@@ -285,18 +256,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if p1 is None:
         S1 = z_final.shape[-1]
         p1 = render_pass(ray_batch, run_fn, S1, z_vals=z_final, noise=noise(S1), white_bkgd=white_bkgd,
-                         want=full + (["raw"] if retraw else []), run_deform=deform(run_fn))
-    ret = {'rgb_map': p1["rgb_map"], 'disp_map': p1["disp_map"], 'acc_map': p1["acc_map"], 'z_vals': z_final,
-           'position_delta': p1["dx"]}
-    if retraw:
-        ret['raw'] = p1["raw"]
-    if N_importance > 0:
-        if p0 is not None and use_two_models_for_fine:
-            ret['rgb0'], ret['disp0'], ret['acc0'] = p0["rgb_map"], p0["disp_map"], p0["acc_map"]
-            ret['position_delta_0'] = p0["dx"]
-        if z_std is not None:
-            ret['z_std'] = z_std
-    return ret
+                         want=full + (["raw"] if retraw else []), run_deform=runs_deform(run_fn, t0))
+    p0_own = p0 if (p0 is not None and use_two_models_for_fine) else None          # the coarse net's own outputs (run_dnerf.py:410-416)
+    return result_dict(p1, retraw, p0_own, z_vals=z_final, position_delta=p1["dx"],
+                       position_delta_0=None if p0_own is None else p0_own["dx"], z_std=z_std)
 
 
 def _render_rays_unfused(ray_batch, network_fn, network_query_fn, N_samples, retraw, lindisp, perturb, N_importance,
@@ -316,11 +279,10 @@ def _render_rays_unfused(ray_batch, network_fn, network_query_fn, N_samples, ret
         with torch.no_grad():
             if fused_plan(network_query_fn, [network_fn], need_time=True) is not None:
                 t0 = _single_time(ray_batch)
-                deform = isinstance(network_fn, DirectTemporalNeRF) and not (t0 == 0. and network_fn.zero_canonical)
                 t_rand, u, noise = _rng_inputs(N_rays, N_samples, N_importance, perturb, raw_noise_std, pytest, ray_batch.device)
                 fused_coarse = coarse_pass_resampled(ray_batch.detach(), network_fn, N_samples, N_importance, want=[], u=u,
                                                      lindisp=lindisp, t_rand=t_rand, noise=noise(N_samples), white_bkgd=white_bkgd,
-                                                     run_deform=deform)
+                                                     run_deform=runs_deform(network_fn, t0))
     z_std = None
     if fused_coarse is not None:
         z_vals, z_std = fused_coarse["z_fine"], fused_coarse["z_std"]
@@ -342,28 +304,16 @@ def _render_rays_unfused(ray_batch, network_fn, network_query_fn, N_samples, ret
     run_fn = network_fn if network_fine is None else network_fine
     raw, position_delta = network_query_fn(pts, viewdirs, frame_time, run_fn)
     rgb_map, disp_map, acc_map, weights, _ = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd, pytest=pytest)
-    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map, 'z_vals': z_vals, 'position_delta': position_delta}
-    if retraw:
-        ret['raw'] = raw
-    if N_importance > 0:
-        for k, v in (('rgb0', rgb_map_0), ('disp0', disp_map_0), ('acc0', acc_map_0), ('position_delta_0', position_delta_0)):
-            if v is not None:
-                ret[k] = v
-        if z_samples is not None:
-            ret['z_std'] = torch.std(z_samples, dim=-1, unbiased=False)
-        elif z_std is not None:
-            ret['z_std'] = z_std
-    return ret
+    if z_samples is not None:
+        z_std = torch.std(z_samples, dim=-1, unbiased=False)
+    p0 = None if rgb_map_0 is None else {'rgb_map': rgb_map_0, 'disp_map': disp_map_0, 'acc_map': acc_map_0}
+    return result_dict({'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map, 'raw': raw}, retraw, p0, z_vals=z_vals,
+                       position_delta=position_delta, position_delta_0=position_delta_0, z_std=z_std)
 
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
-    """d_nerf/run_dnerf.py:86-101."""
-    all_ret = {}
-    for i in range(0, rays_flat.shape[0], chunk):
-        ret = render_rays(rays_flat[i:i + chunk], **kwargs)
-        for k in ret:
-            all_ret.setdefault(k, []).append(ret[k])
-    return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in all_ret.items()}
+    """d_nerf/run_dnerf.py:86-101 (this module's render_rays, looked up per call)."""
+    return batchify_rays_with(render_rays, rays_flat, chunk, **kwargs)
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., frame_time=None,
@@ -390,10 +340,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         all_ret = batchify_rays(rb, chunk, **kwargs)
     finally:
         _TIME_HINT.reset(token)
-    for k in all_ret:
-        all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
-    k_extract = ['rgb_map', 'disp_map', 'acc_map']
-    return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
+    return image_outputs(all_ret, sh)
 
 
 def render_path(render_poses, render_times, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0,

@@ -18,7 +18,7 @@ from . import _lib
 from .embedder import to8b, EmbedFn
 from .png import write_png
 from .ray import get_rays, ndc_rays, raw2outputs
-from .render import closure_embedders, wants_grad, sample_coarse
+from .render import closure_embedders, wants_grad, sample_coarse, pass_args, result_dict, batchify_rays_with, image_outputs
 from .model import TNeRF
 
 DEBUG = False
@@ -93,26 +93,8 @@ def render_pass_tnerf(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, 
     Returns a dict of the requested outputs among rgb_map disp_map acc_map depth_map weights raw z_out."""
     kind, packed, Lp, Ld, Lt = net.packed()
     rb = _lib.dev_f32(ray_batch, "ray_batch")
-    N, cols = rb.shape
-    S = int(n_samples)
-    dev = rb.device
-    shapes = {"rgb_map": (N, 3), "disp_map": (N,), "acc_map": (N,), "depth_map": (N,), "weights": (N, S), "raw": (N, S, 4),
-              "z_out": (N, S)}
-    out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
-    a = _lib.PassArgs()
-    a.ray_batch, a.n_rays, a.cols, a.kind, a.packed = rb.data_ptr(), N, cols, kind, packed.data_ptr()
-    a.L_pos, a.L_dir, a.L_time, a.n_samples = Lp, Ld, Lt, S
-    keep = [rb, packed]
-    for name, t in (("z_vals", z_vals), ("t_rand", t_rand), ("noise", noise)):
-        if t is not None:
-            t = _lib.dev_f32(t, name, S)
-            if t.shape[0] != N:
-                raise ValueError(f"swnerf.render_pass_tnerf: {name} must have {N} rows, got {tuple(t.shape)}")
-            keep.append(t)
-            setattr(a, name, t.data_ptr())
-    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
-    for k, t in out.items():
-        setattr(a, k, t.data_ptr())
+    a, out, _keep = pass_args(rb, kind, packed, (Lp, Ld, Lt), int(n_samples), 4, 0, dict(z_vals=z_vals, t_rand=t_rand, noise=noise), want,
+                              lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_tnerf")
     _lib.check(_lib.lib().swnerf_render_pass(a, _lib.stream_of(rb)), "render_pass")
     return out
 
@@ -152,11 +134,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         want = ["rgb_map", "disp_map", "acc_map"] + (["raw"] if retraw else []) + (["z_out"] if z_vals is None else [])
         o = render_pass_tnerf(ray_batch, network_fn, S, z_vals=z_vals, lindisp=lindisp, t_rand=t_rand, noise=noise,
                               white_bkgd=white_bkgd, want=want)
-        ret = {'rgb_map': o["rgb_map"], 'disp_map': o["disp_map"], 'acc_map': o["acc_map"],
-               'z_vals': o["z_out"] if z_vals is None else z_vals}
-        if retraw:
-            ret['raw'] = o["raw"]
-        return ret
+        return result_dict(o, retraw, z_vals=o["z_out"] if z_vals is None else z_vals)
     # the op path (differentiable)
     rays_o, rays_d = ray_batch[:, 0:3], ray_batch[:, 3:6]
     viewdirs = ray_batch[:, -3:] if ray_batch.shape[-1] > 9 else None
@@ -167,20 +145,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     raw = network_query_fn(pts, viewdirs, frame_time, network_fn)
     rgb_map, disp_map, acc_map, weights, depth_map = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd, pytest=pytest,
                                                                  noise=noise)
-    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map, 'z_vals': z_vals}
-    if retraw:
-        ret['raw'] = raw
-    return ret
+    return result_dict({'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map, 'raw': raw}, retraw, z_vals=z_vals)
 
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
-    """run_tnerf.py:90-103."""
-    all_ret = {}
-    for i in range(0, rays_flat.shape[0], chunk):
-        ret = render_rays(rays_flat[i:i + chunk], **kwargs)
-        for k in ret:
-            all_ret.setdefault(k, []).append(ret[k])
-    return {k: torch.cat(all_ret[k], 0) for k in all_ret}
+    """run_tnerf.py:90-103 (this module's render_rays, looked up per call)."""
+    return batchify_rays_with(render_rays, rays_flat, chunk, **kwargs)
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., frame_time=None,
@@ -207,11 +177,7 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
     rays = torch.cat([rays_o, rays_d, near, far, frame_time], -1)
     if use_viewdirs:
         rays = torch.cat([rays, viewdirs], -1)
-    all_ret = batchify_rays(rays, chunk, **kwargs)
-    for k in all_ret:
-        all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
-    k_extract = ['rgb_map', 'disp_map', 'acc_map']
-    return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
+    return image_outputs(batchify_rays(rays, chunk, **kwargs), sh)
 
 
 def render_path(render_poses, render_times, hwf, chunk, render_kwargs, gt_imgs=None, savedir=None, render_factor=0,

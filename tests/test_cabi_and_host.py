@@ -98,6 +98,139 @@ def test_packed_sizes_and_argument_errors_without_gpu(built):
     assert L.swnerf_relu_mask(None, None, 5, None) == -1 and L.swnerf_relu_mask(None, None, 0, None) == 0
 
 
+E_ARG, E_UNSUPP = -1, -2
+_PASS = dict(packed=8, ray_batch=8, n_rays=4, cols=11, kind=0, n_samples=64, L_pos=10, L_dir=4)      # (pointers never dereferenced)
+_TN = dict(_PASS, kind=3, cols=12, L_time=10)
+_TRAIN = dict(_PASS, raw=8, z_out=8)
+_TRAIN_DN = dict(_TRAIN, kind=1, cols=12, run_deform=1, dx=8, L_time=10)
+_RESAMPLING = [(dict(n_importance=8), E_ARG, b"n_importance>0 needs z_fine"),
+               (dict(n_importance=8, z_fine=8, n_samples=2), E_UNSUPP, b"resampling supports 3<=N_samples<=256 and N_samples+N_importance<=1024"),
+               (dict(n_importance=1000, z_fine=8), E_UNSUPP, b"resampling supports 3<=N_samples<=256")]
+_BANDS3 = [(dict(L_pos=11), E_UNSUPP, b"exceed (10,4,10)"), (dict(L_dir=5), E_UNSUPP, b"exceed (10,4,10)"),
+           (dict(L_time=11), E_UNSUPP, b"exceed (10,4,10)"), (dict(L_pos=-1), E_UNSUPP, b"embedder bands (-1,")]
+_T_RAND = [(dict(z_vals=8, t_rand=8), E_ARG, b"t_rand only applies to coarse sampling")]
+# entry point -> (valid arguments, [(what one call changes, return code, substring of swnerf_last_error())])
+_PASS_REJECTIONS = {
+    "render_pass": (_PASS, [
+        (None, E_ARG, b"NULL args"), (dict(packed=0), E_ARG, b"NULL ray_batch/packed"), (dict(ray_batch=0), E_ARG, b"NULL ray_batch/packed"),
+        (dict(n_samples=1), E_ARG, b"n_rays 4, n_samples 1"), (dict(n_rays=-1), E_ARG, b"n_rays -1, n_samples 64"),
+        (dict(cols=9), E_ARG, b"must have 11 or 12 columns (use_viewdirs) or 8 (SWNERF_NET_NOVIEW), got 9 for kind 0"),
+        (dict(kind=2), E_ARG, b"got 11 for kind 2"), (dict(cols=8), E_ARG, b"got 8 for kind 0"),
+        (dict(kind=1), E_ARG, b"D-NeRF needs the frame_time column"),
+        (dict(kind=2, cols=8, out_ch=4, dx=8), E_ARG, b"a static net has no position_delta output here"),
+        (dict(kind=2, cols=8, out_ch=7), E_UNSUPP, b"out_ch 7"), (dict(kind=7), E_ARG, b"unknown net kind 7"),
+        (dict(n_samples=300, n_importance=8, z_fine=8), E_UNSUPP, b"resampling supports")] + _BANDS3 + _T_RAND + _RESAMPLING),
+    "render_pass (T-NeRF)": (_TN, [
+        (dict(packed=0), E_ARG, b"NULL ray_batch/packed"), (dict(n_samples=1), E_ARG, b"n_samples 1"),
+        (dict(n_importance=8), E_ARG, b"T-NeRF has no hierarchical resampling"), (dict(cols=11), E_ARG, b"T-NeRF needs the 12-column ray batch"),
+        (dict(L_dir=0), E_UNSUPP, b"T-NeRF needs view directions"), (dict(dx=8), E_ARG, b"T-NeRF has no position_delta output")]
+        + _BANDS3 + _T_RAND),
+    "render_pass_x3": (_PASS, [
+        (None, E_ARG, b"NULL args"), (dict(terms=2), E_ARG, b"terms must be 3 (bf16x3) or 1 (plain bf16), got 2"),
+        (dict(packed=0), E_ARG, b"NULL ray_batch/packed"), (dict(ray_batch=0), E_ARG, b"NULL ray_batch/packed"),
+        (dict(kind=2, cols=8), E_ARG, b"unknown net kind 2"), (dict(kind=3, cols=12), E_ARG, b"unknown net kind 3"),
+        (dict(n_samples=1), E_ARG, b"n_samples 1"), (dict(n_rays=-1), E_ARG, b"n_rays -1"),
+        (dict(cols=8), E_ARG, b"must have 11 or 12 columns, got 8"), (dict(kind=1), E_ARG, b"D-NeRF needs the frame_time column")]
+        + _BANDS3 + _T_RAND + _RESAMPLING),
+    "render_pass_train": (_TRAIN, [
+        (None, E_ARG, b"NULL args"), (dict(packed=0), E_ARG, b"NULL pointer"), (dict(ray_batch=0), E_ARG, b"NULL pointer"),
+        (dict(xs=None), E_ARG, b"NULL pointer"), (dict(kind=1), E_UNSUPP, b"the static net (SWNERF_NET_CANON, 11- or 12-column ray batch)"),
+        (dict(cols=8), E_UNSUPP, b"the static net"), (dict(kind=2), E_UNSUPP, b"the static net"), (dict(kind=3, cols=12), E_UNSUPP, b"the static net"),
+        (dict(n_samples=1), E_UNSUPP, b"2 <= n_samples <= 256 (got 1)"), (dict(n_samples=257), E_UNSUPP, b"2 <= n_samples <= 256 (got 257)"),
+        (dict(n_rays=-1), E_UNSUPP, b"2 <= n_samples <= 256"),
+        (dict(raw=0), E_ARG, b"the backward needs raw and the depths"), (dict(z_out=0), E_ARG, b"the backward needs raw and the depths"),
+        (dict(L_pos=11), E_UNSUPP, b"embedder bands (11,4) exceed (10,4)"), (dict(L_dir=5), E_UNSUPP, b"exceed (10,4)"),
+        (dict(dx=8), E_ARG, b"no dx output (static net)"), (dict(kind=2, cols=8, out_ch=3), E_UNSUPP, b"out_ch 3")] + _T_RAND + _RESAMPLING),
+    "render_pass_train_dnerf": (_TRAIN_DN, [
+        (None, E_ARG, b"NULL args"), (dict(packed=0), E_ARG, b"NULL pointer"), (dict(ray_batch=0), E_ARG, b"NULL pointer"),
+        (dict(act_d=None), E_ARG, b"NULL pointer"), (dict(kind=0), E_UNSUPP, b"DirectTemporalNeRF with the deformation pass"),
+        (dict(cols=11), E_UNSUPP, b"DirectTemporalNeRF"), (dict(run_deform=0), E_UNSUPP, b"DirectTemporalNeRF"),
+        (dict(n_samples=1), E_UNSUPP, b"2 <= n_samples <= 256 (got 1)"), (dict(n_samples=300), E_UNSUPP, b"2 <= n_samples <= 256 (got 300)"),
+        (dict(n_importance=8, z_fine=8), E_UNSUPP, b"no resampling in the training pass"),
+        (dict(raw=0), E_ARG, b"the backward needs raw, dx and the depths"), (dict(dx=0), E_ARG, b"the backward needs raw, dx and the depths"),
+        (dict(z_out=0), E_ARG, b"the backward needs raw, dx and the depths")] + _BANDS3 + _T_RAND),
+}
+# ... and what the entry points let through without a launch: an empty batch
+_PASS_EMPTY = [("render_pass", dict(n_rays=0, ray_batch=0), 0, None), ("render_pass", dict(n_rays=0, n_importance=8), 0, None),
+               ("render_pass", dict(n_rays=0, cols=9), E_ARG, b"got 9 for kind 0"), ("render_pass (T-NeRF)", dict(n_rays=0, ray_batch=0), 0, None),
+               ("render_pass_x3", dict(n_rays=0, ray_batch=0, n_importance=8), 0, None), ("render_pass_x3", dict(n_rays=0, L_dir=5), E_UNSUPP, b"exceed"),
+               ("render_pass_train", dict(n_rays=0, ray_batch=0, kind=5, n_samples=0, xs=None), 0, None),
+               ("render_pass_train", dict(n_rays=0, packed=0), E_ARG, b"NULL pointer"),
+               ("render_pass_train_dnerf", dict(n_rays=0, ray_batch=0, kind=0, act_d=None), 0, None)]
+
+
+def _call_pass(built, entry, base, change):
+    L = built.lib()
+    extra = dict(terms=3, act=8, bits=8, xs=8, act_d=8, bits_d=8, xs_d=8)
+    a = None
+    if change is not None:
+        a = built.PassArgs()
+        for k, v in {**base, **change}.items():
+            if k in extra:
+                extra[k] = v
+            else:
+                setattr(a, k, v)
+    if entry == "render_pass_x3":
+        return L.swnerf_render_pass_x3(a, extra["terms"], None)
+    if entry == "render_pass_train":
+        return L.swnerf_render_pass_train(a, extra["act"], extra["bits"], extra["xs"], None)
+    if entry == "render_pass_train_dnerf":
+        return L.swnerf_render_pass_train_dnerf(a, *[extra[k] for k in ("act", "bits", "xs", "act_d", "bits_d", "xs_d")], None)
+    return L.swnerf_render_pass(a, None)
+
+
+def test_pass_entry_points_reject_one_violation_each_without_gpu(built):
+    """Every fused-pass entry point, one broken condition per call: the return code and the message (which names the entry
+    point) are part of the C ABI.  All of these are refused before any device call."""
+    L = built.lib()
+    for entry, (base, rows) in _PASS_REJECTIONS.items():
+        prefix = entry.split(" ")[0].encode() + b": "
+        for change, code, text in rows:
+            rc = _call_pass(built, entry, base, change)
+            msg = L.swnerf_last_error()
+            assert rc == code and text in msg, (entry, change, rc, msg)
+            assert msg.startswith(prefix) or b"out_ch" in text or b"unknown net kind 7" in text, (entry, change, msg)
+    for entry, change, code, text in _PASS_EMPTY:
+        rc = _call_pass(built, entry, _PASS_REJECTIONS[entry][0], change)
+        assert rc == code and (text is None or text in L.swnerf_last_error()), (entry, change, rc, L.swnerf_last_error())
+
+
+# positional arguments of the three backward entry points (include/swnerf.h), all valid
+_BWD = {
+    "render_pass_backward": dict(packed_bwd=8, bits=8, raw=8, z_vals=8, ray_batch=8, cols=11, noise=None, n_rays=4, n_samples=64, white_bkgd=0,
+                                 g_rgb=None, g_disp=None, g_acc=None, g_raw=None, grad=8, d_raw=8),
+    "render_pass_backward_noview": dict(packed_bwd=8, bits=8, raw=8, z_vals=8, ray_batch=8, cols=8, noise=None, n_rays=4, n_samples=64, white_bkgd=0,
+                                        out_ch=5, g_rgb=None, g_disp=None, g_acc=None, g_raw=None, grad=8, d_raw=8),
+    "render_pass_backward_dnerf": dict(packed_bwd=8, bits=8, bits_d=8, raw=8, z_vals=8, ray_batch=8, cols=12, noise=None, dx=8, g_pd=None, n_rays=4,
+                                       n_samples=64, white_bkgd=0, L_pos=10, g_rgb=None, g_disp=None, g_acc=None, g_raw=None, grad=8, grad_d=8,
+                                       d_raw=8, g_dx=8),
+}
+_BWD_COMMON = [(dict(packed_bwd=None), E_ARG, b"NULL pointer or negative n_rays"), (dict(bits=None), E_ARG, b"NULL pointer or negative n_rays"),
+               (dict(raw=None), E_ARG, b"NULL pointer"), (dict(z_vals=None), E_ARG, b"NULL pointer"), (dict(ray_batch=None), E_ARG, b"NULL pointer"),
+               (dict(grad=None), E_ARG, b"NULL pointer"), (dict(d_raw=None), E_ARG, b"NULL pointer"), (dict(n_rays=-1), E_ARG, b"negative n_rays"),
+               (dict(n_samples=1), E_UNSUPP, b"2 <= n_samples <= 256 (got 1)"), (dict(n_samples=257), E_UNSUPP, b"2 <= n_samples <= 256 (got 257)")]
+_BWD_REJECTIONS = {
+    "render_pass_backward": _BWD_COMMON + [(dict(cols=7), E_ARG, b"ray_batch needs >= 8 columns")],
+    "render_pass_backward_noview": _BWD_COMMON + [(dict(cols=7), E_ARG, b"cols 7 / out_ch 5"), (dict(out_ch=3), E_ARG, b"cols 8 / out_ch 3"),
+                                                  (dict(out_ch=6), E_ARG, b"cols 8 / out_ch 6")],
+    "render_pass_backward_dnerf": _BWD_COMMON + [(dict(bits_d=None), E_ARG, b"NULL pointer"), (dict(dx=None), E_ARG, b"NULL pointer"),
+                                                 (dict(grad_d=None), E_ARG, b"NULL pointer"), (dict(g_dx=None), E_ARG, b"NULL pointer"),
+                                                 (dict(cols=7), E_ARG, b"cols 7 / L_pos 10"), (dict(L_pos=11), E_ARG, b"cols 12 / L_pos 11"),
+                                                 (dict(L_pos=-1), E_ARG, b"L_pos -1")],
+}
+
+
+def test_pass_backward_entry_points_reject_one_violation_each_without_gpu(built):
+    L = built.lib()
+    for entry, rows in _BWD_REJECTIONS.items():
+        fn = getattr(L, "swnerf_" + entry)
+        for change, code, text in rows:
+            rc = fn(*{**_BWD[entry], **change}.values(), None)
+            msg = L.swnerf_last_error()
+            assert rc == code and text in msg and msg.startswith(entry.encode() + b": "), (entry, change, rc, msg)
+        assert fn(*{**_BWD[entry], "n_rays": 0, "raw": None, "n_samples": 0}.values(), None) == 0       # an empty batch: nothing to do
+
+
 def test_no_cpu_fallback(built):
     from swnerf import ray, model, embedder
     with pytest.raises(RuntimeError, match="GPU"):
