@@ -175,10 +175,11 @@ int swnerf_mlp_backward_dx(const float* packed_bwd, const float* bits, const flo
                            float* grad, void* stream);
 int swnerf_gemm_tn(const float* A, int lda, int No, const float* B, int ldb, int Ni, int64_t M,
                    float* C, int ldc, float* bias, void* stream);
-/* gemm_tn for a 256 x 256 block (No = Ni = 256) with up to two riders that share one of its operands and its pass
- * over the rows (each may be NULL):
- *   B2 [M, Ni2 <= 64]:  C2[256, ldc2] += A^T . B2            (the gamma(x) columns of a skip layer: same A)
- *   A2 [M, No2 <= 32]:  C3[No2, ldc3] += A2^T . B,  bias3[No2] += column sums of A2   (alpha_linear: same B as feature_linear)
+/* gemm_tn for a 256 x 256 block (No = Ni = 256) with up to two riders that share one of its operands (each may be NULL):
+ *   B2 [M, Ni2 <= 64]:  C2[256, ldc2] += A^T . B2            (the gamma(x) columns of a skip layer: same A; rides on the
+ *                       block's own pass over the rows)
+ *   A2 [M, No2 <= 32]:  C3[No2, ldc3] += A2^T . B,  bias3[No2] += column sums of A2   (a convenience: it costs its own launch,
+ *                       the swnerf_gemm_tn call it stands for, on the same stream)
  * Equivalent to the corresponding separate swnerf_gemm_tn calls (which it falls back to for small or unaligned M). */
 int swnerf_gemm_tn_fused(const float* A, int lda, const float* B, int ldb, int64_t M, float* C, int ldc, float* bias,
                          const float* B2, int ldb2, int Ni2, float* C2, int ldc2,
@@ -186,7 +187,8 @@ int swnerf_gemm_tn_fused(const float* A, int lda, const float* B, int ldb, int64
 /* Several swnerf_gemm_tn_fused problems over the SAME M rows (the weight-gradient GEMMs of one row chunk of a training step:
  * loss.backward() of nerf/run.py:700) as ONE launch: the workgroups are dealt out over the items in proportion to their work,
  * so the chunk pays one launch ramp and one atomic epilogue instead of one per layer.  Field meaning as the arguments of
- * swnerf_gemm_tn_fused (riders may be NULL).  Results equal the separate calls' (split-K atomics add in a different order). */
+ * swnerf_gemm_tn_fused (riders may be NULL; an A2 rider is a launch of its own here too).  Every item's arguments are checked before the first
+ * launch.  Results equal the separate calls' (split-K atomics add in a different order). */
 typedef struct swnerf_gemm_item {
     const float* A; int lda; const float* B; int ldb; float* C; int ldc; float* bias;
     const float* B2; int ldb2; int Ni2; float* C2; int ldc2;
@@ -402,7 +404,7 @@ int swnerf_feature_finish(const float* G, const float* db_hv, const float* Wv, i
 int swnerf_canon_narrow_grads(const float* grad, int ldg, const float* act, int lda, const float* xs, const float* d_out, int64_t M,
                               float* c0s, float* cvs, float* G, float* a4w, float* rgb4, float* b_l0, float* b_hv, float* a4b,
                               float* rgb4b, void* stream);
-/* The same for the deformation net (one launch per chunk; table-driven narrow_plan_kernel, csrc/backward_kernels.hip):
+/* The same for the deformation net (one launch per chunk; table-driven narrow_plan_kernel, csrc/wgrad_kernels.hip):
  * `_time.0` = [gamma(x) | gamma(t)], `_time_out` (model.py:128-136): grad_d / act_d [M, ld >= 2432] (d pre_0 at
  *   column 0, h7 at 1792), xs_d [M, 96] (gamma(x) slots 0..63, gamma(t) slots 64..95), g_dx [M, 4] = d dx with a zero 4th column:
  *   c0s [256,64] += d pre_0^T xs_d[:, :64], cts [256,32] += d pre_0^T xs_d[:, 64:], w4 [4,256] += g_dx^T h7; b_l0 [256], b4 [4]

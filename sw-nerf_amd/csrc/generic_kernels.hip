@@ -8,7 +8,7 @@
 //   gemm_nn  : dX[M,K] = dY[M,N] . W[N,K]                   (its input gradient)
 //   relu_mask: dY *= (Y > 0)                                (relu backward, in place)
 //   linear_act / elu_grad: the same GEMM with an ELU epilogue (elu.h) and its backward from the output (TNeRF, model.py:152-210)
-// The weight gradient dW = dY^T . X and db = column sums are swnerf_gemm_tn (backward_kernels.hip).
+// The weight gradient dW = dY^T . X and db = column sums are swnerf_gemm_tn (wgrad_kernels.hip).
 //
 // One workgroup (4 waves) owns a 64 x 64 block of the output, wave w the 32 x 32 tile (w&1, w>>1); the K dimension
 // is walked in chunks of 32 staged through LDS with bounds-checked 4-byte loads (any leading dimension, any K: 63, 90,

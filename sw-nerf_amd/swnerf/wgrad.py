@@ -1,6 +1,6 @@
 """Weight gradients of the 8x256 nets (model.py:39-62, 128-136 reversed): dW / db of every Linear layer
 from the dX chain's `grad` rows, the saved activations `act`, the encodings and d raw - TN MFMA GEMMs over the (ray, sample) rows
-(csrc/backward_kernels.hip), accumulated chunk by chunk.
+(csrc/wgrad_kernels.hip), accumulated chunk by chunk.
 
 ONE table-driven routine (`WeightGrads`) serves the three net kinds (canonical with view directions, without, deformation)
 on both paths - the fused training passes (encodings in operand SLOT order, `xs`) and the op path (embedded rows `x`): round 3
@@ -214,10 +214,12 @@ class WeightGrads:
         mm = lambda A, a_col, No, B, b_col, Ni, C, c_col, bias: _gemm_tn(L, st, M, A, a_col, No, B, b_col, Ni, C, c_col, bias)
         c0 = (s["c0s"], 0) if self.fused else (g[0], 0)
         aligned4 = draw.stride(0) == 4 and draw.data_ptr() % 16 == 0
+        # the fused narrow kernels (csrc/wgrad_kernels.hip) take the fused pass's own buffers: slot-ordered xs rows, a 4-column d raw
+        one_pass = (self.fused and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
+                    and not (grad.data_ptr() | act.data_ptr() | enc.data_ptr()) % 16)
         if self.kind == "canon":
-            if (self.fused and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
-                    and not (grad.data_ptr() | act.data_ptr() | enc.data_ptr()) % 16):
-                # the five narrow products below as ONE pass over the rows (csrc/backward_kernels.hip narrow5_kernel)
+            if one_pass:
+                # the five narrow products below as ONE pass over the rows (narrow5_kernel)
                 _lib.check(L.swnerf_canon_narrow_grads(_lib.ptr(grad), grad.stride(0), _lib.ptr(act), act.stride(0), _lib.ptr(enc), _lib.ptr(draw), M,
                                                        _lib.ptr(s["c0s"]), _lib.ptr(s["cvs"]), _lib.ptr(s["gfeat"]), _lib.ptr(s["a4w"]), _lib.ptr(s["rgb4w"]),
                                                        _lib.ptr(g[1]), _lib.ptr(g[17]), _lib.ptr(s["a4b"]), _lib.ptr(s["rgb4b"]), _st(st)), "canon_narrow_grads")
@@ -240,8 +242,7 @@ class WeightGrads:
             mm(grad, 0, 256, enc, 0, e0, c0[0], c0[1], g[1])                               # pts_linears.0
             mm(draw, 0, 8, act, SW_ACT_H7, 256, s["w8"], 0, s["b8"])                       # output_linear (rows 0..out_ch-1)
         else:
-            if (self.fused and aligned4 and grad.stride(0) == act.stride(0) and enc.stride(0) == 96
-                    and not (grad.data_ptr() | act.data_ptr() | enc.data_ptr()) % 16):
+            if one_pass:                                       # its three narrow products likewise (narrow_plan_kernel)
                 _lib.check(L.swnerf_deform_narrow_grads(_lib.ptr(grad), grad.stride(0), _lib.ptr(act), act.stride(0), _lib.ptr(enc), _lib.ptr(draw), M,
                                                         _lib.ptr(s["c0s"]), _lib.ptr(s["cts"]), _lib.ptr(s["w4"]), _lib.ptr(g[1]), _lib.ptr(s["b4"]), _st(st)),
                            "deform_narrow_grads")

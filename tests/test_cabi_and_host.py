@@ -231,6 +231,66 @@ def test_pass_backward_entry_points_reject_one_violation_each_without_gpu(built)
         assert fn(*{**_BWD[entry], "n_rays": 0, "raw": None, "n_samples": 0}.values(), None) == 0       # an empty batch: nothing to do
 
 
+# one valid fused weight-gradient item (include/swnerf.h swnerf_gemm_item; pointers never dereferenced: rejected first), in field order
+_ITEM = dict(A=16, lda=256, B=16, ldb=256, C=16, ldc=256, bias=None, B2=None, ldb2=0, Ni2=0, C2=None, ldc2=0,
+             A2=None, lda2=0, No2=0, C3=None, ldc3=0, bias3=None)
+_ITEM_REJECTIONS = [(dict(A=None), b"bad main operands"), (dict(B=None), b"bad main operands"), (dict(C=None), b"bad main operands"),
+                    (dict(lda=255), b"bad main operands (lda=255 "),
+                    (dict(B2=16, ldb2=96, Ni2=65, C2=16, ldc2=96), b"Ni2=65 "),              # Ni2 > 64
+                    (dict(B2=16, ldb2=96, Ni2=64, ldc2=64), b"bad B2 rider"),                               # B2 without C2
+                    (dict(A2=16, lda2=64, No2=33, C3=16, ldc3=256), b"No2=33)"),             # No2 > 32
+                    (dict(A2=16, lda2=4, No2=1, ldc3=256), b"bad A2 rider")]                                # A2 without C3
+
+
+def test_gemm_tn_fused_and_group_reject_one_violation_each_without_gpu(built):
+    """swnerf_gemm_tn_fused and swnerf_gemm_tn_group check an item through the same code: one broken condition per call, the same
+    return code from both, each message naming its entry point (and the item).  The group checks EVERY item before its first
+    launch: a bad item at the end of the list is refused exactly like one at its start (at M = 1024 the good items in front of
+    it would otherwise already have been launched one by one; the GPU half of this is tests/test_gpu_backward.py test_gemm_tn_group)."""
+    L = built.lib()
+    M = 1024
+    fused = lambda q: L.swnerf_gemm_tn_fused(q["A"], q["lda"], q["B"], q["ldb"], M, q["C"], q["ldc"], q["bias"], q["B2"], q["ldb2"], q["Ni2"],
+                                             q["C2"], q["ldc2"], q["A2"], q["lda2"], q["No2"], q["C3"], q["ldc3"], q["bias3"], None)
+    group = lambda qs, n=None: L.swnerf_gemm_tn_group((built.GemmItem * len(qs))(*[built.GemmItem(*q.values()) for q in qs]),
+                                                      len(qs) if n is None else n, M, None)
+    assert list(_ITEM) == [f for f, _ in built.GemmItem._fields_]
+    for change, text in _ITEM_REJECTIONS:
+        bad = {**_ITEM, **change}
+        assert fused(bad) == E_ARG and text in L.swnerf_last_error() and L.swnerf_last_error().startswith(b"gemm_tn_fused: "), (change, L.swnerf_last_error())
+        assert group([bad]) == E_ARG and text in L.swnerf_last_error() and L.swnerf_last_error().startswith(b"gemm_tn_group: item 0: "), change
+        assert group([bad, _ITEM, _ITEM]) == E_ARG and b"item 0: " in L.swnerf_last_error(), change
+        assert group([_ITEM, _ITEM, bad]) == E_ARG and text in L.swnerf_last_error() and b"item 2: " in L.swnerf_last_error(), (change, L.swnerf_last_error())
+    assert group([_ITEM], n=-1) == E_ARG and b"negative count" in L.swnerf_last_error()
+    assert L.swnerf_gemm_tn_group(None, 1, M, None) == E_ARG
+    assert L.swnerf_gemm_tn_fused(16, 256, 16, 256, -1, 16, 256, None, None, 0, 0, None, 0, None, 0, 0, None, 0, None, None) == E_ARG
+    # nothing to do: no rows, no items (checked before anything else, as before)
+    assert group([{**_ITEM, "A": None}], n=0) == 0 and L.swnerf_gemm_tn_group(None, 0, M, None) == 0
+    assert L.swnerf_gemm_tn_fused(None, 0, None, 0, 0, None, 0, None, None, 0, 0, None, 0, None, 0, 0, None, 0, None, None) == 0
+
+
+def test_row_split_arithmetic(tmp_path):
+    """csrc/wgrad_host.h (plain C, no HIP): every weight-gradient launch splits its rows with split_rows - whole slabs per
+    workgroup, every row covered, no empty workgroup, never more workgroups than asked for."""
+    src = tmp_path / "split.c"
+    src.write_text('#include <stdio.h>\n#include "wgrad_host.h"\nint main(){\n'
+                   'const long long Ms[] = {1, 31, 4096, 4097, 196608, 393216, 2147483653LL};\n'
+                   'const int targets[] = {1, 85, 170, 256, 512}, slabs[] = {16, 32};\n'
+                   'for (int a = 0; a < 7; ++a) for (int b = 0; b < 5; ++b) for (int c = 0; c < 2; ++c) {\n'
+                   '  RowSplit s = split_rows(Ms[a], targets[b], slabs[c]);\n'
+                   '  printf("%lld %d %d %lld %lld\\n", Ms[a], targets[b], slabs[c], (long long)s.rows_per_wg, (long long)s.nwg); }\n'
+                   'printf("%d %d %d %d\\n", fits_u32_offsets(32, 2432), fits_u32_offsets(1 << 20, 1 << 10), dma_aligned((void*)32, 2432), dma_aligned((void*)36, 2432) + dma_aligned((void*)32, 90));\n'
+                   'return 0;}\n')
+    exe = tmp_path / "split"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "sw-nerf_amd", "csrc"), str(src), "-o", str(exe)], check=True)
+    rows = [[int(x) for x in l.split()] for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()]
+    assert len(rows) == 7 * 5 * 2 + 1
+    for M, target, slab, rpw, nwg in rows[:-1]:
+        assert rpw > 0 and rpw % slab == 0 and nwg * rpw >= M and (nwg - 1) * rpw < M and 1 <= nwg <= target, (M, target, slab, rpw, nwg)
+    assert rows[-1] == [1, 0, 1, 0]
+    # the training chunk: 393 216 rows over 256 workgroups of 32-row slabs = 1536 rows each, nothing ragged
+    assert [r[3:] for r in rows if r[:3] == [393216, 256, 32]] == [[1536, 256]]
+
+
 def test_no_cpu_fallback(built):
     from swnerf import ray, model, embedder
     with pytest.raises(RuntimeError, match="GPU"):

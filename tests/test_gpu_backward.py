@@ -603,8 +603,8 @@ def test_training_loop_through_create_nerf(dev, tmp_path):
 @pytest.mark.parametrize("M", [4096, 70000 + 13, 300])
 def test_gemm_tn_fused_riders(dev, M):
     """swnerf_gemm_tn_fused against torch in float64: the B2 rider (63 columns of an unaligned [M,90] operand into a
-    column window of C), the A2 rider (column 3 of an [M,4] operand, with its bias), both together, and the small-M
-    fallback (separate launches)."""
+    column window of C; part of the GEMM's launch), the A2 rider (column 3 of an [M,4] operand, with its bias; always a launch
+    of its own), both together, and the small-M fallback (separate launches)."""
     from swnerf import _lib, model
     L = _lib.lib()
     gen = torch.Generator(device="cpu").manual_seed(7 * M)
@@ -645,8 +645,10 @@ def test_gemm_tn_fused_riders(dev, M):
 def test_gemm_tn_group(dev, M, n_plain):
     """swnerf_gemm_tn_group - the 256 x 256 weight-gradient GEMMs of one row chunk as ONE launch, the workgroups dealt out
     over the items - against torch in float64: plain items, one with the B2 rider (64 slot columns), one with the A2 rider
-    (column 3 of a [M,4] operand, with its bias), an item with BOTH riders (split off), ragged M (a last slab of 5 rows,
-    slices of unequal length), the small-M fallback, and accumulation into non-zero C (C += ...)."""
+    (column 3 of a [M,4] operand, with its bias: served by a launch of its own), an item with BOTH riders, ragged M (a last
+    slab of 5 rows, slices of unequal length), the small-M fallback, and accumulation into non-zero C (C += ...).
+    Then a list whose LAST item is invalid, at a row count where every item gets its own launch: refused as a whole, before
+    the first launch - every C of the valid items in front of it stays exactly zero."""
     from swnerf import _lib, model
     L = _lib.lib()
     gen = torch.Generator(device="cpu").manual_seed(11 * M + n_plain)
@@ -683,6 +685,19 @@ def test_gemm_tn_group(dev, M, n_plain):
     assert not grp.items
     for got, ref, what in want:
         assert float((got.double() - ref).abs().max()) <= tol(ref) + 1e-4, f"{what} (M={M}): {float((got.double() - ref).abs().max()):.3e} of {float(ref.abs().max()):.3e}"
+    Ms = 1024                                                 # < 4096: no item qualifies for the grouped kernel
+    Cs = [torch.zeros((256, 256), device=dev) for _ in range(3)]
+    bs = [torch.zeros(256, device=dev) for _ in range(3)]
+    for k in range(3):
+        model._gemm_tn(L, grp, Ms, A, 256 * k, 256, B, 256 * k, 256, Cs[k], 0, bs[k])
+    grp.items[-1].lda = 255                                   # the last item: leading dimension below its 256 columns
+    arr = (_lib.GemmItem * 3)(*grp.items)
+    grp.items = []
+    rc = L.swnerf_gemm_tn_group(arr, 3, Ms, grp.st)
+    torch.cuda.synchronize()
+    assert rc == -1 and b"item 2" in L.swnerf_last_error(), (rc, L.swnerf_last_error())
+    for k in range(3):
+        assert not Cs[k].any() and not bs[k].any(), f"item {k} was launched although item 2 is invalid"
 
 
 def test_feature_finish_kernel(dev):

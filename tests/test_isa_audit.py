@@ -105,27 +105,37 @@ def test_mfma_kernels_isa(asm):
 
 
 def test_weight_gradient_gemm_isa(tmp_path):
-    """backward_kernels.hip: every weight-gradient GEMM kernel - the 256x256 LDS-DMA GEMM (with and without riders, grouped), the
-    fused narrow products and
-    all four operand-alignment variants of the narrow GEMM, whose slabs are staged by LDS-DMA too - holds no scratch
-    (round-1 VERDICT: the narrow GEMM spilled 56-176 B/lane through its staging registers)."""
+    """wgrad_kernels.hip: every weight-gradient GEMM kernel holds no scratch (round-1 VERDICT: the narrow GEMM spilled 56-176 B/lane
+    through its staging registers; the first narrow5_kernel spilled 428 B/lane).  The kernels, 14 in all:
+      4  gemm_tn_kernel<VA, VB>                   the operand-alignment variants of the narrow GEMM (slabs staged by LDS-DMA too)
+      2  gemm_tn_dma_kernel<HB2>                  the 256x256 LDS-DMA GEMM, without and with the B2 rider
+      1  gemm_tn_dma_group_kernel                 the grouped launch: both of those bodies
+      5  gemm_tn_tiled_kernel<TO, TI, WO, WI>     the wave grids of the skinny double-buffered kernel
+      1  narrow5_kernel, 1 narrow_plan_kernel     the fused narrow products (five roles / four tile shapes, the slab loop once per role)
+    and the static MFMA counts of the two kernels that hold several bodies: a body that comes back (or goes missing) shows here."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = tmp_path / "bwd.s"
+    out = tmp_path / "wgrad.s"
     subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
-                    os.path.join(ROOT, "sw-nerf_amd", "csrc", "backward_kernels.hip")], check=True, stderr=subprocess.DEVNULL)
+                    os.path.join(ROOT, "sw-nerf_amd", "csrc", "wgrad_kernels.hip")], check=True, stderr=subprocess.DEVNULL)
     asm = out.read_text()
-    seen = 0
+    seen, mfma = 0, {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", asm, re.S):
         name = m.group(1)
-        if "gemm_tn" not in name and "narrow5" not in name:
+        if "gemm_tn" not in name and "narrow5" not in name and "narrow_plan" not in name:
             continue
         priv = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
         assert priv == 0, f"{name} spills {priv} bytes/lane"
         body = asm[asm.index("\n" + name + ":"):]
-        assert "scratch_" not in body[:body.index("s_endpgm")]
+        body = body[:body.index(".Lfunc_end")]                # the whole kernel (these kernels have early exits: several s_endpgm)
+        assert "scratch_" not in body, name
+        mfma[name] = len(re.findall(r"^\s*v_mfma", body, re.M))
         seen += 1
-    assert seen == 14               # + the five wave grids of the skinny double-buffered kernel (gemm_tn_tiled_kernel) + the grouped launch
-                                    # + the fused narrow products (narrow5_kernel: its first version spilled 428 B / lane)
+    assert seen == 14
+    count = lambda key: [n for k, n in mfma.items() if key in k]
+    # four tile shapes x 8 k-pairs of a 16-row slab x 4 tiles
+    assert count("narrow_plan_kernel") == [4 * 8 * 4]
+    # two bodies, each the slab loop once per bias role: without the rider 16 k-pairs x 4 tiles, with it 4 unrolled k-pairs x 5 tiles
+    assert count("gemm_tn_dma_group_kernel") == [2 * 16 * 4 + 2 * 4 * 5]
 
 
 def test_x3_kernels_isa(tmp_path):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The 256 x 256 weight-gradient GEMMs of one 393 216-row chunk of a training step, alone on the GPU: one launch each (plain,
-with the B2 rider, with the A2 rider), the six plain ones back to back on one stream, on two streams, and as ONE grouped launch
+"""The 256 x 256 weight-gradient GEMMs of one 393 216-row chunk of a training step, alone on the GPU: one call each (plain,
+with the B2 rider, with the A2 rider - which is a second launch), the six plain ones back to back on one stream, on two streams, and as ONE grouped launch
 (swnerf_gemm_tn_group), with and without the two rider items in the group.  ms per call, TFLOP/s on the MFMA work."""
 import os
 import sys
@@ -90,9 +90,9 @@ print("| what | ms | TFLOP/s (main 256x256 MFMA work only) |")
 print("|---|---|---|")
 timeit("one plain GEMM", lambda: plain(st, 1), FL)
 timeit("one GEMM with the B2 rider (pts_linears.5)", lambda: l5(st), FL)
-timeit("one GEMM with the A2 rider (feature_linear + alpha_linear)", lambda: feat(st), FL)
+timeit("one GEMM with the A2 rider (feature_linear + alpha_linear: TWO launches, the rider is its own)", lambda: feat(st), FL)
 timeit("six plain, one stream", six_serial, 6 * FL)
 timeit("six plain, two side streams", six_two_streams, 6 * FL)
 timeit("six plain, ONE grouped launch", group(0), 6 * FL)
 timeit("six plain + two with riders, two side streams", eight_two_streams, 8 * FL)
-timeit("six plain + two with riders, ONE grouped launch", group(2), 8 * FL)
+timeit("six plain + two with riders, ONE grouped launch (+ the A2 rider's own)", group(2), 8 * FL)
