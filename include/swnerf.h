@@ -425,6 +425,14 @@ int swnerf_linear(const float* x, int ldx, int64_t M, int K, const float* weight
 int swnerf_gemm_nn(const float* a, int lda, int64_t M, int K, const float* b, int ldb, int N, float* c, int ldc,
                    void* stream);
 int swnerf_relu_mask(float* dy, const float* y, int64_t n, void* stream);
+/* swnerf_gemm_tn with a reproducible sum, for any No, Ni up to 65536: every row slice stores its own partial product into
+ * ws and the slices are added in slice order (no atomics), and the split depends on (M, No, Ni) alone, so two equal calls give
+ * equal bits.  C and bias are accumulated into, as by swnerf_gemm_tn; bias may be NULL.  ws: DEVICE scratch of at least
+ * swnerf_gemm_tn_ordered_ws_floats(M, No, Ni) floats (0 for M == 0 or a shape that is not accepted): up to 256 partial
+ * products, as many as fit into 16 MiB, at least one. */
+size_t swnerf_gemm_tn_ordered_ws_floats(int64_t M, int No, int Ni);
+int swnerf_gemm_tn_ordered(const float* A, int lda, int No, const float* B, int ldb, int Ni, int64_t M,
+                           float* C, int ldc, float* bias, float* ws, size_t ws_floats, void* stream);
 
 /* The same GEMM with a choice of epilogue, and the ELU backward (TNeRF, model.py:152-210, on the op path):
  * linear_act: y = act(x . weight^T + bias), act = SWNERF_ACT_NONE / SWNERF_ACT_RELU / SWNERF_ACT_ELU (alpha = 1; an
@@ -461,6 +469,25 @@ size_t swnerf_metrics_workspace_bytes(int64_t n, int64_t h, int64_t w, int mode)
 int swnerf_image_metrics(const float* pred, const float* gt, int64_t n, int64_t h, int64_t w, int mode, int range_mode,
                          double fixed_range, int clip_pred, void* workspace, double* mse, double* psnr, double* range,
                          double* ssim, float* ssim_map /* may be NULL */, void* stream);
+
+/* ---- Laplacian pyramid (multires_dnerf/pyramid.py) ------------------------------------------------------------------
+ * Images are [n, h, w, c] fp32 NHWC, contiguous, c in 1..4, sides in 1..2^20; every element offset is 64-bit.  n == 0 is
+ * a successful no-op.  One launch each, no workspace, no host synchronisation, no atomics: bit-identical from run to run.
+ *   down        dst[n, h/2, w/2, c] = box2x2(blur_k(src)): blur_k is the k x k cross-correlation with zero padding k/2
+ *               (weights: DEVICE float [k*k], row-major; k odd, k <= 7), box2x2 the mean of pixels (2i, 2j) .. (2i+1, 2j+1)
+ *               = F.interpolate(scale_factor=0.5, bilinear, align_corners=False).  An odd last row / column is dropped by
+ *               the box but seen by its neighbours' taps.  h, w >= 2.
+ *   up_axpy     out[n, H, W, c] = base + alpha * up(coarse[n, h, w, c]); base may be NULL (out = alpha * up(coarse)).  up is
+ *               bilinear with align_corners=False: per axis s = max(scale * (d + 0.5) - 0.5, 0), scale = (float)n_in / n_out,
+ *               i0 = floor(s), i1 = min(i0 + 1, n_in - 1), lambda = s - i0, all fp32.  (h, w) == (H, W): exactly
+ *               base + alpha * coarse.  out may be base itself.
+ *   up_adjoint  g_coarse[n, h, w, c] = the transpose of up applied to g_out[n, H, W, c], gathered in a fixed order. */
+int swnerf_pyramid_down(const float* src, int64_t n, int64_t h, int64_t w, int c, const float* weights, int k, float* dst,
+                        void* stream);
+int swnerf_pyramid_up_axpy(const float* coarse, int64_t n, int64_t h, int64_t w, int c, const float* base /* may be NULL */,
+                           float alpha, int64_t H, int64_t W, float* out, void* stream);
+int swnerf_pyramid_up_adjoint(const float* g_out, int64_t n, int64_t H, int64_t W, int c, int64_t h, int64_t w,
+                              float* g_coarse, void* stream);
 
 #ifdef __cplusplus
 }

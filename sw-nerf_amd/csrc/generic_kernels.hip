@@ -318,3 +318,121 @@ extern "C" int swnerf_elu_grad(float* dy, const float* y, int64_t n, void* strea
     hipLaunchKernelGGL(elu_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, y, n);
     return sw_check(hipGetLastError(), "elu_grad launch");
 }
+
+// ---------------------------------------------------------------------------------------------
+// The weight gradient with a REPRODUCIBLE sum: C[No,ldc] += A[M,lda]^T . B[M,ldb], bias[No] += column sums of A - what
+// swnerf_gemm_tn computes, but swnerf_gemm_tn combines its row slices with float atomics, so two identical calls differ
+// in the last bits.  Here every row slice writes its own partial product (plain stores, one owner per entry) and a second
+// kernel adds the slices in slice order.  The split depends on (M, No, Ni) alone, so equal calls give equal bits.
+//   ws: [nslices][No][Ni + 1] - column Ni holds the slice's column sums of A.
+// One wave owns a 32 x 32 tile of a slice's partial product (4 waves: 4 neighbouring column tiles, sharing the A rows
+// through L1); lane (i, h) supplies A[m + h][o0 + i] and B[m + h][i0 + i] straight from global memory, two contiguous
+// 128-byte segments per wave load, bounds checked (any leading dimension, any No / Ni, odd slice lengths).
+struct OrderedTN { const float* A; int lda; int No; const float* B; int ldb; int Ni; int64_t M; int64_t rows_per_slice; float* ws; };
+
+__global__ void __launch_bounds__(256) gemm_tn_slice_kernel(OrderedTN P) {
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int it = 4 * blockIdx.z + (threadIdx.x >> 6);       // this wave's column tile
+    if (32 * it >= P.Ni) return;                                // (no barrier below)
+    const int o = 32 * blockIdx.y + i, col = 32 * it + i;
+    const bool ao = o < P.No, bc = col < P.Ni;
+    const int64_t m0 = (int64_t)blockIdx.x * P.rows_per_slice;
+    const int64_t mend = m0 + P.rows_per_slice < P.M ? m0 + P.rows_per_slice : P.M;
+    const float* Ap = P.A + (ao ? o : 0);
+    const float* Bp = P.B + (bc ? col : 0);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    float bsum = 0.f;
+    const int64_t nsteps = (mend - m0 + 1) / 2;               // two rows per MFMA; an odd slice's last step has one
+    // a row past the slice (and a column past the operand) is read at a clamped, valid address and replaced by zero
+    auto step = [&](int64_t s, float& a, float& b) {
+        const int64_t m = m0 + 2 * s + h, mc = m < mend ? m : mend - 1;
+        a = Ap[mc * P.lda];
+        b = Bp[mc * P.ldb];
+        a = (m < mend && ao) ? a : 0.f;
+        b = (m < mend && bc) ? b : 0.f;
+    };
+    int64_t s = 0;
+    for (; s + 4 <= nsteps; s += 4) {                          // four steps' loads in flight
+        float a[4], b[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) step(s + q, a[q], b[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            bsum += a[q];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], b[q], acc, 0, 0, 0);
+        }
+    }
+    for (; s < nsteps; ++s) {
+        float a, b;
+        step(s, a, b);
+        bsum += a;
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+    }
+    // C/D map: register r of lane (j = i, h) is row (r&3) + 8(r>>2) + 4h of the tile, column j
+    float* W = P.ws + (size_t)blockIdx.x * P.No * (P.Ni + 1);
+    if (bc) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int orow = 32 * blockIdx.y + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (orow < P.No) W[(size_t)orow * (P.Ni + 1) + col] = acc[r];
+        }
+    }
+    if (it == 0) {
+        bsum += __shfl_xor(bsum, 32, 64);
+        if (h == 0 && ao) W[(size_t)o * (P.Ni + 1) + P.Ni] = bsum;
+    }
+}
+
+__global__ void __launch_bounds__(256) gemm_tn_sum_slices_kernel(const float* ws, int nslices, int No, int Ni, float* C, int ldc, float* bias) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x, n = (int64_t)No * (Ni + 1);
+    if (e >= n) return;
+    float s = 0.f;
+    for (int k = 0; k < nslices; ++k) s += ws[k * n + e];       // slice order, always
+    const int o = (int)(e / (Ni + 1)), col = (int)(e % (Ni + 1));
+    if (col < Ni) C[(size_t)o * ldc + col] += s;
+    else if (bias) bias[o] += s;
+}
+
+// at most 256 slices of at least 512 rows (an even number each), and at most 16 MiB of partial products
+static void ordered_split(int64_t M, int No, int Ni, int64_t* rows_per_slice, int64_t* nslices) {
+    int64_t ns = (M + 511) / 512;
+    const int64_t cap = ((int64_t)4 << 20) / ((int64_t)No * (Ni + 1));
+    if (ns > 256) ns = 256;
+    if (ns > cap) ns = cap;
+    if (ns < 1) ns = 1;
+    const int64_t rows = ((M + ns - 1) / ns + 1) / 2 * 2;
+    *rows_per_slice = rows;
+    *nslices = (M + rows - 1) / rows;
+}
+
+// (the tiles of C lie on grid.y and grid.z: 65535 blocks each at most)
+static bool ordered_shape_ok(int64_t M, int No, int Ni) { return M >= 0 && No >= 1 && No <= 65536 && Ni >= 1 && Ni <= 65536; }
+
+extern "C" size_t swnerf_gemm_tn_ordered_ws_floats(int64_t M, int No, int Ni) {
+    if (!ordered_shape_ok(M, No, Ni) || M == 0) return 0;
+    int64_t rows, ns;
+    ordered_split(M, No, Ni, &rows, &ns);
+    return (size_t)ns * No * (Ni + 1);
+}
+
+extern "C" int swnerf_gemm_tn_ordered(const float* A, int lda, int No, const float* B, int ldb, int Ni, int64_t M,
+                                      float* C, int ldc, float* bias, float* ws, size_t ws_floats, void* stream) {
+    if (M == 0) return 0;
+    if (!A || !B || !C || !ws || M < 0 || No < 1 || Ni < 1 || lda < No || ldb < Ni || ldc < Ni)
+        return sw_fail(SWNERF_E_ARG, "gemm_tn_ordered: bad arguments (M=%lld No=%d Ni=%d lda=%d ldb=%d ldc=%d)", (long long)M, No, Ni, lda, ldb, ldc);
+    if (!ordered_shape_ok(M, No, Ni)) return sw_fail(SWNERF_E_UNSUPP, "gemm_tn_ordered: No and Ni up to 65536 (No=%d Ni=%d)", No, Ni);
+    OrderedTN P;
+    int64_t ns;
+    ordered_split(M, No, Ni, &P.rows_per_slice, &ns);
+    if (ws_floats < (size_t)ns * No * (Ni + 1))
+        return sw_fail(SWNERF_E_ARG, "gemm_tn_ordered: workspace of %zu floats, needs %zu (swnerf_gemm_tn_ordered_ws_floats)", ws_floats, (size_t)ns * No * (Ni + 1));
+    P.A = A; P.lda = lda; P.No = No; P.B = B; P.ldb = ldb; P.Ni = Ni; P.M = M; P.ws = ws;
+    const int ti = (Ni + 31) / 32;
+    hipLaunchKernelGGL(gemm_tn_slice_kernel, dim3((unsigned)ns, (unsigned)((No + 31) / 32), (unsigned)((ti + 3) / 4)), dim3(256), 0, (hipStream_t)stream, P);
+    if (int rc = sw_check(hipGetLastError(), "gemm_tn_ordered launch")) return rc;
+    const int64_t n = (int64_t)No * (Ni + 1);
+    hipLaunchKernelGGL(gemm_tn_sum_slices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)ws, (int)ns, No, Ni, C, ldc, bias);
+    return sw_check(hipGetLastError(), "gemm_tn_ordered sum launch");
+}

@@ -28,7 +28,9 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_packed_x3_floats_kind", "swnerf_pack_net_x3_kind",
            "swnerf_mc_workspace_bytes", "swnerf_mc_count", "swnerf_mc_emit",
            "swnerf_linear_act", "swnerf_elu_grad",
-           "swnerf_metrics_workspace_bytes", "swnerf_image_metrics"]
+           "swnerf_metrics_workspace_bytes", "swnerf_image_metrics",
+           "swnerf_pyramid_down", "swnerf_pyramid_up_axpy", "swnerf_pyramid_up_adjoint",
+           "swnerf_gemm_tn_ordered_ws_floats", "swnerf_gemm_tn_ordered"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -104,6 +106,10 @@ def lib():
     L.swnerf_pack_net_bwd.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]
     L.swnerf_mlp_backward_dx.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
     L.swnerf_gemm_tn.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]
+    L.swnerf_gemm_tn_ordered_ws_floats.restype = c_size_t
+    L.swnerf_gemm_tn_ordered_ws_floats.argtypes = [c_int64, c_int, c_int]
+    L.swnerf_gemm_tn_ordered.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]
     L.swnerf_gemm_tn_fused.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p,
                                        c_void_p, c_int, c_int, c_void_p, c_int,
                                        c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
@@ -155,10 +161,14 @@ def lib():
     L.swnerf_metrics_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int]
     L.swnerf_image_metrics.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_double, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.swnerf_pyramid_down.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]
+    L.swnerf_pyramid_up_axpy.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, ctypes.c_float, c_int64, c_int64,
+                                         c_void_p, c_void_p]
+    L.swnerf_pyramid_up_adjoint.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
                         "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",
-                        "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes"):
+                        "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes", "swnerf_gemm_tn_ordered_ws_floats"):
             getattr(L, name).restype = c_int
     if L.swnerf_version() != 112:
         raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 112 - rebuild it "

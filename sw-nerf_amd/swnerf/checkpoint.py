@@ -53,3 +53,31 @@ def reload_latest(basedir, expname, network_fn, network_fine=None, optimizer=Non
     if len(ckpts) > 0 and not no_reload:
         return load_checkpoint(ckpts[-1], network_fn, network_fine, optimizer, map_location), ckpts[-1]
     return 0, None
+
+
+def save_multires(basedir, expname, step, global_step, networks_fn, networks_fine=None, optimizers=None):
+    """multires_dnerf/multires_dnerf.py:1011-1023: ONE basedir/expname/{step:06d}.tar for all levels, with
+    global_step, network_fn_{l}, network_fine_{l} (levels that have a fine net) and optimizer_{l}; returns the path."""
+    os.makedirs(os.path.join(basedir, expname), exist_ok=True)
+    path = os.path.join(basedir, expname, '{:06d}.tar'.format(step))
+    d = {'global_step': global_step}
+    for l, net in enumerate(networks_fn):
+        d[f'network_fn_{l}'] = net.state_dict()
+        fine = None if networks_fine is None else networks_fine[l]
+        if fine is not None:
+            d[f'network_fine_{l}'] = fine.state_dict()
+        if optimizers is not None and optimizers[l] is not None:
+            d[f'optimizer_{l}'] = optimizers[l].state_dict()
+    torch.save(d, path)
+    return path
+
+
+def load_multires(path, layer, network_fn, network_fine=None, optimizer=None, map_location=None):
+    """multires_dnerf.py:314-327: level `layer` of a MultiRes checkpoint into its nets and optimizer; returns global_step."""
+    ckpt = torch.load(path, map_location=map_location, weights_only=False)
+    if optimizer is not None and ckpt.get(f'optimizer_{layer}'):
+        optimizer.load_state_dict(ckpt[f'optimizer_{layer}'])
+    network_fn.load_state_dict(ckpt[f'network_fn_{layer}'])
+    if network_fine is not None:
+        network_fine.load_state_dict(ckpt[f'network_fine_{layer}'])
+    return int(ckpt['global_step'])

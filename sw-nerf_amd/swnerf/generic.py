@@ -4,6 +4,8 @@ use_viewdirs=True with get_embedder-sized inputs): `use_viewdirs=False` - the re
 utils.py:26-29, handled at model.py:59-60 -, other depths / widths / skip sets, other input sizes.  Slower than the
 fused path (every activation round-trips HBM, like in the reference), same arithmetic class (fp32 MFMA, fp32
 accumulate), differentiable: dX = dY.W (swnerf_gemm_nn), dW = dY^T.X / db (swnerf_gemm_tn), relu' (swnerf_relu_mask).
+swnerf_gemm_tn adds its row slices with float atomics, so two equal backward passes differ in the last bits; a module with
+`reproducible_wgrad = True` (create_multires sets it) takes swnerf_gemm_tn_ordered instead, which adds them in a fixed order.
 The `cat`/`split` glue between layers is torch (memory movement only)."""
 import torch
 
@@ -35,9 +37,9 @@ class _Linear(torch.autograd.Function):
     """y = act(x . W^T + b) with hand-written forward and backward kernels."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act):
+    def forward(ctx, x, weight, bias, act, ordered=False):
         y = _linear_raw(x, weight, bias, act)
-        ctx.act = act
+        ctx.act, ctx.ordered = act, ordered
         ctx.save_for_backward(x, weight, y if act != _lib.ACT_NONE else x.new_empty(0))
         ctx.has_bias = bias is not None
         return y
@@ -63,45 +65,52 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             dw = torch.zeros((N, K), dtype=torch.float32, device=x.device)
             db = torch.zeros((N,), dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            if ctx.ordered:
+                nws = L.swnerf_gemm_tn_ordered_ws_floats(M, N, K)
+                ws = torch.empty((nws,), dtype=torch.float32, device=x.device)
+                _lib.check(L.swnerf_gemm_tn_ordered(_lib.ptr(dy), N, N, _lib.ptr(x), x.stride(0), K, M, _lib.ptr(dw), K, _lib.ptr(db),
+                                                    _lib.ptr(ws), nws, st), "gemm_tn_ordered")
+                return dx, dw, db, None, None
             for o0 in range(0, N, 256):                      # swnerf_gemm_tn: up to 256 output rows per call
                 no = min(256, N - o0)
                 _lib.check(L.swnerf_gemm_tn(dy.data_ptr() + 4 * o0, N, no, _lib.ptr(x), x.stride(0), K, M, dw.data_ptr() + 4 * o0 * K, K,
                                             (db.data_ptr() + 4 * o0) if db is not None else None, st), "gemm_tn")
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
-def linear(x, lin, relu=False, act=None):
+def linear(x, lin, relu=False, act=None, ordered=False):
     """nn.Linear `lin` applied to x [M, K] by the HIP GEMM with a fused epilogue: `act` (_lib.ACT_NONE / ACT_RELU / ACT_ELU),
-    or, when act is None, relu if `relu`."""
+    or, when act is None, relu if `relu`.  ordered: the weight gradient adds its row slices in a fixed order."""
     act = (_lib.ACT_RELU if relu else _lib.ACT_NONE) if act is None else int(act)
     x = _lib.dev_f32(x, "x", lin.in_features)
     w, b = lin.weight, lin.bias
     if not w.is_cuda:
         raise RuntimeError("swnerf: module parameters must be on the GPU (call .to('cuda')); no CPU fallback")
     if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad)):
-        return _Linear.apply(x, _c32(w), None if b is None else _c32(b), act)
+        return _Linear.apply(x, _c32(w), None if b is None else _c32(b), act, bool(ordered))
     return _linear_raw(x, _c32(w.detach()), None if b is None else _c32(b.detach()), act)
 
 
-def canonical_forward(mod, x):
+def canonical_forward(mod, x, ordered=None):
     """vallina_NeRF.forward / NeRFOriginal.forward (model.py:39-62, 273-296) for any D, W, skips, use_viewdirs."""
+    ordered = getattr(mod, "reproducible_wgrad", False) if ordered is None else ordered
     lead = x.shape[:-1]
     x = _lib.dev_f32(x, "x").reshape(-1, x.shape[-1])
     input_pts, input_views = torch.split(x, [mod.input_ch, mod.input_ch_views], dim=-1)
     h = input_pts
     for i, l in enumerate(mod.pts_linears):
-        h = linear(h, l, relu=True)
+        h = linear(h, l, relu=True, ordered=ordered)
         if i in mod.skips:
             h = torch.cat([input_pts, h], -1)
     if mod.use_viewdirs:
-        alpha = linear(h, mod.alpha_linear)
-        feature = linear(h, mod.feature_linear)
+        alpha = linear(h, mod.alpha_linear, ordered=ordered)
+        feature = linear(h, mod.feature_linear, ordered=ordered)
         h = torch.cat([feature, input_views], -1)
         for l in mod.views_linears:
-            h = linear(h, l, relu=True)
-        outputs = torch.cat([linear(h, mod.rgb_linear), alpha], -1)
+            h = linear(h, l, relu=True, ordered=ordered)
+        outputs = torch.cat([linear(h, mod.rgb_linear, ordered=ordered), alpha], -1)
     else:
-        outputs = linear(h, mod.output_linear)
+        outputs = linear(h, mod.output_linear, ordered=ordered)
     return outputs.reshape(*lead, outputs.shape[-1])
 
 
@@ -143,6 +152,7 @@ def temporal_forward(mod, x, ts):
     x = _lib.dev_f32(x, "x").reshape(-1, x.shape[-1])
     input_pts, input_views = torch.split(x, [mod.input_ch, mod.input_ch_views], dim=-1)
     t = ts[0].reshape(-1, ts[0].shape[-1])
+    ordered = getattr(mod, "reproducible_wgrad", False)
     lo, hi = torch.aminmax(t[:, :1])
     lo, hi = float(lo), float(hi)
     assert lo == hi, "Only accepts all points from same time"                # model.py:141
@@ -151,14 +161,14 @@ def temporal_forward(mod, x, ts):
     else:
         h = torch.cat([input_pts, _lib.dev_f32(t, "ts[0]")], dim=-1)         # query_time, model.py:128-136
         for i, l in enumerate(mod._time):
-            h = linear(h, l, relu=True)
+            h = linear(h, l, relu=True, ordered=ordered)
             if i in mod.skips:
                 h = torch.cat([input_pts, h], -1)
-        dx = linear(h, mod._time_out)
+        dx = linear(h, mod._time_out, ordered=ordered)
         if mod.embed_fn is None:
             raise RuntimeError("swnerf: DirectTemporalNeRF needs embed_fn to re-embed x + dx (model.py:148-149)")
         input_pts = embed_with_grad(mod.embed_fn, input_pts[:, :3] + dx)
-    out = canonical_forward(mod._occ, torch.cat([input_pts, input_views], dim=-1))
+    out = canonical_forward(mod._occ, torch.cat([input_pts, input_views], dim=-1), ordered=ordered)
     return out.reshape(*lead, out.shape[-1]), dx.reshape(*lead, 3)
 
 

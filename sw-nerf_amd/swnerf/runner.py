@@ -8,13 +8,15 @@ written against the reference only swaps its imports.  `args` is any object with
 (nerf/run.py:557-596 with calculate_metrics :49-61, and the last cell of d_nerf/metrics.ipynb) on the GPU metrics."""
 import json
 import os
+import random
 
 import numpy as np
 import torch
 
-from . import metrics, render, render_dnerf, render_tnerf
-from .png import read_png
-from .checkpoint import reload_latest
+from . import metrics, pyramid, render, render_dnerf, render_tnerf
+from .png import read_png, write_png
+from .checkpoint import reload_latest, find_checkpoints, load_multires, to8b
+from .ray import get_rays
 from .embedder import get_embedder
 from .model import vallina_NeRF, NeRF, TNeRF
 
@@ -147,6 +149,190 @@ def create_tnerf(args, device=None):
     test['perturb'] = False
     test['raw_noise_std'] = 0.
     return kw, test, start, grad_vars, optimizer
+
+
+# ---- MultiRes D-NeRF (multires_dnerf/multires_dnerf.py): one DirectTemporalNeRF per Laplacian-pyramid level -------------
+MULTIRES_CHANNELS = [(20, 8, 20), (10, 4, 10), (10, 4, 10), (-1, -1, -1)]      # multires_dnerf.py:665, per level
+
+
+def create_multires(args, device=None):
+    """multires_dnerf.py:658-685 with its create_nerf(args, channels, layer) (:242-352): for every level the D-NeRF pair
+    with that level's encoders - get_embedder(channels[0], 3, channels[0]) for position, channels[1] for TIME and
+    channels[2] for the VIEWS (the reference's order; -1 is the identity encoder) -, one Adam per level, and the level's
+    part of the newest MultiRes checkpoint.  -> the five lists (render_kwargs_train_list, render_kwargs_test_list,
+    start_list, grad_vars_list, optimizer_list); near / far are left to the caller.  None of the level shapes is a fused
+    shape: they run layer by layer on the generic kernels (swnerf/generic.py).  args.reproducible_wgrad (extra, optional,
+    default False): the nets' weight gradients add their row slices in a fixed order (swnerf_gemm_tn_ordered) instead of with
+    float atomics, so that a backward pass repeats bit for bit - slower on large batches.  fp32 only."""
+    if getattr(args, "do_half_precision", False):
+        raise NotImplementedError("swnerf.create_multires: do_half_precision (apex amp) is not built; the HIP path is fp32")
+    if not 1 <= args.layer_num <= len(MULTIRES_CHANNELS):
+        raise ValueError(f"swnerf.create_multires: layer_num must be 1..{len(MULTIRES_CHANNELS)}, got {args.layer_num}")
+    device = _device(device)
+    ckpts = find_checkpoints(args.basedir, args.expname, args.ft_path)
+    trains, tests, starts, grads, optimizers = [], [], [], [], []
+    for layer in range(args.layer_num):
+        train, test, start, grad_vars, optimizer = _create_multires_level(args, MULTIRES_CHANNELS[layer], layer, device, ckpts)
+        trains.append(train)
+        tests.append(test)
+        starts.append(start)
+        grads.append(grad_vars)
+        optimizers.append(optimizer)
+    return trains, tests, starts, grads, optimizers
+
+
+def _create_multires_level(args, channels, layer, device, ckpts):
+    embed_fn, input_ch = get_embedder(channels[0], 3, channels[0])
+    embedtime_fn, input_ch_time = get_embedder(channels[1], 1, channels[1])
+    input_ch_views, embeddirs_fn = 0, None
+    if args.use_viewdirs:
+        embeddirs_fn, input_ch_views = get_embedder(channels[2], 3, channels[2])
+    output_ch = 5 if args.N_importance > 0 else 4
+    skips = [4]
+    make = lambda D, W: NeRF.get_by_name(args.nerf_type, D=D, W=W, input_ch=input_ch, output_ch=output_ch, skips=skips,
+                                         input_ch_views=input_ch_views, input_ch_time=input_ch_time,
+                                         use_viewdirs=args.use_viewdirs, embed_fn=embed_fn,
+                                         zero_canonical=not args.not_zero_canonical).to(device)
+    model = make(args.netdepth, args.netwidth)
+    grad_vars = list(model.parameters())
+    model_fine = None
+    if args.use_two_models_for_fine:
+        model_fine = make(args.netdepth_fine, args.netwidth_fine)
+        grad_vars += list(model_fine.parameters())
+    netchunk, discr = args.netchunk, args.nerf_type != "temporal"
+    network_query_fn = lambda inputs, viewdirs, ts, network_fn: render_dnerf.run_network(
+        inputs, viewdirs, ts, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, embedtime_fn=embedtime_fn,
+        netchunk=netchunk, embd_time_discr=discr)
+    for net in (model, model_fine):
+        if net is not None:                                  # generic.py: weight gradients summed in a fixed order, equal bits every pass
+            net.reproducible_wgrad = bool(getattr(args, "reproducible_wgrad", False))
+    optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
+    start = 0
+    if len(ckpts) > 0 and not args.no_reload:
+        start = load_multires(ckpts[-1], layer, model, model_fine, optimizer, map_location=device)
+    train, test = _render_kwargs(args, network_query_fn, model, model_fine,
+                                 {'use_two_models_for_fine': args.use_two_models_for_fine})
+    return train, test, start, grad_vars, optimizer
+
+
+def pyramid_hwf(hwf, layer_num):
+    """multires_dnerf.py:629-637: [H // 2^l, W // 2^l, focal / 2^l] per level."""
+    H, W, focal = hwf
+    H, W = int(H), int(W)
+    out = []
+    for layer in range(layer_num):
+        scale = 2 ** layer
+        if H // scale <= 0 or W // scale <= 0:
+            raise ValueError(f"swnerf.pyramid_hwf: level {layer} of a {H} x {W} image is empty")
+        out.append([H // scale, W // scale, focal / scale])
+    return out
+
+
+def get_random_patch_coords(H, W, patch_size, current_iter, n=4000, sigma_factor=4):
+    """multires_dnerf.py:500-561: the (y, x) corner of a patch: before iteration n uniform over the central region, from
+    then on normal around the centre (sigma = side / sigma_factor), clipped into the image."""
+    if H <= patch_size or W <= patch_size:
+        return 0, 0
+    center_y = (H - patch_size) / 2
+    center_x = (W - patch_size) / 2
+    if current_iter < n:
+        half_patch_area_y = H / 4
+        half_patch_area_x = W / 4
+        min_y = max(0, int(center_y - half_patch_area_y / 2))
+        max_y = min(int(center_y + half_patch_area_y / 2), H - patch_size)
+        min_x = max(0, int(center_x - half_patch_area_x / 2))
+        max_x = min(int(center_x + half_patch_area_x / 2), W - patch_size)
+        y = random.randint(min_y, max_y)
+        x = random.randint(min_x, max_x)
+    else:
+        y = int(torch.normal(mean=center_y, std=H / sigma_factor, size=(1,)).item())
+        x = int(torch.normal(mean=center_x, std=W / sigma_factor, size=(1,)).item())
+        y = max(0, min(y, H - patch_size))
+        x = max(0, min(x, W - patch_size))
+    return y, x
+
+
+def initialize_patches(pyr_hwf, base_patch_size=4, cur_iter=0):
+    """multires_dnerf.py:562-585: one (y, x) per level, finest first: drawn at the COARSEST level with `base_patch_size`
+    (the reference's train() passes its finest-level patch size, 32, here: kept as it is) and doubled level by level."""
+    patch_coords = []
+    for layer, (H, W, focal) in enumerate(pyr_hwf[::-1]):
+        if layer == 0:
+            y, x = get_random_patch_coords(H, W, base_patch_size, cur_iter)
+        else:
+            prev_y, prev_x = patch_coords[layer - 1]
+            y, x = prev_y * 2, prev_x * 2
+        patch_coords.append((y, x))
+    return patch_coords[::-1]
+
+
+def multires_train_loss(i, img_i, images, pyr_images, poses, times, pyr_hwf, patch_size_list, render_kwargs_train_list, args,
+                        base_patch_size=32, patch_coords=None):
+    """The body of the reference's joint iteration (multires_dnerf.py:909-996) up to, and excluding, backward(): per level a
+    patch of rays of frame img_i rendered by that level's nets against the same patch of that level of the pyramid
+    (mse of rgb, plus mse of rgb0 when present), then the levels' patches reconstructed through the pyramid against the
+    patch of the full image, added to the loss once i >= args.global_optimization_epoch.  near / far come with the
+    render kwargs.  `patch_coords` (extra, optional) fixes the per-level corners instead of drawing them.
+    -> (loss, per_level_losses, global_loss, global_psnr, reconstructed)."""
+    if patch_coords is None:
+        patch_coords = initialize_patches(pyr_hwf, base_patch_size=base_patch_size, cur_iter=i)
+    pyramid_outputs, per_level = [], []
+    loss = 0
+    for layer, render_kwargs_train in enumerate(render_kwargs_train_list):
+        H_l, W_l, focal_l = pyr_hwf[layer]
+        patch_size = patch_size_list[layer]
+        y, x = patch_coords[layer]
+        target_patch = pyr_images[layer][img_i][y:y + patch_size, x:x + patch_size, :3]
+        rays_o, rays_d = get_rays(H_l, W_l, float(focal_l), poses[img_i, :3, :4])
+        rays_o = rays_o[y:y + patch_size, x:x + patch_size].reshape(-1, 3)
+        rays_d = rays_d[y:y + patch_size, x:x + patch_size].reshape(-1, 3)
+        rgb, disp, acc, extras = render_dnerf.render(patch_size, patch_size, focal_l, chunk=args.chunk, rays=(rays_o, rays_d),
+                                                     frame_time=times[img_i], retraw=True, **render_kwargs_train)
+        ph, pw = target_patch.shape[0], target_patch.shape[1]
+        rgb = rgb.reshape(ph, pw, 3)
+        img_loss = torch.nn.functional.mse_loss(rgb, target_patch)
+        if 'rgb0' in extras:
+            loss = loss + torch.nn.functional.mse_loss(extras['rgb0'].reshape(ph, pw, 3), target_patch)
+        loss = loss + img_loss
+        per_level.append(img_loss)
+        pyramid_outputs.append(rgb.unsqueeze(0))
+    y, x = patch_coords[0]
+    patch_size = patch_size_list[0]
+    target = images[img_i][y:y + patch_size, x:x + patch_size, :3]
+    reconstructed, global_loss, global_psnr = pyramid.reconstruct_and_compute_loss(pyramid_outputs, target)
+    if i >= args.global_optimization_epoch:
+        loss = loss + global_loss
+    return loss, per_level, global_loss, global_psnr, reconstructed
+
+
+def render_path_multires(render_poses, render_times, hwf, chunk, render_kwargs_test_list, level_hwf="reference", gt_imgs=None,
+                         savedir=None):
+    """The test-set / video render of the MultiRes runner (multires_dnerf.py:741-755): every level's frames, then their
+    reconstruction.  level_hwf="reference": every level at `hwf`, as the reference does - reconstruct is then the exact
+    fp32 sum of the levels; "pyramid": level l at pyramid_hwf(hwf)[l], 1 + 1/4 + 1/16 + ... of one frame's rays, and
+    reconstruct upsamples through the pyramid kernels.  With `savedir` the levels' PNGs go to savedir/layer_{l}/estim/
+    (render_dnerf.render_path) and the reconstructed frames to savedir/estim/.  gt_imgs: per level, or None.
+    -> (frames [N,H,W,3], per_level_frames: list of [N,H_l,W_l,3]), numpy."""
+    if level_hwf not in ("reference", "pyramid"):
+        raise ValueError(f"swnerf.render_path_multires: level_hwf must be 'reference' or 'pyramid', got {level_hwf!r}")
+    n_levels = len(render_kwargs_test_list)
+    hwfs = pyramid_hwf(hwf, n_levels) if level_hwf == "pyramid" else [list(hwf)] * n_levels
+    per_level = []
+    with torch.no_grad():
+        for layer, kw in enumerate(render_kwargs_test_list):
+            H_l, W_l, focal_l = hwfs[layer]
+            rgbs, _ = render_dnerf.render_path(render_poses, render_times, [int(H_l), int(W_l), focal_l], chunk, kw,
+                                               gt_imgs=None if gt_imgs is None else gt_imgs[layer],
+                                               savedir=None if savedir is None else os.path.join(savedir, f'layer_{layer}'))
+            per_level.append(rgbs)
+        dev = _device(None)
+        frames = pyramid.reconstruct_image_from_pyramid_batch(
+            [torch.from_numpy(np.ascontiguousarray(r, dtype=np.float32)).to(dev) for r in per_level]).cpu().numpy()
+    if savedir is not None:
+        os.makedirs(os.path.join(savedir, "estim"), exist_ok=True)
+        for i, f in enumerate(frames):
+            write_png(os.path.join(savedir, "estim", '{:03d}.png'.format(i)), to8b(f))
+    return frames, per_level
 
 
 def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, render_factor=0):
