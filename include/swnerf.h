@@ -489,6 +489,56 @@ int swnerf_pyramid_up_axpy(const float* coarse, int64_t n, int64_t h, int64_t w,
 int swnerf_pyramid_up_adjoint(const float* g_out, int64_t n, int64_t H, int64_t W, int c, int64_t h, int64_t w,
                               float* g_coarse, void* stream);
 
+/* ---- 2-D image fitting (2d_pos_encoding/: encoding.py, model.py, utils.py) ---------------------------------------------
+ * The net: n_layers x (Linear -> ReLU -> BatchNorm1d) at width `hidden`, then Linear(hidden, 3), on encode(pos, L).
+ *
+ * encode2d (encoding.py:22-40): pos [N, 2] -> out [N, 4L + 2] = [x, y, then per band i: sin(a_i x), sin(a_i y), cos(a_i x),
+ *   cos(a_i y)] with (x, y) = 2 * (pos / (max_x, max_y)) - 1 (a correctly rounded fp32 division and two more roundings) and the
+ *   argument fl32(2^i pi) * x as ONE fp32 product; sin / cos by a double-precision argument reduction in every band (max abs
+ *   error 1.2e-7).  0 <= L <= 23; max_x, max_y > 0 (the reference divides by zero for a 1-pixel-wide picture: SWNERF_E_ARG here).
+ *
+ * BatchNorm1d on [M, C] fp32 rows, any C >= 1, with an optional ReLU IN FRONT (relu != 0: x = max(a, 0), and the backward
+ * masks with a > 0).  Column sums are fp64 in a fixed order without atomics: two equal calls give equal bits.
+ *   bn_forward_train  mean and BIASED variance over the M >= 2 rows (M == 1: SWNERF_E_ARG, as torch raises);
+ *                     y = gamma (x - mean) invstd + beta, invstd = 1 / sqrt(var + eps); save_mean / save_invstd [C];
+ *                     running_mean / running_var (both or neither NULL) updated in place:
+ *                     r = (1 - momentum) r + momentum * (mean | var * M / (M - 1)).
+ *   bn_backward       dbeta = sum dy, dgamma = sum dy xhat, dx = gamma invstd / M (M dy - dbeta - xhat dgamma), then the ReLU mask.
+ *   bn_apply          the eval form y = x s + t, s = gamma / sqrt(running_var + eps), t = beta - running_mean s.
+ * ws: DEVICE scratch of bn_workspace_bytes(M, C) bytes (0 up to 512 rows, where one launch does everything; above, the rows
+ * are split over the grid and added in a second fixed-order stage), may be NULL when that is 0.
+ *
+ * fit2d_loss (utils.py:13,56,62-64): out, target [M, 3]; sums (DEVICE double [2]): [0] = mse + reg * mean(max(max(0, x - 1),
+ *   max(-x, 0))), [1] = the grey-scale mse (weights 0.2989 / 0.5870 / 0.1140); grad [M, 3] = d sums[0] / d out (may be NULL).
+ *   One launch, fp64 sums in a fixed order.  At the ties x == 0 and x == 1 the clip term's subgradient is 0 (torch: a quarter).
+ *
+ * pack_fit2d: hidden == 256 only.  params: HOST array of 6 n_layers + 2 DEVICE pointers - per hidden layer the Linear weight
+ *   [256, in] and bias, the BatchNorm1d weight, bias, running_mean, running_var; then the head's weight [3, 256] and bias.
+ *   Every BatchNorm1d is folded into the NEXT Linear: W . diag(s), b + W . t (fp64 product, one rounding; the fold is behind the
+ *   ReLU, so the sign of s needs no care).  packed: fit2d_packed_floats(n_layers) floats = (96 + 256 (n_layers - 1) + 16) * 256
+ *   + (8 n_layers + 25) * 32; 1 <= n_layers <= 64.  Repack whenever a parameter OR a running buffer changes.
+ * fit2d_forward: Model.forward in eval mode on encoded rows x [M, ldx >= 4L + 2] -> out [M, 3].
+ * fit2d_picture: get_picture (utils.py:103-126) - pixel (x, y) of an H x W picture is encoded in registers from its index
+ *   (max_x = W - 1, max_y = H - 1; H, W >= 2) and run through the net; out_f32 [H, W, 3] = clip(., 0, 1) and / or out_u8
+ *   [H, W, 3] = to8b of it (at least one non-NULL).  Nothing is read but the weights.  Both passes: one wave per 32 rows,
+ *   one encoder and one trunk, so the same pixel gives the same bits in both. */
+int swnerf_encode2d(const float* pos, int64_t N, float max_x, float max_y, int L, float* out, void* stream);
+size_t swnerf_bn_workspace_bytes(int64_t M, int C);
+int swnerf_bn_forward_train(const float* a, int64_t M, int C, int relu, const float* gamma, const float* beta, double eps,
+                            double momentum, float* y, float* save_mean, float* save_invstd, float* running_mean /* may be NULL */,
+                            float* running_var /* may be NULL */, void* ws, void* stream);
+int swnerf_bn_backward(const float* dy, const float* a, int64_t M, int C, int relu, const float* gamma, const float* save_mean,
+                       const float* save_invstd, float* dx, float* dgamma, float* dbeta, void* ws, void* stream);
+int swnerf_bn_apply(const float* x, int64_t M, int C, int relu, const float* gamma, const float* beta, const float* running_mean,
+                    const float* running_var, double eps, float* y, void* stream);
+int swnerf_fit2d_loss(const float* out, const float* target, int64_t M, float reg, double* sums, float* grad /* may be NULL */,
+                      void* stream);
+size_t swnerf_fit2d_packed_floats(int n_layers);
+int swnerf_pack_fit2d(const float* const* params /*HOST*/, int n_layers, int L, double eps, float* packed, void* stream);
+int swnerf_fit2d_forward(const float* packed, const float* x, int64_t M, int ldx, int L, int n_layers, float* out, void* stream);
+int swnerf_fit2d_picture(const float* packed, int64_t H, int64_t W, int L, int n_layers, float* out_f32 /* may be NULL */,
+                         unsigned char* out_u8 /* may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

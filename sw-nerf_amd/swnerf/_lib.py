@@ -30,7 +30,9 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_linear_act", "swnerf_elu_grad",
            "swnerf_metrics_workspace_bytes", "swnerf_image_metrics",
            "swnerf_pyramid_down", "swnerf_pyramid_up_axpy", "swnerf_pyramid_up_adjoint",
-           "swnerf_gemm_tn_ordered_ws_floats", "swnerf_gemm_tn_ordered"]
+           "swnerf_gemm_tn_ordered_ws_floats", "swnerf_gemm_tn_ordered",
+           "swnerf_encode2d", "swnerf_bn_workspace_bytes", "swnerf_bn_forward_train", "swnerf_bn_backward", "swnerf_bn_apply",
+           "swnerf_fit2d_loss", "swnerf_fit2d_packed_floats", "swnerf_pack_fit2d", "swnerf_fit2d_forward", "swnerf_fit2d_picture"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -165,10 +167,23 @@ def lib():
     L.swnerf_pyramid_up_axpy.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, ctypes.c_float, c_int64, c_int64,
                                          c_void_p, c_void_p]
     L.swnerf_pyramid_up_adjoint.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p]
+    L.swnerf_encode2d.argtypes = [c_void_p, c_int64, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p]
+    L.swnerf_bn_workspace_bytes.restype = c_size_t
+    L.swnerf_bn_workspace_bytes.argtypes = [c_int64, c_int]
+    L.swnerf_bn_forward_train.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 7
+    L.swnerf_bn_backward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8
+    L.swnerf_bn_apply.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]
+    L.swnerf_fit2d_loss.argtypes = [c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p, c_void_p, c_void_p]
+    L.swnerf_fit2d_packed_floats.restype = c_size_t
+    L.swnerf_fit2d_packed_floats.argtypes = [c_int]
+    L.swnerf_pack_fit2d.argtypes = [POINTER(c_void_p), c_int, c_int, c_double, c_void_p, c_void_p]
+    L.swnerf_fit2d_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.swnerf_fit2d_picture.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
     for name in EXPORTS:
         if name not in ("swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
                         "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",
-                        "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes", "swnerf_gemm_tn_ordered_ws_floats"):
+                        "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes", "swnerf_gemm_tn_ordered_ws_floats",
+                        "swnerf_bn_workspace_bytes", "swnerf_fit2d_packed_floats"):
             getattr(L, name).restype = c_int
     if L.swnerf_version() != 112:
         raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 112 - rebuild it "

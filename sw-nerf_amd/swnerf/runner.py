@@ -151,6 +151,21 @@ def create_tnerf(args, device=None):
     return kw, test, start, grad_vars, optimizer
 
 
+def create_fit2d(args, device=None):
+    """2d_pos_encoding/main.py:19-24: Model(2 + 4 L, layer_num), AdamW(lr 1e-3), ExponentialLR(gamma 0.95); with
+    args.checkpoint_load the model, the optimizer and the starting epoch come from that file (utils.py:15-21, 38-40 - the scheduler
+    restarts, as in the reference).  Returns model, optimizer, scheduler, start epoch, metrics."""
+    from . import fit2d
+    device = _device(device)
+    model = fit2d.Model(input_dimension=2 + 4 * args.L, layer_num=args.layer_num).to(device)
+    optimizer = torch.optim.AdamW(model.parameters(), lr=0.001)
+    scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.95)
+    start, metrics = 0, {"MSE": [], "PSNR": []}
+    if getattr(args, "checkpoint_load", None):
+        start, metrics = fit2d.load_checkpoint(model, optimizer, args)
+    return model, optimizer, scheduler, start, metrics
+
+
 # ---- MultiRes D-NeRF (multires_dnerf/multires_dnerf.py): one DirectTemporalNeRF per Laplacian-pyramid level -------------
 MULTIRES_CHANNELS = [(20, 8, 20), (10, 4, 10), (10, 4, 10), (-1, -1, -1)]      # multires_dnerf.py:665, per level
 

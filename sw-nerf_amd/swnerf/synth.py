@@ -163,3 +163,25 @@ def shard_range(n_total, world_size, rank):
     base, rem = divmod(n_total, world_size)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+def fit2d_state_dict(seed, input_dimension=82, layer_num=10, hidden_dim=256, output_dim=3):
+    """Weights of one 2-D fitting `Model` (2d_pos_encoding/model.py:6-23: layer_num x (Linear, ReLU, BatchNorm1d), then Linear) with
+    every BatchNorm1d far from its defaults - a fresh one is the identity in eval mode and would pin nothing: weight in
+    +-(0.5, 1.5) with about 10 % negative, bias in +-0.3, running_mean in (0, 0.6), running_var in (0.3, 2); Linear biases in +-0.2."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    k = input_dimension
+    for i in range(layer_num):
+        sd[f"model.{3 * i}.weight"] = _he(rng, hidden_dim, k)
+        sd[f"model.{3 * i}.bias"] = rng.uniform(-0.2, 0.2, hidden_dim).astype(np.float32)
+        sign = np.where(rng.random(hidden_dim) < 0.1, -1.0, 1.0)
+        sd[f"model.{3 * i + 2}.weight"] = (sign * rng.uniform(0.5, 1.5, hidden_dim)).astype(np.float32)
+        sd[f"model.{3 * i + 2}.bias"] = rng.uniform(-0.3, 0.3, hidden_dim).astype(np.float32)
+        sd[f"model.{3 * i + 2}.running_mean"] = rng.uniform(0.0, 0.6, hidden_dim).astype(np.float32)
+        sd[f"model.{3 * i + 2}.running_var"] = rng.uniform(0.3, 2.0, hidden_dim).astype(np.float32)
+        sd[f"model.{3 * i + 2}.num_batches_tracked"] = np.array(7, np.int64)
+        k = hidden_dim
+    sd[f"model.{3 * layer_num}.weight"] = _he(rng, output_dim, k)
+    sd[f"model.{3 * layer_num}.bias"] = rng.uniform(-0.2, 0.2, output_dim).astype(np.float32)
+    return sd
