@@ -539,6 +539,38 @@ int swnerf_fit2d_forward(const float* packed, const float* x, int64_t M, int ldx
 int swnerf_fit2d_picture(const float* packed, int64_t H, int64_t W, int L, int n_layers, float* out_f32 /* may be NULL */,
                          unsigned char* out_u8 /* may be NULL */, void* stream);
 
+/* ---- the data side of a training step (nerf/run.py:598-696, d_nerf/run_dnerf.py:648-683; csrc/batch_kernels.hip) -----------
+ * perm_indices: out[i] = perm(key, n, k0 + i), i < count - a keyed bijection of [0, n), 1 <= n < 2^40, any 64-bit key; a batch
+ *   drawn without replacement is its image of a run of consecutive k.  A balanced 6-round Feistel network over the smallest even
+ *   bit-width covering n with cycle walking; integer arithmetic only, defined by swnerf.batching.perm_index_np.
+ *   k0 >= 0, k0 + count <= n (else SWNERF_E_ARG).
+ *
+ * train_batch: ONE launch, 256 rays per workgroup.  Ray i of the batch is pixel id_i of the domain [0, n_train * h * w):
+ *   id_i = perm(key, domain, k0 + i) (k0 + n <= domain), or ids_in[i] when ids_in (DEVICE int64 [n]) is not NULL;
+ *   id -> (slot, y, x) = (id / (h w), y0 + (id % (h w)) / w, x0 + id % w) inside the crop window (y0, x0, h, w) of an H x W image;
+ *   image = i_train[slot] (DEVICE int64 [n_train], values in [0, n_images)).  The pose is c2w[image] (DEVICE [n_images, 3, 4]), the
+ *   ray that of get_rays (fx .. focal_branch as there), the row that of pack_ray_batch: cols = 8 [o d near far], 11 (+ viewdirs,
+ *   taken before the NDC warp) or 12 (+ the frame time times[image], DEVICE [n_images], in column 8).  ndc != 0: the warp of
+ *   pack_ray_batch at ndc_focal.  target [n, 3] = the pixel of images (DEVICE [n_images, H, W, channels], channels 3 or 4,
+ *   float32, or bytes with images_u8 != 0: (float)((double)u / 255.)); with 4 channels and white_bkgd != 0 c * a + (1 - a) in
+ *   float32, each operation rounded.  ids_out (DEVICE int64 [n], may be NULL) receives the ids.  An id outside the domain or an
+ *   i_train value outside [0, n_images) gives a NaN row and a NaN target and reads nothing.
+ *   SWNERF_E_ARG: NULL table, empty window or one outside the image, cols / channels not as above, k0 + n > domain without ids_in.
+ *
+ * photo_loss: rgb, rgb0 (may be NULL), target [N, 3].  sums (DEVICE double [2]) = sum (rgb - target)^2, sum (rgb0 - target)^2
+ *   (0 without rgb0), added in fp64 in a fixed order: equal bits on every run.  losses (DEVICE float [3], may be NULL) =
+ *   [mse + mse0, mse, mse0], each formed in fp64 and rounded once.  d_rgb / d_rgb0 (may be NULL) = d losses[0] / d rgb, rgb0 =
+ *   2 (x - target) / (3 N), formed in fp64 and rounded once.  One launch. */
+int swnerf_perm_indices(uint64_t key, int64_t n, int64_t k0, int64_t count, int64_t* out, void* stream);
+int swnerf_train_batch(const void* images, int images_u8, int channels, int64_t n_images, int H, int W,
+                       const float* c2w, const float* times /* may be NULL unless cols == 12 */, const int64_t* i_train, int64_t n_train,
+                       int y0, int x0, int h, int w, double fx, double fy, double cx, double cy, int focal_branch,
+                       double near, double far, int cols, int ndc, double ndc_focal, int white_bkgd,
+                       uint64_t key, int64_t k0, int64_t n, const int64_t* ids_in /* may be NULL */,
+                       float* ray_batch, float* target, int64_t* ids_out /* may be NULL */, void* stream);
+int swnerf_photo_loss(const float* rgb, const float* rgb0 /* may be NULL */, const float* target, int64_t N, double* sums,
+                      float* losses /* may be NULL */, float* d_rgb /* may be NULL */, float* d_rgb0 /* may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@
 #include "../../include/swnerf.h"
 #include "swnerf_common.h"
 #include "host_util.h"
+#include "ray_rows.h"
 #include "resample.h"
 #include "composite.h"
 
@@ -21,18 +22,12 @@ extern "C" size_t swnerf_packed_floats(int kind) {
 static inline unsigned nblocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // ---- get_rays (ray.py:10-38) ---------------------------------------------------------------
-struct Cam { float fx, fy, cx, cy; float r[9]; float t[3]; };
-
+// the arithmetic of a ray, of the NDC warp and of a batch row: ray_rows.h (shared with batch_kernels.hip)
 __global__ void __launch_bounds__(256) get_rays_kernel(Cam c, int W, int64_t ray0, int64_t n, float* ro, float* rd) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int64_t p = ray0 + i;
-    const float px = (float)(p % W), py = (float)(p / W);        // integer pixel centres, no +0.5
-    const float a = (px - c.cx) / c.fx, b = -(py - c.cy) / c.fy, m = -1.f;
-    // sum(dirs[..., None, :] * c2w[:3,:3], -1): products rounded, then added left to right
-    rd[i * 3 + 0] = a * c.r[0] + b * c.r[1] + m * c.r[2];
-    rd[i * 3 + 1] = a * c.r[3] + b * c.r[4] + m * c.r[5];
-    rd[i * 3 + 2] = a * c.r[6] + b * c.r[7] + m * c.r[8];
+    ray_dir(c, (float)(p % W), (float)(p / W), rd[i * 3 + 0], rd[i * 3 + 1], rd[i * 3 + 2]);
     if (ro) { ro[i * 3 + 0] = c.t[0]; ro[i * 3 + 1] = c.t[1]; ro[i * 3 + 2] = c.t[2]; }
 }
 
@@ -42,24 +37,14 @@ extern "C" int swnerf_get_rays(int H, int W, double fx, double fy, double cx, do
     if (!c2w || !rays_d || H <= 0 || W <= 0 || n < 0 || ray0 < 0 || ray0 + n > (int64_t)H * W)
         return sw_fail(SWNERF_E_ARG, "get_rays: bad arguments (H=%d W=%d ray0=%lld n=%lld)", H, W, (long long)ray0, (long long)n);
     Cam c;
-    if (focal_branch) { c.fx = (float)fx; c.fy = (float)fx; c.cx = (float)(W * 0.5); c.cy = (float)(H * 0.5); }
-    else { c.fx = (float)fx; c.fy = (float)fy; c.cx = (float)cx; c.cy = (float)cy; }
-    for (int i = 0; i < 3; ++i) { for (int k = 0; k < 3; ++k) c.r[i * 3 + k] = c2w[i * 4 + k]; c.t[i] = c2w[i * 4 + 3]; }
+    cam_intrinsics(c, H, W, fx, fy, cx, cy, focal_branch);
+    cam_pose(c, c2w);
     if (n == 0) return 0;
     hipLaunchKernelGGL(get_rays_kernel, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, c, W, ray0, n, rays_o, rays_d);
     return sw_check(hipGetLastError(), "get_rays launch");
 }
 
 // ---- ndc_rays (ray.py:75-92) -----------------------------------------------------------------
-__device__ __forceinline__ void ndc_one(float sx, float sy, float near, float& ox, float& oy, float& oz,
-                                        float& dx, float& dy, float& dz) {
-    const float t = -(near + oz) / dz;
-    ox = ox + t * dx; oy = oy + t * dy; oz = oz + t * dz;
-    const float o0 = sx * ox / oz, o1 = sy * oy / oz, o2 = 1.f + 2.f * near / oz;
-    const float d0 = sx * (dx / dz - ox / oz), d1 = sy * (dy / dz - oy / oz), d2 = -2.f * near / oz;
-    ox = o0; oy = o1; oz = o2; dx = d0; dy = d1; dz = d2;
-}
-
 __global__ void __launch_bounds__(256) ndc_kernel(float sx, float sy, float near, const float* ro, const float* rd,
                                                   int64_t n, float* oo, float* od) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -69,9 +54,6 @@ __global__ void __launch_bounds__(256) ndc_kernel(float sx, float sy, float near
     oo[i * 3] = ox; oo[i * 3 + 1] = oy; oo[i * 3 + 2] = oz;
     od[i * 3] = dx; od[i * 3 + 1] = dy; od[i * 3 + 2] = dz;
 }
-
-// the python scalars -1./(W/(2.*focal)) are evaluated in double and then cast (ray.py:81-86)
-static inline float ndc_scale(int WH, double focal) { return (float)(-1. / (WH / (2. * focal))); }
 
 extern "C" int swnerf_ndc_rays(int H, int W, double focal, double near, const float* rays_o, const float* rays_d,
                                int64_t n, float* o_out, float* d_out, void* stream) {
@@ -83,34 +65,19 @@ extern "C" int swnerf_ndc_rays(int H, int W, double focal, double near, const fl
 }
 
 // ---- ray batch packing (nerf/run.py:137-158, d_nerf/run_dnerf.py:137-160) ----------------------
-// A block packs 256 rays: the 11- / 12-float rows are assembled in LDS and leave as 16-byte stores of the block's
-// contiguous 11 / 12 KiB of the batch (a row-per-thread store pattern writes 11 dwords at a 44-byte stride: every store
-// instruction touches 22 lines for 256 useful bytes).  The last, partial block stores dword-wise.
+// A block packs 256 rays: the 11- / 12-float rows are assembled in LDS (pack_row) and leave as 16-byte stores
+// (rows_to_global, ray_rows.h).
 __global__ void __launch_bounds__(256) pack_rays_kernel(const float* ro, const float* rd, int64_t n, float near, float far,
                                                         int has_time, float ft, int ndc, float sx, float sy, float* out) {
     __shared__ __attribute__((aligned(16))) float rows[256 * 12];
     const int t = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * 256, i = i0 + t;
     const int cols = has_time ? 12 : 11;
-    if (i < n) {
-        float ox = ro[i * 3], oy = ro[i * 3 + 1], oz = ro[i * 3 + 2], dx = rd[i * 3], dy = rd[i * 3 + 1], dz = rd[i * 3 + 2];
-        const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float v0 = dx / nrm, v1 = dy / nrm, v2 = dz / nrm;     // viewdirs BEFORE the NDC warp
-        if (ndc) ndc_one(sx, sy, 1.f, ox, oy, oz, dx, dy, dz);       // caller hard-wires near=1. (nerf/run.py:149)
-        float* o = rows + t * cols;
-        o[0] = ox; o[1] = oy; o[2] = oz; o[3] = dx; o[4] = dy; o[5] = dz; o[6] = near; o[7] = far;
-        int k = 8;
-        if (has_time) o[k++] = ft;
-        o[k] = v0; o[k + 1] = v1; o[k + 2] = v2;
-    }
+    if (i < n)
+        pack_row(rows + t * cols, cols, ro[i * 3], ro[i * 3 + 1], ro[i * 3 + 2], rd[i * 3], rd[i * 3 + 1], rd[i * 3 + 2],
+                 near, far, ft, ndc, sx, sy);
     __syncthreads();
-    float* dst = out + i0 * cols;                                     // 256 * cols * 4 bytes per block: 16-byte aligned when `out` is
-    const int live = (int)min((int64_t)256, n - i0) * cols;
-    if (live == 256 * cols && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
-        for (int q = t; q < 64 * cols; q += 256) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(rows)[q];
-    } else {
-        for (int q = t; q < live; q += 256) dst[q] = rows[q];
-    }
+    rows_to_global(rows, out, i0, n, cols, t);
 }
 
 extern "C" int swnerf_pack_ray_batch(const float* rays_o, const float* rays_d, int64_t n, double near, double far,

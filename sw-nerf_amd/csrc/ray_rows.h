@@ -1,0 +1,67 @@
+// ray_rows.h - the per-pixel ray arithmetic of get_rays (ray.py:10-38), the NDC warp (ray.py:75-92) and the assembly of one
+// ray-batch row [o d near far (t) (viewdirs)] (nerf/run.py:137-158, d_nerf/run_dnerf.py:137-160), written once: the standalone
+// kernels of misc_kernels.hip and the training-batch kernel of batch_kernels.hip are the same instructions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+struct Cam { float fx, fy, cx, cy; float r[9]; float t[3]; };
+
+// intrinsics as get_rays casts them: the focal branch (a Python float) centres at W/2, H/2 evaluated in double
+static inline void cam_intrinsics(Cam& c, int H, int W, double fx, double fy, double cx, double cy, int focal_branch) {
+    if (focal_branch) { c.fx = (float)fx; c.fy = (float)fx; c.cx = (float)(W * 0.5); c.cy = (float)(H * 0.5); }
+    else { c.fx = (float)fx; c.fy = (float)fy; c.cx = (float)cx; c.cy = (float)cy; }
+}
+
+// c2w: a [3,4] row-major pose (host or device memory, whichever side calls)
+__host__ __device__ __forceinline__ void cam_pose(Cam& c, const float* c2w) {
+    for (int i = 0; i < 3; ++i) { for (int k = 0; k < 3; ++k) c.r[i * 3 + k] = c2w[i * 4 + k]; c.t[i] = c2w[i * 4 + 3]; }
+}
+
+// direction of the ray through the integer pixel centre (px, py), no +0.5
+__device__ __forceinline__ void ray_dir(const Cam& c, float px, float py, float& d0, float& d1, float& d2) {
+    const float a = (px - c.cx) / c.fx, b = -(py - c.cy) / c.fy, m = -1.f;
+    // sum(dirs[..., None, :] * c2w[:3,:3], -1): products rounded, then added left to right
+    d0 = a * c.r[0] + b * c.r[1] + m * c.r[2];
+    d1 = a * c.r[3] + b * c.r[4] + m * c.r[5];
+    d2 = a * c.r[6] + b * c.r[7] + m * c.r[8];
+}
+
+__device__ __forceinline__ void ndc_one(float sx, float sy, float near, float& ox, float& oy, float& oz,
+                                        float& dx, float& dy, float& dz) {
+    const float t = -(near + oz) / dz;
+    ox = ox + t * dx; oy = oy + t * dy; oz = oz + t * dz;
+    const float o0 = sx * ox / oz, o1 = sy * oy / oz, o2 = 1.f + 2.f * near / oz;
+    const float d0 = sx * (dx / dz - ox / oz), d1 = sy * (dy / dz - oy / oz), d2 = -2.f * near / oz;
+    ox = o0; oy = o1; oz = o2; dx = d0; dy = d1; dz = d2;
+}
+
+// the python scalars -1./(W/(2.*focal)) are evaluated in double and then cast (ray.py:81-86)
+static inline float ndc_scale(int WH, double focal) { return (float)(-1. / (WH / (2. * focal))); }
+
+// one row of `cols` floats: 8 = [o d near far], 11 = ... viewdirs, 12 = ... t viewdirs
+__device__ __forceinline__ void pack_row(float* o, int cols, float ox, float oy, float oz, float dx, float dy, float dz,
+                                         float near, float far, float ft, int ndc, float sx, float sy) {
+    const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float v0 = dx / nrm, v1 = dy / nrm, v2 = dz / nrm;     // viewdirs BEFORE the NDC warp
+    if (ndc) ndc_one(sx, sy, 1.f, ox, oy, oz, dx, dy, dz);       // caller hard-wires near=1. (nerf/run.py:149)
+    o[0] = ox; o[1] = oy; o[2] = oz; o[3] = dx; o[4] = dy; o[5] = dz; o[6] = near; o[7] = far;
+    if (cols == 8) return;
+    int k = 8;
+    if (cols == 12) o[k++] = ft;
+    o[k] = v0; o[k + 1] = v1; o[k + 2] = v2;
+}
+
+// A block's 256 rows, assembled in LDS, leave as 16-byte stores of the block's contiguous 256 * cols floats of the batch (a
+// row-per-thread store pattern writes `cols` dwords at a 4 * cols-byte stride: every store instruction touches 22 lines for
+// 256 useful bytes).  The last, partial block - and an `out` that is not 16-byte aligned - stores dword-wise.  Call after
+// __syncthreads().
+__device__ __forceinline__ void rows_to_global(const float* rows, float* out, int64_t i0, int64_t n, int cols, int t) {
+    float* dst = out + i0 * cols;                                     // 256 * cols * 4 bytes per block: 16-byte aligned when `out` is
+    const int live = (int)min((int64_t)256, n - i0) * cols;
+    if (live == 256 * cols && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        for (int q = t; q < 64 * cols; q += 256) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(rows)[q];
+    } else {
+        for (int q = t; q < live; q += 256) dst[q] = rows[q];
+    }
+}

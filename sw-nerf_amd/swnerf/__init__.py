@@ -3,4 +3,4 @@ daihangpku/SW-NeRF (get_rays / ndc_rays / sample_pdf / raw2outputs / Embedder /
 NeRF MLPs / run_network / render_rays / render).  See DESIGN.md and INTEGRATION.md."""
 from . import synth  # noqa: F401  (numpy only)
 
-__all__ = ["synth", "ray", "embedder", "model", "render", "pyramid", "runner", "fit2d"]
+__all__ = ["synth", "ray", "embedder", "model", "render", "pyramid", "runner", "fit2d", "batching"]

@@ -32,7 +32,8 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_pyramid_down", "swnerf_pyramid_up_axpy", "swnerf_pyramid_up_adjoint",
            "swnerf_gemm_tn_ordered_ws_floats", "swnerf_gemm_tn_ordered",
            "swnerf_encode2d", "swnerf_bn_workspace_bytes", "swnerf_bn_forward_train", "swnerf_bn_backward", "swnerf_bn_apply",
-           "swnerf_fit2d_loss", "swnerf_fit2d_packed_floats", "swnerf_pack_fit2d", "swnerf_fit2d_forward", "swnerf_fit2d_picture"]
+           "swnerf_fit2d_loss", "swnerf_fit2d_packed_floats", "swnerf_pack_fit2d", "swnerf_fit2d_forward", "swnerf_fit2d_picture",
+           "swnerf_perm_indices", "swnerf_train_batch", "swnerf_photo_loss"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -179,6 +180,11 @@ def lib():
     L.swnerf_pack_fit2d.argtypes = [POINTER(c_void_p), c_int, c_int, c_double, c_void_p, c_void_p]
     L.swnerf_fit2d_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]
     L.swnerf_fit2d_picture.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.swnerf_perm_indices.argtypes = [ctypes.c_uint64, c_int64, c_int64, c_int64, c_void_p, c_void_p]
+    L.swnerf_train_batch.argtypes = ([c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                      c_double, c_double, c_double, c_double, c_int, c_double, c_double, c_int, c_int, c_double, c_int,
+                                      ctypes.c_uint64, c_int64, c_int64, c_void_p] + [c_void_p] * 4)
+    L.swnerf_photo_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_void_p] * 5
     for name in EXPORTS:
         if name not in ("swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
                         "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",

@@ -5,7 +5,9 @@ written against the reference only swaps its imports.  `args` is any object with
 (utils.py config_parser / run_dnerf.py config_parser); the closure is built inside the function, which is how
 `render.fused_plan` finds the encoders and sends `render_rays` to the fused HIP pass.
 `render_test` and `evaluate_dir` are what follows the render path: the reference's scoring of test renders
-(nerf/run.py:557-596 with calculate_metrics :49-61, and the last cell of d_nerf/metrics.ipynb) on the GPU metrics."""
+(nerf/run.py:557-596 with calculate_metrics :49-61, and the last cell of d_nerf/metrics.ipynb) on the GPU metrics.
+`train` and `train_dnerf` are the two runners' training loops from `create_nerf` on, with the batch and the loss made on the
+device (swnerf.batching)."""
 import json
 import os
 import random
@@ -387,3 +389,239 @@ def evaluate_dir(files_dir):
     with open(os.path.join(files_dir, "metrics.txt"), "w") as f:
         f.write(str(errors))
     return errors
+
+
+# ---- train() of the two runners (nerf/run.py:598-796, d_nerf/run_dnerf.py:596-820) ---------------------------------------
+_RENDER_ONLY_KEYS = ('ndc', 'near', 'far', 'use_viewdirs', 'c2w_staticcam')      # what render() consumes before render_rays
+
+
+def _train_data(data, with_times):
+    """The loaders' tuple (images, poses, render_poses, hwf, i_split[, times]) + (near, far), or a dict with those names
+    (and optionally 'K')."""
+    if isinstance(data, dict):
+        d = dict(data)
+    else:
+        names = ['images', 'poses', 'render_poses', 'hwf', 'i_split'] + (['times'] if len(data) == 8 else []) + ['near', 'far']
+        if len(data) != len(names):
+            raise ValueError(f"swnerf.runner.train: data must be (images, poses, render_poses, hwf, i_split[, times], near, far), got {len(data)} entries")
+        d = dict(zip(names, data))
+    if with_times and d.get('times') is None:
+        raise ValueError("swnerf.runner.train_dnerf: data carries no frame times")
+    H, W, focal = d['hwf']
+    d['hwf'] = [int(H), int(W), float(focal)]
+    if d.get('K') is None:                                                       # nerf/run.py:518-523
+        d['K'] = np.array([[float(focal), 0, 0.5 * int(W)], [0, float(focal), 0.5 * int(H)], [0, 0, 1]])
+    return d
+
+
+def _gt_rgb(images, idx, white_bkgd):
+    """images[idx] as the reference holds them after loading: float32 RGB (bytes / 255., RGBA composited on white or cut)."""
+    im = torch.as_tensor(images)[torch.as_tensor(np.asarray(idx, dtype=np.int64))].cpu().numpy()
+    if im.dtype == np.uint8:
+        im = (im / 255.).astype(np.float32)
+    if im.shape[-1] == 4:
+        im = im[..., :3] * im[..., -1:] + (1. - im[..., -1:]) if white_bkgd else im[..., :3]
+    return im
+
+
+class _Record:
+    """Per-step loss / psnr / lr.  The losses stay on the device until `flush` (one transfer per i_print steps, no sync per step)."""
+
+    def __init__(self):
+        self.steps, self._pending = [], []
+
+    def add(self, i, loss, img_loss, lr):
+        self._pending.append((i, loss.detach(), img_loss.detach(), lr))
+
+    def flush(self):
+        if self._pending:
+            from .embedder import mse2psnr
+            loss = torch.stack([p[1] for p in self._pending]).reshape(-1)
+            mse = torch.stack([p[2] for p in self._pending]).reshape(-1)
+            loss, psnr = loss.cpu().tolist(), mse2psnr(mse).cpu().tolist()
+            for (i, _, _, lr), l, p in zip(self._pending, loss, psnr):
+                self.steps.append({'step': i, 'loss': l, 'psnr': p, 'lr': lr})
+            self._pending = []
+        return self.steps
+
+
+def _opt(args, name, default):
+    return getattr(args, name, default)
+
+
+def _train_common(args, d, device, sampler, loss_fn, dnerf):
+    from . import batching
+    if sampler not in ("device", "numpy"):
+        raise ValueError(f"swnerf.runner.train: sampler must be 'device' or 'numpy', got {sampler!r}")
+    device = _device(device)
+    create = create_dnerf if dnerf else create_nerf
+    train_kw, test_kw, start, grad_vars, optimizer = create(args, device=device)
+    bds = {'near': d['near'], 'far': d['far']}
+    train_kw.update(bds)
+    test_kw.update(bds)
+    i_train = np.asarray(d['i_split'][0]).reshape(-1)
+    batcher = batching.RayBatcher(d['images'], d['poses'], d['hwf'] if dnerf else d['K'],        # the runners' own get_rays calls: focal there, K here
+                                  i_train, d['near'], d['far'], times=d.get('times') if dnerf else None,
+                                  ndc=train_kw.get('ndc', True), use_viewdirs=train_kw['use_viewdirs'], white_bkgd=args.white_bkgd,
+                                  seed=_opt(args, 'seed', 0), device=device)
+    rays_kw = {k: v for k, v in train_kw.items() if k not in _RENDER_ONLY_KEYS}
+    return device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, (loss_fn or batching.photometric_loss)
+
+
+def _image_draw(args, batcher, i, img_i, sampler, N_rand):
+    """One `no_batching` batch of image img_i at iteration i (nerf/run.py:659-681)."""
+    from . import batching
+    crop = batching.precrop_crop(batcher.H, batcher.W, args.precrop_frac) if i < _opt(args, 'precrop_iters', 0) else None
+    ids = None
+    if sampler == "numpy":
+        n_px = batcher.H * batcher.W if crop is None else crop[2] * crop[3]
+        ids = np.random.choice(n_px, size=[N_rand], replace=False)
+    return batcher.image_batch(img_i, N_rand, i, crop=crop, ids=ids, return_ids=True)
+
+
+def _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks):
+    """lr decay, checkpoint, print - the part of an iteration both runners share (nerf/run.py:702-753)."""
+    from .batching import lr_at
+    new_lrate = lr_at(args.lrate, args.lrate_decay, global_step)
+    for param_group in optimizer.param_groups:
+        param_group['lr'] = new_lrate
+    record.add(i, loss, img_loss, new_lrate)
+    if i % _opt(args, 'i_weights', 10000) == 0:
+        from .checkpoint import save_checkpoint
+        path = save_checkpoint(args.basedir, args.expname, i, global_step, train_kw['network_fn'], train_kw['network_fine'], optimizer)
+        print('Saved checkpoints at', path)
+    if i % _opt(args, 'i_print', 100) == 0:
+        last = record.flush()[-1]
+        print(f"[TRAIN] Iter: {i} Loss: {last['loss']}  PSNR: {last['psnr']}")
+    if hooks and 'on_step' in hooks:
+        hooks['on_step'](i, optimizer)
+
+
+def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
+    """The training loop of nerf/run.py:598-796 from `create_nerf` on: a batch from swnerf.batching.RayBatcher (use_batching
+    over all training rays, or no_batching from one image with the precrop window), the render of the PACKED batch
+    (render.batchify_rays + image_outputs, retraw=True), loss, backward, Adam, the lr decay, a checkpoint every i_weights, a
+    print every i_print, render_test every i_testset.  Video, TensorBoard and the config file are not written.
+
+    args: the reference's option names (N_rand, no_batching, precrop_iters, precrop_frac, chunk, lrate, lrate_decay, i_print,
+    i_weights, i_testset, ...; N_iters - extra, default 200000 - is the last iteration; seed - extra, default 0 - keys the
+    device sampler).  data: (images, poses, render_poses, hwf, i_split, near, far) or a dict with those names (+ 'K').
+    sampler: "device" draws the pixels on the GPU with the keyed permutation; "numpy" draws np.random.choice(..., replace=False)
+    on the host as the reference does and hands the indices to the same kernel - the reference's random stream and rays.
+    loss_fn(rgb, target, rgb0) -> (loss, img_loss, img_loss0): default batching.photometric_loss.
+    hooks: {'on_batch': f(i, img_i, ray_batch, target, ids), 'on_step': f(i, optimizer)}.
+    -> the per-step record: a list of {'step', 'loss', 'psnr', 'lr'}."""
+    d = _train_data(data, False)
+    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, False)
+    H, W, focal = d['hwf']
+    N_rand = args.N_rand
+    use_batching = not args.no_batching
+    N_iters = _opt(args, 'N_iters', 200000) + 1
+    global_step = start
+    record = _Record()
+    for i in range(start + 1, N_iters):
+        if use_batching:
+            img_i = None
+            ray_batch, target_s, ids = batcher.global_batch(N_rand, return_ids=True)
+        else:
+            img_i = np.random.choice(i_train)
+            ray_batch, target_s, ids = _image_draw(args, batcher, i, img_i, sampler, N_rand)
+        if hooks and 'on_batch' in hooks:
+            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
+        all_ret = render.batchify_rays(ray_batch, _opt(args, 'chunk', 1024 * 32), retraw=True, **rays_kw)
+        rgb, disp, acc, extras = render.image_outputs(all_ret, (ray_batch.shape[0], 3))
+        optimizer.zero_grad()
+        loss, img_loss, img_loss0 = loss_fn(rgb, target_s, extras.get('rgb0'))
+        loss.backward()
+        optimizer.step()
+        _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks)
+        i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
+        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
+            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
+            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
+            with torch.no_grad():
+                render_test(poses_test, d['hwf'], d['K'], _opt(args, 'chunk', 1024 * 32), test_kw,
+                            _gt_rgb(d['images'], i_test, args.white_bkgd), testsavedir)
+            print('Saved test set')
+        global_step += 1
+    return record.flush()
+
+
+def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
+    """The training loop of d_nerf/run_dnerf.py:596-820 from `create_nerf` on; as `train`, plus the time curriculum
+    precrop_iters_time (:650-655), the frame time of the drawn image in column 8 of the batch (read from the device table by the
+    batch kernel) and, with add_tv_loss, the TV loss of :690-725: a second render of the SAME rays on extras['z_vals'].detach()
+    at a random time between the frame and its previous / next one.  use_batching raises NotImplementedError, as the reference.
+    data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  args.N_iter is the last iteration.
+    hooks: those of `train`, and 'on_tv': f(i, which, ray_batch_other, z_vals) before each prev / next render."""
+    d = _train_data(data, True)
+    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, True)
+    N_rand = args.N_rand
+    if not args.no_batching:
+        raise NotImplementedError("Time not implemented")                        # run_dnerf.py:634
+    N_iters = _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)) + 1
+    times = batcher.times_host
+    chunk = _opt(args, 'chunk', 1024 * 32)
+    add_tv = bool(_opt(args, 'add_tv_loss', False))
+    from .batching import time_curriculum_max
+
+    def render_packed(rb, t_host, **more):
+        # the frame time is known here as the kernels read it (float32): no device->host read per chunk (render_dnerf._TIME_HINT)
+        token = render_dnerf._TIME_HINT.set((rb.untyped_storage().data_ptr(), float(t_host)))
+        try:
+            all_ret = render_dnerf.batchify_rays(rb, chunk, retraw=True, **more, **rays_kw)
+        finally:
+            render_dnerf._TIME_HINT.reset(token)
+        return render.image_outputs(all_ret, (rb.shape[0], 3))
+
+    global_step = start
+    record = _Record()
+    for i in range(start + 1, N_iters):
+        max_sample = time_curriculum_max(i, _opt(args, 'precrop_iters_time', 0), len(i_train))
+        img_i = np.random.choice(i_train if max_sample is None else i_train[:max_sample])
+        ray_batch, target_s, ids = _image_draw(args, batcher, i, img_i, sampler, N_rand)
+        frame_time = times[img_i]
+        if hooks and 'on_batch' in hooks:
+            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
+        rgb, disp, acc, extras = render_packed(ray_batch, frame_time)
+        others = []
+        if add_tv:
+            frame_time_prev = times[img_i - 1] if img_i > 0 else None
+            frame_time_next = times[img_i + 1] if img_i < times.shape[0] - 1 else None
+            if frame_time_prev is not None and frame_time_next is not None:
+                if np.random.rand() > .5:
+                    frame_time_prev = None
+                else:
+                    frame_time_next = None
+            for which, other in (('prev', frame_time_prev), ('next', frame_time_next)):
+                if other is None:
+                    continue
+                u = np.float32(torch.rand(1)[0].item())
+                rand_time = other + (frame_time - other) * u if which == 'prev' else frame_time + (other - frame_time) * u
+                rb_other = batcher.with_time(ray_batch, float(rand_time))
+                z = extras['z_vals'].detach()
+                if hooks and 'on_tv' in hooks:
+                    hooks['on_tv'](i, which, rb_other, z)
+                others.append(render_packed(rb_other, np.float32(rand_time), z_vals=z)[3])
+        optimizer.zero_grad()
+        loss, img_loss, img_loss0 = loss_fn(rgb, target_s, extras.get('rgb0'))
+        if add_tv:
+            tv_loss = 0
+            for ex in others:
+                tv_loss = tv_loss + ((extras['position_delta'] - ex['position_delta']).pow(2)).sum()
+                if 'position_delta_0' in extras:
+                    tv_loss = tv_loss + ((extras['position_delta_0'] - ex['position_delta_0']).pow(2)).sum()
+            loss = loss + tv_loss * args.tv_loss_weight
+        loss.backward()
+        optimizer.step()
+        _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks)
+        i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
+        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
+            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
+            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
+            with torch.no_grad():
+                render_dnerf.render_path(poses_test, torch.as_tensor(times[i_test]).to(device), d['hwf'], chunk, test_kw,
+                                         gt_imgs=_gt_rgb(d['images'], i_test, args.white_bkgd), savedir=testsavedir)
+            print('Saved test set')
+        global_step += 1
+    return record.flush()
