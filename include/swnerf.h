@@ -414,6 +414,48 @@ int swnerf_deform_narrow_grads(const float* grad_d, int ldg, const float* act_d,
 /* ... for xs_d: slots 64..95 hold gamma(t) (L_time bands) instead of gamma(d) */
 int swnerf_unslot_grad_time(const float* Cs, int ld_s, int rows_w, int nslots, int L_time, float* W, int ldw, int col0, void* stream);
 
+/* ---- the fused T-NeRF pass under autograd (TNeRF, model.py:152-210; the step of t_nerf/run_tnerf.py:646-720) ----------------
+ * SWNERF_NET_TNERF, 12-column ray batch, 2 <= n_samples <= 256, no resampling.  swnerf_render_pass_train refuses this kind (its
+ * saved buffers are the 8 x 256 nets'); this pair is the T-NeRF counterpart.
+ *
+ * render_pass_train_tnerf: exactly swnerf_render_pass with kind SWNERF_NET_TNERF (same arithmetic, bit-equal outputs) and
+ * additionally saves, per padded row (rows = swnerf_train_rows(N, S), the row rule above):
+ *   act [rows, swnerf_tnerf_act_floats_per_row() = 1088]  post-ELU h_l at column 128*l (l = 0..7), the layer_9 hidden at 1024.
+ *                                                         ELU' needs y itself (1 for y > 0, y + 1 otherwise), so no bit masks.
+ *   xs  [rows, swnerf_tnerf_xs_floats_per_row() = 128]    the encodings in the kernel's operand slot order: gamma(x) slots 0..63,
+ *                                                         gamma(t) 64..95, gamma(d) 96..127 (the ray's tiles repeated in every row
+ *                                                         of the ray: the weight-gradient GEMMs run over rows)
+ * args->raw and the depths (args->z_vals given, or args->z_out) are required.  act, xs and raw 16-byte aligned.
+ *
+ * pack_net_bwd_tnerf: the transposed stream of the dX chain (params as for swnerf_pack_net(SWNERF_NET_TNERF)): the folded layer_9
+ * W9f^T, layers.7 .. layers.1 (layer 5: its h4 columns), density.weight and color.weight rows; swnerf_packed_bwd_tnerf_floats()
+ * floats.
+ *
+ * render_pass_backward_tnerf: gradients of (rgb_map, disp_map, acc_map) and g_raw = the upstream gradient of the returned raw
+ * (retraw=True), each NULL or given -> d_raw [rows, 4] = [d(pre-ReLU colour)(3), d sigma] (padded rows; zeros past S; the colour
+ * head's ReLU mask comes from raw) and grad [rows, act floats] = d(pre-activation) of every layer in the layout of act.  One
+ * wavefront per ray: compositing backward in the wave's LDS slice, then the dX chain tile by tile, the saved activations fetched
+ * one layer ahead through LDS.  cols must be 12; z_vals [N,S]: the depths the forward used; noise as in the forward.
+ *
+ * tnerf_feature_finish: `feature` is folded into layer_9 in both kernels.  From G [64,128] = sum_rows d pre_9 (x) h7, db9 [64] and
+ * the CURRENT weights this adds
+ *   dW9[u][o] += sum_i G[u][i] Wf[o][i] + db9[u] bf[o]      (d layer_9.weight[:, :128]; W9 / dW9: [64, ld >= 128])
+ *   dWf[o][i] += sum_u W9[u][o] G[u][i],   dbf[o] += sum_u W9[u][o] db9[u]      (d feature.weight / .bias)
+ *   dW_density[i] += a4w[3][i],  db_density += a4b[3]      (density from the 4-row form: a4w [4,128] = d_raw^T . h7, a4b [4]) */
+size_t swnerf_tnerf_act_floats_per_row(void);
+size_t swnerf_tnerf_xs_floats_per_row(void);
+int swnerf_render_pass_train_tnerf(const swnerf_pass_args* args /*HOST*/, float* act, float* xs, void* stream);
+size_t swnerf_packed_bwd_tnerf_floats(void);
+int swnerf_pack_net_bwd_tnerf(const float* const* params /*HOST*/, int L_pos, int L_dir, int L_time, float* packed_bwd, void* stream);
+int swnerf_render_pass_backward_tnerf(const float* packed_bwd, const float* act, const float* raw /*[N,S,4]*/,
+                                      const float* z_vals /*[N,S]*/, const float* ray_batch, int cols, const float* noise,
+                                      int64_t n_rays, int n_samples, int white_bkgd, const float* g_rgb /*[N,3]*/,
+                                      const float* g_disp /*[N]*/, const float* g_acc /*[N]*/, const float* g_raw /*[N,S,4] or NULL*/,
+                                      float* grad, float* d_raw, void* stream);
+int swnerf_tnerf_feature_finish(const float* G, const float* db9, const float* W9, int ld9, const float* Wf, const float* bf,
+                                const float* a4w, const float* a4b, float* dW9, int ld_dw9, float* dWf, float* dbf,
+                                float* dW_density, float* db_density, void* stream);
+
 /* ---- any-shape MLP layers (model.py:10-62, 93-151, 227-296 at shapes the fused kernels are not built for:
  * use_viewdirs=False - the reference's argparse default, utils.py:26-29 / model.py:59-60 -, other D / W / skips) -------
  * linear   : y[M,N] = act(x[M,K] . weight[N,K]^T + bias)   torch.nn.functional.linear (+ relu if relu != 0); bias may be NULL

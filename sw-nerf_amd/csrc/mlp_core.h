@@ -121,9 +121,21 @@ struct SideStore {
     float* mp; f32x4 mv;
 };
 
-template <int S, int NS, int NT, int KT, int INIT, int SK>
+// Side fetches (the T-NeRF backward chain): while a segment runs, FK tiles of a row-major [M, ld] buffer - the activations the
+// NEXT step of the chain needs - are pulled into an LDS slot by LDS-DMA, ONE 1-KiB step every few weight steps, right behind a
+// step's weight DMA: chunk c = 4n + g (16 bytes per lane: floats 32n + 8g .. + 3 from this lane's row base) -> slot + c KiB.
+// Issued as a burst in front of the segment the same DMAs stall it: `vmcnt` retires in order, so the first counted waits sit
+// behind every one of them (a full HBM round trip per layer with one wave per SIMD).  Spread out, each is one more op in the
+// queue, as a side store is.  The last one goes out at least SW_RING steps before the segment ends, so that every fetch has
+// been retired by a counted wait of THIS segment and the slot may be read right behind it.
+// base: wave-uniform (the tile's first row + the column), voff: this lane's byte offset, lds_addr: the slot.
+struct SideFetch {
+    const char* base; unsigned voff, lds_addr;
+};
+
+template <int S, int NS, int NT, int KT, int INIT, int SK, int FK = 0>
 __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)[KT], WStream& ws, f32x16& binit, float scale,
-                                          const SideStore& ss) {
+                                          const SideStore& ss, const SideFetch& sf = SideFetch{nullptr, 0u, 0u}) {
     if constexpr (S < NS) {
         constexpr int n = S / (KT * 4), kt = (S / 4) % KT, q = S % 4;
         constexpr int slot = S % SW_RING, nslot = (S + 1) % SW_RING;
@@ -166,8 +178,16 @@ __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)
             }
             __builtin_amdgcn_sched_barrier(0);   // the store stays HERE, not bunched up by the scheduler
         }
+        if constexpr (FK > 0) {
+            constexpr int ftotal = 4 * FK, fevery = (NS - SW_RING) / ftotal;
+            static_assert(fevery >= 1, "segment too short for its side fetches");
+            if constexpr (S % fevery == 0 && S / fevery < ftotal) {
+                constexpr int c = S / fevery;
+                ws_dma(sf.base + (32 * (c >> 2) + 8 * (c & 3)) * 4, sf.voff, sf.lds_addr + c * 1024);
+            }
+        }
         ws.a_cur = a_next;
-        seg_steps<S + 1, NS, NT, KT, INIT, SK>(out, kin, ws, binit, scale, ss);
+        seg_steps<S + 1, NS, NT, KT, INIT, SK, FK>(out, kin, ws, binit, scale, ss, sf);
     }
 }
 
@@ -176,14 +196,16 @@ __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)
 //   SEG_ACC (false) keep accumulating | SEG_BIAS (true) the bias tile (so no separate bias pass) |
 //   SEG_ZERO zeros | SEG_BIAS_SCALED the bias tile times a per-lane scalar (backward: w_alpha * d sigma)
 // SK > 0: the first SK k-tiles of `kin` are written out through `ss` while the segment runs (SideStore).
-template <int NT, int KT, int INIT, int SK = 0>
+// FK > 0: FK tiles are fetched into an LDS slot through `sf` while the segment runs (SideFetch).
+template <int NT, int KT, int INIT, int SK = 0, int FK = 0>
 __device__ __forceinline__ void seg_mfma(f32x16 (&out)[NT], const f32x16 (&kin)[KT], WStream& ws, float scale = 1.f,
-                                         const SideStore& ss = SideStore{nullptr, nullptr, {0.f, 0.f, 0.f, 0.f}}) {
+                                         const SideStore& ss = SideStore{nullptr, nullptr, {0.f, 0.f, 0.f, 0.f}},
+                                         const SideFetch& sf = SideFetch{nullptr, 0u, 0u}) {
     constexpr int NS = NT * KT * 4;
     static_assert(NS % SW_RING == 0, "segment must keep the ring phase");
     f32x16 binit;
     seg_init_read<INIT>(binit, ws, 0);
-    seg_steps<0, NS, NT, KT, INIT, SK>(out, kin, ws, binit, scale, ss);
+    seg_steps<0, NS, NT, KT, INIT, SK, FK>(out, kin, ws, binit, scale, ss, sf);
     if (INIT == SEG_BIAS || INIT == SEG_BIAS_SCALED) ws.bias += NT * SW_BIAS_TILE_FLOATS;
     ws.base += NS * 1024;
 }

@@ -311,6 +311,33 @@ static int pack_tnerf(const float* const* params, int L_pos, int L_dir, int L_ti
     return pk.flush();
 }
 
+// The dX chain's stream of the fused T-NeRF backward (tnerf_train_kernels.hip; swnerf_common.h SW_TN_BWD_*): W9f^T from the fold
+// (recomputed into this blob's scratch behind the bias-style tiles), layers.7 .. layers.1 transposed (layer 5: its h4 columns), then
+// density.weight and color.weight rows as bias-style tiles.  params as swnerf_pack_net(SWNERF_NET_TNERF).
+extern "C" size_t swnerf_packed_bwd_tnerf_floats(void) { return (size_t)SW_TN_BWD_FLOATS; }
+extern "C" int swnerf_pack_net_bwd_tnerf(const float* const* params, int L_pos, int L_dir, int L_time, float* packed_bwd, void* stream) {
+    if (!params || !packed_bwd) return sw_fail(SWNERF_E_ARG, "pack_net_bwd_tnerf: NULL pointer");
+    if (L_pos < 0 || L_pos > 10 || L_dir < 1 || L_dir > 4 || L_time < 0 || L_time > 10)
+        return sw_fail(SWNERF_E_UNSUPP, "pack_net_bwd_tnerf: T-NeRF embedder bands (%d,%d,%d) outside (0..10, 1..4, 0..10)", L_pos, L_dir, L_time);
+    for (int i = 0; i < 24; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net_bwd_tnerf: params[%d] is NULL", i);
+    const int Cdir = 3 * (1 + 2 * L_dir), Cin = 3 * (1 + 2 * L_pos) + 1 + 2 * L_time;
+    hipStream_t st = (hipStream_t)stream;
+    float* fold = packed_bwd + SW_TN_BWD_W_FLOATS + SW_TN_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS;
+    hipLaunchKernelGGL(fold_tnerf_kernel, dim3(64), dim3(256), 0, st, params[20], params[21], params[18], params[19], Cdir, fold);
+    int rc = sw_check(hipGetLastError(), "pack_net_bwd_tnerf fold launch");
+    if (rc) return rc;
+    Packer pk(st, packed_bwd, packed_bwd + SW_TN_BWD_W_FLOATS, L_pos, L_dir, L_time);
+    pk.segT(fold, 64, SW_TN_FOLD_LD, 0, 128, 4, 2);                              // W9f^T  (layer_9.weight[:, :128] . feature.weight)
+    for (int l = 7; l >= 1; --l)                                                 // layers.l.weight[:, -128:]^T
+        pk.segT(params[2 * l], 128, l == 5 ? Cin + 128 : 128, l == 5 ? Cin : 0, 128, 4, 4);
+    if (!pk.rc && pk.w != packed_bwd + (size_t)SW_TN_BWD_STEPS * SW_STEP_FLOATS) return sw_fail(SWNERF_E_ARG, "pack_net_bwd_tnerf: internal layout mismatch");
+    pk.tail();
+    pk.vecs(params[16], 1, 128);                                                 // density.weight [1,128] as 4 bias-style tiles
+    pk.vecs(params[22], 3, 64);                                                  // color.weight rows as 3 x 2 tiles
+    if (!pk.rc && pk.b != fold) return sw_fail(SWNERF_E_ARG, "pack_net_bwd_tnerf: bias layout mismatch");
+    return pk.flush();
+}
+
 extern "C" int swnerf_pack_net(int kind, const float* const* params, int L_pos, int L_dir, int L_time, float* packed, void* stream) {
     if (!params || !packed) return sw_fail(SWNERF_E_ARG, "pack_net: NULL pointer");
     if (kind == SWNERF_NET_TNERF) {

@@ -156,6 +156,67 @@ static inline int pass_resampling(const char* name, const swnerf_pass_args& a, P
     return 0;
 }
 
+// ---- the compositing backward of ONE ray by its wave (autograd of ray.py:155-198; composite.h), shared by the fused backward
+// kernels (train_kernels.hip render_pass_backward_kernel, tnerf_train_kernels.hip tnerf_backward_kernel): forward recompute of T and
+// w from the saved raw [S, oc] and depths zv [S] (-> T_[S], W_[S] in the wave's LDS slice), suffix sums of G.w in double, d raw of
+// every sample -> dR[S][4] in LDS.  noise: this ray's [S] or NULL; g_rgb [3] / g_disp [1] / g_acc [1]: this ray's upstream
+// gradients, each may be NULL.  VEC4: raw rows are 16-byte aligned (oc == 4).  Ends with the LDS visible to the whole wave.
+template <bool VEC4>
+__device__ __forceinline__ void comp_bwd_ray(const float* raw, int oc, const float* zv, const float* noise, int S, int lane, float dnorm,
+                                             int white, const float* g_rgb, const float* g_disp, const float* g_acc,
+                                             float* T_, float* W_, float* dR) {
+    CompGrads g = {g_rgb ? g_rgb[0] : 0.f, g_rgb ? g_rgb[1] : 0.f, g_rgb ? g_rgb[2] : 0.f, g_acc ? g_acc[0] : 0.f, 0.f};
+    double Tc = 1.0;
+    float pa = 0.f, pd = 0.f;
+    for (int base = 0; base < S; base += 64) {
+        const int s = base + lane;
+        const bool live = s < S;
+        const int sc = live ? s : S - 1;
+        const float z = zv[sc];
+        const float zn = (s + 1 < S) ? zv[s + 1] : z;
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
+        float sg = raw[sc * oc + 3];
+        if (noise) sg += noise[sc];
+        const float alpha = comp_alpha(sg, dist, live);
+        const float T = comp_transmittance(excl_cumprod_shfl<64>(comp_survival(alpha), lane), Tc);
+        const float w = alpha * T;
+        if (live) { T_[s] = T; W_[s] = w; }
+        pa += w; pd += w * z;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { pa += __shfl_xor(pa, o, 64); pd += __shfl_xor(pd, o, 64); }
+    comp_bwd_fold(g, white, g_disp, pd, pa);
+    wave_lds_sync();
+    double carry = 0.0;
+    const int nch = (S + 63) / 64;
+    for (int ch = nch - 1; ch >= 0; --ch) {
+        const int s = ch * 64 + lane;
+        const bool live = s < S;
+        const int sc = live ? s : S - 1;
+        f32x4 r4;
+        if (!VEC4) { r4[0] = raw[sc * oc]; r4[1] = raw[sc * oc + 1]; r4[2] = raw[sc * oc + 2]; r4[3] = raw[sc * oc + 3]; }   // rows of 5 floats are not 16-byte aligned
+        else r4 = *reinterpret_cast<const f32x4*>(raw + sc * 4);
+        const float z = zv[sc];
+        const float c0 = comp_sigmoid(r4[0]), c1 = comp_sigmoid(r4[1]), c2 = comp_sigmoid(r4[2]);
+        const float w = live ? W_[sc] : 0.f, T = live ? T_[sc] : 0.f;
+        const float G = comp_bwd_G(g, c0, c1, c2, z);
+        double v = live ? (double)G * (double)w : 0.0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const double dn = __shfl_down(v, o, 64); if (lane + o < 64) v += dn; }
+        double after = __shfl_down(v, 1, 64);
+        if (lane == 63) after = 0.0;
+        const double R = carry + after;
+        carry += __shfl(v, 0, 64);
+        const float zn = (s + 1 < S) ? zv[s + 1] : z;
+        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
+        float sg = r4[3];
+        if (noise) sg += noise[sc];
+        const f32x4 o4 = comp_bwd_sample(g, G, T, w, R, sg, dist, c0, c1, c2);
+        if (live) *reinterpret_cast<f32x4*>(dR + 4 * s) = o4;
+    }
+    wave_lds_sync();
+}
+
 // ------------------------------------------------------------------------------------------
 // TRAIN, static net: the LDS bias region holds the canonical tiles alone (the deformation tiles' 11 KB are what lets the
 // 16-deep ring of the training translation unit AND the resampling scratch fit into 160 KB).  TRAIN + DNERF keeps both

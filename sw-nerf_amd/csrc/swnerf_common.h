@@ -284,3 +284,18 @@ SW_HD float sw_linspace(float start, float end, int steps, int i) {
 #define SW_TN_W_FLOATS     ((SW_TN_STEPS + SW_TAIL) * SW_STEP_FLOATS)
 #define SW_TN_FOLD_OFFSET  (SW_TN_W_FLOATS + SW_TN_BIAS_TILES * SW_BIAS_TILE_FLOATS)
 #define SW_TN_FLOATS       (SW_TN_FOLD_OFFSET + SW_TN_FOLD_FLOATS)
+
+// ---- T-NeRF training (tnerf_pass.h TRAIN variant, instantiated in tnerf_train_kernels.hip with the backward; DESIGN.md 6e "Training") -------------------
+// Saved per padded row (swnerf_train_rows): act / grad [rows, SW_TN_ACT_LD]: h_l (post-ELU) / d pre_l at 128*l for l = 0..7,
+// the layer_9 hidden (post-ELU) / d pre_9 at SW_TN_ACT_HV; xs [rows, SW_TN_XS_LD] in B-operand slot order: gamma(x) slots 0..63
+// (sw_pos_col), gamma(t) 64..95 (sw_time_col), gamma(d) 96..127 (sw_dir_col) - the ray-constant tiles are written into every row
+// of the ray, so that the skip-input weight gradients are plain TN GEMMs over the rows (no per-ray reduction kernel).
+#define SW_TN_ACT_LD       1088
+#define SW_TN_ACT_HV       1024
+#define SW_TN_XS_LD        128
+// backward stream: W9f^T (4x2: d h7 <- d pre_9 through the folded layer_9) | L7^T .. L1^T (4x4 each; L5: its h4 columns);
+// then bias-style tiles: density.weight 4 | color.weight 3 x 2; then SW_TN_FOLD_FLOATS of scratch (the fold W9f^T was packed from)
+#define SW_TN_BWD_STEPS    (32 + 7 * 64)
+#define SW_TN_BWD_W_FLOATS ((SW_TN_BWD_STEPS + SW_TAIL) * SW_STEP_FLOATS)
+#define SW_TN_BWD_BIAS_TILES 10
+#define SW_TN_BWD_FLOATS   (SW_TN_BWD_W_FLOATS + SW_TN_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS + SW_TN_FOLD_FLOATS)

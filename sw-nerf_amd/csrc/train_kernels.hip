@@ -264,58 +264,9 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
     WStream ws;
     ws_start(ws, P.w0, lds_all, lds_ring, lane);      // the weight ring fills while the compositing backward runs
 
-    // ---- 1. compositing backward (composite.h; no d(depth_map) and no d(weights) reach the fused step)
-    CompGrads g = {P.g_rgb ? P.g_rgb[ray * 3] : 0.f, P.g_rgb ? P.g_rgb[ray * 3 + 1] : 0.f, P.g_rgb ? P.g_rgb[ray * 3 + 2] : 0.f,
-                   P.g_acc ? P.g_acc[ray] : 0.f, 0.f};
-    double Tc = 1.0;
-    float pa = 0.f, pd = 0.f;
-    for (int base = 0; base < S; base += 64) {
-        const int s = base + lane;
-        const bool live = s < S;
-        const int sc = live ? s : S - 1;
-        const float z = zv[sc];
-        const float zn = (s + 1 < S) ? zv[s + 1] : z;
-        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
-        float sg = raw[sc * oc + 3];
-        if (P.noise) sg += P.noise[ray * S + sc];
-        const float alpha = comp_alpha(sg, dist, live);
-        const float T = comp_transmittance(excl_cumprod_shfl<64>(comp_survival(alpha), lane), Tc);
-        const float w = alpha * T;
-        if (live) { T_[s] = T; W_[s] = w; }
-        pa += w; pd += w * z;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { pa += __shfl_xor(pa, o, 64); pd += __shfl_xor(pd, o, 64); }
-    comp_bwd_fold(g, P.white, P.g_disp ? P.g_disp + ray : nullptr, pd, pa);
-    wave_lds_sync();
-    double carry = 0.0;
-    const int nch = (S + 63) / 64;
-    for (int ch = nch - 1; ch >= 0; --ch) {
-        const int s = ch * 64 + lane;
-        const bool live = s < S;
-        const int sc = live ? s : S - 1;
-        f32x4 r4;
-        if (NOVIEW) { r4[0] = raw[sc * oc]; r4[1] = raw[sc * oc + 1]; r4[2] = raw[sc * oc + 2]; r4[3] = raw[sc * oc + 3]; }   // rows of 5 floats are not 16-byte aligned
-        else r4 = *reinterpret_cast<const f32x4*>(raw + sc * 4);
-        const float z = zv[sc];
-        const float c0 = comp_sigmoid(r4[0]), c1 = comp_sigmoid(r4[1]), c2 = comp_sigmoid(r4[2]);
-        const float w = live ? W_[sc] : 0.f, T = live ? T_[sc] : 0.f;
-        const float G = comp_bwd_G(g, c0, c1, c2, z);
-        double v = live ? (double)G * (double)w : 0.0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const double dn = __shfl_down(v, o, 64); if (lane + o < 64) v += dn; }
-        double after = __shfl_down(v, 1, 64);
-        if (lane == 63) after = 0.0;
-        const double R = carry + after;
-        carry += __shfl(v, 0, 64);
-        const float zn = (s + 1 < S) ? zv[s + 1] : z;
-        const float dist = comp_dist(s + 1 < S, zn, z, dnorm);
-        float sg = r4[3];
-        if (P.noise) sg += P.noise[ray * S + sc];
-        const f32x4 o4 = comp_bwd_sample(g, G, T, w, R, sg, dist, c0, c1, c2);
-        if (live) *reinterpret_cast<f32x4*>(dR + 4 * s) = o4;
-    }
-    wave_lds_sync();
+    // ---- 1. compositing backward (render_pass.h comp_bwd_ray; no d(depth_map) and no d(weights) reach the fused step)
+    comp_bwd_ray<!NOVIEW>(raw, oc, zv, P.noise ? P.noise + ray * S : nullptr, S, lane, dnorm, P.white, P.g_rgb ? P.g_rgb + ray * 3 : nullptr,
+                          P.g_disp ? P.g_disp + ray : nullptr, P.g_acc ? P.g_acc + ray : nullptr, T_, W_, dR);
 
     // ---- 2. the dX chain(s), tile by tile: mlp_backward_dx_kernel<DNERF> [+ deform_backward_dx_kernel]
     const f32x4 nomask = {0.f, 0.f, 0.f, 0.f};

@@ -33,7 +33,9 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_gemm_tn_ordered_ws_floats", "swnerf_gemm_tn_ordered",
            "swnerf_encode2d", "swnerf_bn_workspace_bytes", "swnerf_bn_forward_train", "swnerf_bn_backward", "swnerf_bn_apply",
            "swnerf_fit2d_loss", "swnerf_fit2d_packed_floats", "swnerf_pack_fit2d", "swnerf_fit2d_forward", "swnerf_fit2d_picture",
-           "swnerf_perm_indices", "swnerf_train_batch", "swnerf_photo_loss"]
+           "swnerf_perm_indices", "swnerf_train_batch", "swnerf_photo_loss",
+           "swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_render_pass_train_tnerf",
+           "swnerf_packed_bwd_tnerf_floats", "swnerf_pack_net_bwd_tnerf", "swnerf_render_pass_backward_tnerf", "swnerf_tnerf_feature_finish"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -185,8 +187,18 @@ def lib():
                                       c_double, c_double, c_double, c_double, c_int, c_double, c_double, c_int, c_int, c_double, c_int,
                                       ctypes.c_uint64, c_int64, c_int64, c_void_p] + [c_void_p] * 4)
     L.swnerf_photo_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_void_p] * 5
+    for name in ("swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_packed_bwd_tnerf_floats"):
+        getattr(L, name).restype = c_size_t
+        getattr(L, name).argtypes = []
+    L.swnerf_render_pass_train_tnerf.argtypes = [POINTER(PassArgs), c_void_p, c_void_p, c_void_p]
+    L.swnerf_pack_net_bwd_tnerf.argtypes = [POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_void_p]
+    L.swnerf_render_pass_backward_tnerf.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.swnerf_tnerf_feature_finish.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     for name in EXPORTS:
-        if name not in ("swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
+        if name not in ("swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_packed_bwd_tnerf_floats",
+                        "swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
                         "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",
                         "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes", "swnerf_gemm_tn_ordered_ws_floats",
                         "swnerf_bn_workspace_bytes", "swnerf_fit2d_packed_floats"):

@@ -505,6 +505,25 @@ class TNeRF(nn.Module):
         self.layer_9 = nn.Sequential(nn.Linear(in_features=net_dim + dir_feat, out_features=net_dim // 2), nn.ELU())
         self.color = nn.Sequential(nn.Linear(in_features=net_dim // 2, out_features=3), nn.ReLU())
         self._pack_key, self._packed = None, None
+        self._pack_bwd_key, self._packed_bwd = None, None
+
+    def packed_bwd(self):
+        """The transposed weight stream of the fused backward's dX chain (include/swnerf.h swnerf_pack_net_bwd_tnerf), cached like
+        packed(): repacked when a parameter changed in place (optimizer step, load_state_dict) or moved."""
+        bands = self.fused_bands()
+        if bands is None:
+            raise NotImplementedError("swnerf: the fused T-NeRF training pass is built for depth 8, net_dim 128, skip_layer 4")
+        sd = dict(self.named_parameters())
+        ps = [sd[n] for n in _TNERF_ORDER]
+        key = tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._pack_bwd_key:
+            L = _lib.lib()
+            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
+            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
+            buf = torch.empty(L.swnerf_packed_bwd_tnerf_floats(), dtype=torch.float32, device=ps[0].device)
+            _lib.check(L.swnerf_pack_net_bwd_tnerf(arr, *bands, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net_bwd_tnerf")
+            self._packed_bwd, self._pack_bwd_key = buf, key
+        return self._packed_bwd
 
     def forward(self, inp, vdir, dyn_t):
         from .generic import tnerf_forward

@@ -4,10 +4,14 @@ run_network, batchify_rays, render, render_path and render_rays with the referen
 render_rays takes the fused T-NeRF pass (csrc/tnerf_kernels.hip: one wave per ray, the 8 x 128 ELU net in registers,
 compositing in the same kernel) when `tnerf_plan` holds: no grad, a GPU TNeRF of depth 8 / width 128 / skip 4, the
 closure's standard encoders with matching sizes, and embd_time_discr.  It keeps run_network's one-time-per-batch assertion.
+Under grad with `fused_train=True` (opt-in) and 2 <= S <= 256 it takes the fused training pass instead (`_FusedPassTrainTnerf`,
+csrc/tnerf_train_kernels.hip: the same forward that also saves activations, a one-wave-per-ray backward, TN GEMMs for dW).
 Otherwise it takes the differentiable op path: the HIP sampling op,
 `network_query_fn` (embedders + TNeRF.forward on the generic GEMMs with ELU) and the raw2outputs op with its backward.
 The fused pass does not go through batchify, so it renders any ray count; on the op path, as in the reference, a sample
 count that netchunk does not divide makes batchify's torch.cat fail ("Sizes of tensors must match")."""
+import contextlib
+import contextvars
 import inspect
 import os
 
@@ -18,10 +22,25 @@ from . import _lib
 from .embedder import to8b, EmbedFn
 from .png import write_png
 from .ray import get_rays, ndc_rays, raw2outputs
-from .render import closure_embedders, wants_grad, sample_coarse, pass_args, result_dict, batchify_rays_with, image_outputs
+from .render import (closure_embedders, wants_grad, sample_coarse, pass_args, result_dict, batchify_rays_with, image_outputs,
+                     chunked_backward, f32_grads, ray_ptrs, TRAIN_FUSED_MAX_SAMPLES)
 from .model import TNeRF
 
 DEBUG = False
+
+# The opt-in to the fused training pass.  render_rays keeps the reference's parameter list (tests pin it), so the switch travels
+# beside it: a context variable (per thread / task, restored on exit), set by `with fused_train():` or by batchify_rays' keyword.
+_FUSED_TRAIN = contextvars.ContextVar("swnerf_tnerf_fused_train", default=False)
+
+
+@contextlib.contextmanager
+def fused_train(on=True):
+    """with fused_train(): render_rays calls under grad take the fused T-NeRF training pass where it applies (default: op path)."""
+    tok = _FUSED_TRAIN.set(bool(on))
+    try:
+        yield
+    finally:
+        _FUSED_TRAIN.reset(tok)
 
 
 def batchify(fn, chunk):
@@ -69,10 +88,11 @@ def _time_discr(network_query_fn):
     return getattr(args, "nerf_type", None) != "temporal"
 
 
-def tnerf_plan(network_query_fn, net):
-    """(L_pos, L_dir, L_time) when render_rays may take the fused T-NeRF pass: no grad, a TNeRF on the GPU with the fused
-    shape, and the standard encoders in the closure with sizes matching the net; else None."""
-    if not isinstance(net, TNeRF) or wants_grad([net]):
+def tnerf_plan(network_query_fn, net, allow_train=False):
+    """(L_pos, L_dir, L_time) when render_rays may take the fused T-NeRF pass: no grad (allow_train: or grad - the caller then
+    takes the fused TRAINING pass), a TNeRF on the GPU with the fused shape, and the standard encoders in the closure with sizes
+    matching the net; else None."""
+    if not isinstance(net, TNeRF) or (wants_grad([net]) and not allow_train):
         return None
     bands = net.fused_bands()
     if bands is None or not next(net.parameters()).is_cuda:
@@ -99,6 +119,69 @@ def render_pass_tnerf(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, 
     return out
 
 
+class _FusedPassTrainTnerf(torch.autograd.Function):
+    """The fused T-NeRF pass under autograd (the step of t_nerf/run_tnerf.py:680-720: render -> img2mse -> loss.backward()).
+    forward = swnerf_render_pass_train_tnerf: the inference pass, bit for bit, that also saves the post-ELU activations and the
+    encodings; backward = swnerf_render_pass_backward_tnerf (one wave per ray: compositing backward in LDS, then the dX chain
+    per tile with ELU' from the saved activations) + one TN GEMM per weight block (wgrad.WeightGrads kind "tnerf"; `feature` is
+    un-folded from G in swnerf_tnerf_feature_finish).  Gradients flow to the net's parameters only (rays are data)."""
+
+    @staticmethod
+    def forward(ctx, net, rb, z_vals, S, lindisp, t_rand, noise, white_bkgd, *params):
+        kind, packed, Lp, Ld, Lt = net.packed()
+        L = _lib.lib()
+        N = rb.shape[0]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
+        rows = L.swnerf_train_rows(N, S)
+        act, xs = new(rows, L.swnerf_tnerf_act_floats_per_row()), new(rows, L.swnerf_tnerf_xs_floats_per_row())
+        a, o, _keep = pass_args(rb, kind, packed, (Lp, Ld, Lt), S, 4, 0, dict(z_vals=z_vals, t_rand=t_rand, noise=noise),
+                                ["rgb_map", "disp_map", "acc_map", "raw"] + ([] if z_vals is not None else ["z_out"]),
+                                lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_train_tnerf")
+        z = z_vals if z_vals is not None else o["z_out"]
+        _lib.check(L.swnerf_render_pass_train_tnerf(a, _lib.ptr(act), _lib.ptr(xs), _lib.stream_of(rb)), "render_pass_train_tnerf")
+        ctx.net, ctx.S, ctx.white, ctx.bands = net, S, bool(white_bkgd), (Lp, Ld, Lt)
+        ctx.has_noise = noise is not None
+        ctx.save_for_backward(rb, z, o["raw"], act, xs, noise if noise is not None else new(0), *params)
+        ctx.mark_non_differentiable(z)
+        ctx.set_materialize_grads(False)       # an output the loss does not use arrives as None (no zero fill, no read of zeros in the kernel)
+        return o["rgb_map"], o["disp_map"], o["acc_map"], z, o["raw"]
+
+    @staticmethod
+    def backward(ctx, *grads_out):
+        from .wgrad import WeightGrads
+        rb, z, raw, act, xs, noise, *params = ctx.saved_tensors
+        net, S = ctx.net, ctx.S
+        L = _lib.lib()
+        N, cols = rb.shape
+        st = _lib.stream_of(rb)
+        g_rgb, g_disp, g_acc, _gz, g_raw = f32_grads(*grads_out)
+        wg = WeightGrads(L, "tnerf", params, fused=True, Cpos=net.in_feat, Cdir=net.dir_feat, Ct=net.time_feat, bands=ctx.bands)
+        packed_bwd = net.packed_bwd()
+
+        def launch(r0, r1, bufs):
+            _lib.check(L.swnerf_render_pass_backward_tnerf(
+                _lib.ptr(packed_bwd), *ray_ptrs(r0, r1, act, per_ray=act.shape[0] // N), *ray_ptrs(r0, r1, raw, z, rb), cols,
+                *ray_ptrs(r0, r1, noise if ctx.has_noise else None), r1 - r0, S, int(ctx.white),
+                *ray_ptrs(r0, r1, g_rgb, g_disp, g_acc, g_raw), _lib.ptr(bufs[0]), _lib.ptr(bufs[1]), st), "render_pass_backward_tnerf")
+
+        jobs = lambda a0, a1, m, bufs: [lambda st_, part: wg.chunk(st_, m, bufs[0][:m], act[a0:a1], xs[a0:a1], bufs[1][:m], part=part)]
+        chunked_backward(rb, act.shape[0], 1, (act.shape[1], 4), launch, jobs, rest_on_main=False)
+        return (None,) * 8 + tuple(gi.to(p.dtype) for gi, p in zip(wg.finish(st), params))
+
+
+def render_pass_train_tnerf(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand=None, noise=None, white_bkgd=False):
+    """One differentiable fused T-NeRF pass (`_FusedPassTrainTnerf`): dict with rgb_map disp_map acc_map raw z."""
+    from .model import _TNERF_ORDER
+    rb = _lib.dev_f32(ray_batch.detach(), "ray_batch", 12)
+    S = int(n_samples)
+    chk = lambda t, name: None if t is None else _lib.dev_f32(t.detach(), name, S)
+    z_vals, t_rand, noise = chk(z_vals, "z_vals"), chk(t_rand, "t_rand"), chk(noise, "noise")
+    sd = dict(net.named_parameters())
+    rgb, disp, acc, z, raw = _FusedPassTrainTnerf.apply(net, rb, z_vals, S, bool(lindisp), t_rand, noise, bool(white_bkgd),
+                                                        *[sd[n] for n in _TNERF_ORDER])
+    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "raw": raw, "z": z}
+
+
 def _rng(N, S, perturb, raw_noise_std, pytest, dev, need_t_rand):
     """The random tensors of render_rays in the reference's order: t_rand (run_tnerf.py:461-468; its pytest branch scales by
     raw_noise_std, kept), then the sigma noise of raw2outputs (:367-374)."""
@@ -120,17 +203,26 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                 network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, z_vals=None,
                 use_two_models_for_fine=False):
     """run_tnerf.py:395-500 -> {rgb_map, disp_map, acc_map, z_vals (, raw)}.  One net; N_importance only prints the
-    reference's warning."""
+    reference's warning.  The parameter list is the reference's; the opt-in to the fused TRAINING pass is `fused_train`
+    (the context manager below, or batchify_rays' keyword): under grad it is taken when the fused pass's conditions hold and
+    2 <= S <= 256; where they do not, the call falls through to the op path as without it."""
     N_rays = ray_batch.shape[0]
     dev = ray_batch.device
     if z_vals is None and N_importance > 0:
         print("Warning: N_importance is set but only a single model is used.")
     S = int(N_samples) if z_vals is None else int(z_vals.shape[-1])
     t_rand, noise = _rng(N_rays, S, perturb, raw_noise_std, pytest, dev, z_vals is None)
-    bands = tnerf_plan(network_query_fn, network_fn) if ray_batch.shape[-1] == 12 else None
+    train = _FUSED_TRAIN.get() and wants_grad([network_fn])
+    bands = tnerf_plan(network_query_fn, network_fn, allow_train=train) if ray_batch.shape[-1] == 12 else None
+    if bands is not None and wants_grad([network_fn]) and not (train and N_rays > 0 and 2 <= S <= TRAIN_FUSED_MAX_SAMPLES):
+        bands = None
     if bands is not None:
         # run_network's assertion (run_tnerf.py:52), which the fused pass - it reads each ray's own time - would not need
         assert len(torch.unique(ray_batch[:, 8])) == 1, "Only accepts all points from same time"
+        if train:
+            p = render_pass_train_tnerf(ray_batch, network_fn, S, z_vals=z_vals, lindisp=lindisp, t_rand=t_rand, noise=noise,
+                                        white_bkgd=white_bkgd)
+            return result_dict(p, retraw, z_vals=p["z"])
         want = ["rgb_map", "disp_map", "acc_map"] + (["raw"] if retraw else []) + (["z_out"] if z_vals is None else [])
         o = render_pass_tnerf(ray_batch, network_fn, S, z_vals=z_vals, lindisp=lindisp, t_rand=t_rand, noise=noise,
                               white_bkgd=white_bkgd, want=want)
@@ -149,8 +241,11 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
-    """run_tnerf.py:90-103 (this module's render_rays, looked up per call)."""
-    return batchify_rays_with(render_rays, rays_flat, chunk, **kwargs)
+    """run_tnerf.py:90-103 (this module's render_rays, looked up per call).  One keyword more than the reference passes on:
+    fused_train (default False) - under grad, the chunks take the fused training pass (see `fused_train`)."""
+    on = bool(kwargs.pop("fused_train", False))
+    with fused_train(on or _FUSED_TRAIN.get()):
+        return batchify_rays_with(render_rays, rays_flat, chunk, **kwargs)
 
 
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., frame_time=None,

@@ -449,19 +449,20 @@ def _opt(args, name, default):
     return getattr(args, name, default)
 
 
-def _train_common(args, d, device, sampler, loss_fn, dnerf):
+def _train_common(args, d, device, sampler, loss_fn, create, timed):
+    """create: the runner's creator (create_nerf / create_dnerf / create_tnerf); timed: the D-NeRF and T-NeRF runners build rays
+    from hwf's focal and carry the frame time in column 8."""
     from . import batching
     if sampler not in ("device", "numpy"):
         raise ValueError(f"swnerf.runner.train: sampler must be 'device' or 'numpy', got {sampler!r}")
     device = _device(device)
-    create = create_dnerf if dnerf else create_nerf
     train_kw, test_kw, start, grad_vars, optimizer = create(args, device=device)
     bds = {'near': d['near'], 'far': d['far']}
     train_kw.update(bds)
     test_kw.update(bds)
     i_train = np.asarray(d['i_split'][0]).reshape(-1)
-    batcher = batching.RayBatcher(d['images'], d['poses'], d['hwf'] if dnerf else d['K'],        # the runners' own get_rays calls: focal there, K here
-                                  i_train, d['near'], d['far'], times=d.get('times') if dnerf else None,
+    batcher = batching.RayBatcher(d['images'], d['poses'], d['hwf'] if timed else d['K'],        # the runners' own get_rays calls: focal there, K here
+                                  i_train, d['near'], d['far'], times=d.get('times') if timed else None,
                                   ndc=train_kw.get('ndc', True), use_viewdirs=train_kw['use_viewdirs'], white_bkgd=args.white_bkgd,
                                   seed=_opt(args, 'seed', 0), device=device)
     rays_kw = {k: v for k, v in train_kw.items() if k not in _RENDER_ONLY_KEYS}
@@ -488,7 +489,7 @@ def _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw
     record.add(i, loss, img_loss, new_lrate)
     if i % _opt(args, 'i_weights', 10000) == 0:
         from .checkpoint import save_checkpoint
-        path = save_checkpoint(args.basedir, args.expname, i, global_step, train_kw['network_fn'], train_kw['network_fine'], optimizer)
+        path = save_checkpoint(args.basedir, args.expname, i, global_step, train_kw['network_fn'], train_kw.get('network_fine'), optimizer)
         print('Saved checkpoints at', path)
     if i % _opt(args, 'i_print', 100) == 0:
         last = record.flush()[-1]
@@ -512,7 +513,7 @@ def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
     hooks: {'on_batch': f(i, img_i, ray_batch, target, ids), 'on_step': f(i, optimizer)}.
     -> the per-step record: a list of {'step', 'loss', 'psnr', 'lr'}."""
     d = _train_data(data, False)
-    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, False)
+    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, create_nerf, False)
     H, W, focal = d['hwf']
     N_rand = args.N_rand
     use_batching = not args.no_batching
@@ -555,7 +556,7 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  args.N_iter is the last iteration.
     hooks: those of `train`, and 'on_tv': f(i, which, ray_batch_other, z_vals) before each prev / next render."""
     d = _train_data(data, True)
-    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, True)
+    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, create_dnerf, True)
     N_rand = args.N_rand
     if not args.no_batching:
         raise NotImplementedError("Time not implemented")                        # run_dnerf.py:634
@@ -621,6 +622,52 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
             poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
             with torch.no_grad():
                 render_dnerf.render_path(poses_test, torch.as_tensor(times[i_test]).to(device), d['hwf'], chunk, test_kw,
+                                         gt_imgs=_gt_rgb(d['images'], i_test, args.white_bkgd), savedir=testsavedir)
+            print('Saved test set')
+        global_step += 1
+    return record.flush()
+
+
+def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
+    """The training loop of t_nerf/run_tnerf.py:596-800 from `create_nerf` on; as `train_dnerf` without the TV loss: the time
+    curriculum precrop_iters_time (:646-651), a 12-column batch with the drawn image's frame time in column 8 (from the batcher's
+    device table), render_tnerf.batchify_rays(..., retraw=True, fused_train=...), the single-net loss (rgb0 is None), Adam and
+    the lr decay, a checkpoint every i_weights (network_fine None), render_tnerf.render_path every i_testset.
+    args.N_iter is the last iteration; args.fused_train (extra, default True) = False keeps loss.backward() on the op path.
+    use_batching raises NotImplementedError: the reference's branch (:631-642) builds rays without a frame time and cannot run.
+    data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  hooks: those of `train`."""
+    d = _train_data(data, True)
+    if not args.no_batching:
+        raise NotImplementedError("swnerf.runner.train_tnerf: use_batching is not built - the reference's branch (run_tnerf.py:631-642) "
+                                  "draws rays that carry no frame time and cannot run; pass no_batching=True")
+    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, create_tnerf, True)
+    N_rand = args.N_rand
+    N_iters = _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)) + 1
+    times = batcher.times_host
+    chunk = _opt(args, 'chunk', 1024 * 32)
+    fused = bool(_opt(args, 'fused_train', True))
+    from .batching import time_curriculum_max
+    global_step = start
+    record = _Record()
+    for i in range(start + 1, N_iters):
+        max_sample = time_curriculum_max(i, _opt(args, 'precrop_iters_time', 0), len(i_train))
+        img_i = np.random.choice(i_train if max_sample is None else i_train[:max_sample])
+        ray_batch, target_s, ids = _image_draw(args, batcher, i, img_i, sampler, N_rand)
+        if hooks and 'on_batch' in hooks:
+            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
+        all_ret = render_tnerf.batchify_rays(ray_batch, chunk, retraw=True, fused_train=fused, **rays_kw)
+        rgb, disp, acc, extras = render.image_outputs(all_ret, (ray_batch.shape[0], 3))
+        optimizer.zero_grad()
+        loss, img_loss, img_loss0 = loss_fn(rgb, target_s, None)
+        loss.backward()
+        optimizer.step()
+        _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks)
+        i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
+        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
+            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
+            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
+            with torch.no_grad():
+                render_tnerf.render_path(poses_test, [float(t) for t in times[i_test]], d['hwf'], chunk, test_kw,
                                          gt_imgs=_gt_rgb(d['images'], i_test, args.white_bkgd), savedir=testsavedir)
             print('Saved test set')
         global_step += 1

@@ -137,7 +137,12 @@ KINDS = {
     "noview": dict(n_params=18, head=(16, 17, "w8", "b8", None)),
     # the deformation net of DirectTemporalNeRF: _DEFORM_ORDER (_time 0..15, _time_out 16/17)
     "deform": dict(n_params=18, head=(16, 17, "w4", "b4", 3)),
+    # TNeRF (8 x 128, ELU; fused pass only): _TNERF_ORDER (layers 0..15, density 16/17, feature 18/19, layer_9 20/21, color 22/23).
+    # Buffers of csrc/tnerf_train_kernels.hip: grad / act [M, 1088] (layer l at 128 l, the layer_9 hidden at 1024), xs [M, 128]
+    # (gamma(x) slots 0..63, gamma(t) 64..95, gamma(d) 96..127), d raw [M, 4] = [d pre-ReLU colour, d sigma]
+    "tnerf": dict(n_params=24, head=(22, 23, "rgb4w", "rgb4b", 3)),
 }
+TN_ACT_HV, TN_ACT_H7 = 1024, 896   # csrc/swnerf_common.h SW_TN_ACT_HV; column of h7
 
 
 class WeightGrads:
@@ -163,9 +168,12 @@ class WeightGrads:
             hrows = params[hw].shape[0]                          # output_linear: 4 or 5 channels
         self.head = (hw, hb, sw, sb, hrows)
         scratch = {}
-        if fused:
+        if fused and kind != "tnerf":
             scratch["c0s"], scratch["c5s"] = (256, 64), (256, 64)
-        if kind == "canon":
+        if kind == "tnerf":
+            assert fused, "T-NeRF weight gradients are built for the fused training pass (the op path is torch autograd over the generic GEMMs)"
+            scratch.update(c0s=(128, 96), c5s=(128, 96), c9s=(64, 32), gfeat=(64, 128), a4w=(4, 128), a4b=(4,), rgb4w=(4, 64), rgb4b=(4,))
+        elif kind == "canon":
             scratch.update(gfeat=(128, 256), a4w=(4, 256), a4b=(4,), rgb4w=(4, 128), rgb4b=(4,))
             if fused:
                 scratch["cvs"] = (128, 32)
@@ -203,6 +211,8 @@ class WeightGrads:
         """part: "plain" = the seven 256 x 256 GEMMs only, the skip layer's with its gamma(x) rider (for the chunk's grouped
         launch, _chunk_gemms), "rest" = everything else, "all" = both."""
         L, g, s, Cpos = self.L, self.g, self.s, self.Cpos
+        if self.kind == "tnerf":
+            return self._chunk_tnerf(st, M, grad, act, enc, draw, part)
         e0 = 64 if self.fused else Cpos                          # width of the gamma(x) block of `enc`
         c5 = (s["c5s"], 0) if self.fused else (g[10], 0)         # where the skip layer's gamma(x) columns accumulate
         if part != "rest":
@@ -253,10 +263,44 @@ class WeightGrads:
             ncol = 4 if aligned4 else draw.shape[1]
             mm(draw, 0, ncol, act, SW_ACT_H7, 256, s["w4"], 0, s["b4"] if ncol == 4 else s["b4"][:ncol])     # _time_out (rows 0..2)
 
+    def _chunk_tnerf(self, st, M, grad, act, enc, draw, part):
+        """TNeRF: thirteen narrow products (No, Ni <= 128), none of them a 256 x 256 block - all in the "rest" part."""
+        if part == "plain":
+            return
+        L, g, s = self.L, self.g, self.s
+        Cin = self.Cpos + self.Ct                                # layers.5.weight = [gamma(x) | gamma(t) | h4]
+        mm = lambda A, a_col, No, B, b_col, Ni, C, c_col, bias: _gemm_tn(L, st, M, A, a_col, No, B, b_col, Ni, C, c_col, bias)
+        for l in (1, 2, 3, 4, 6, 7):
+            mm(grad, 128 * l, 128, act, 128 * (l - 1), 128, g[2 * l], 0, g[2 * l + 1])
+        mm(grad, 640, 128, act, 512, 128, g[10], Cin, g[11])                                # layers.5, h4 columns
+        mm(grad, 640, 128, enc, 0, 96, s["c5s"], 0, None)                                   # ... its gamma(x), gamma(t) slots
+        mm(grad, 0, 128, enc, 0, 96, s["c0s"], 0, g[1])                                     # layers.0 = [gamma(x) | gamma(t)]
+        mm(grad, TN_ACT_HV, 64, act, TN_ACT_H7, 128, s["gfeat"], 0, g[21])                  # G (+ layer_9.bias)
+        mm(grad, TN_ACT_HV, 64, enc, 96, 32, s["c9s"], 0, None)                             # layer_9, gamma(d) slots
+        mm(draw, 0, 4, act, TN_ACT_H7, 128, s["a4w"], 0, s["a4b"])                          # density = row 3 of d raw^T . h7
+        mm(draw, 0, 4, act, TN_ACT_HV, 64, s["rgb4w"], 0, s["rgb4b"])                       # color = rows 0..2
+
+    def _finish_tnerf(self, st):
+        L, g, s = self.L, self.g, self.s
+        Lp, Ld, Lt = self.bands
+        for cs, W in ((s["c0s"], g[0]), (s["c5s"], g[10])):                                 # slot-ordered columns to their reference columns
+            _lib.check(L.swnerf_unslot_grad(_lib.ptr(cs), 96, 128, 0, 64, Lp, 0, W.data_ptr(), W.stride(0), 0, st), "unslot_grad")
+            _lib.check(L.swnerf_unslot_grad_time(ctypes.c_void_p(cs.data_ptr() + 4 * 64), 96, 128, 32, Lt, W.data_ptr(), W.stride(0), self.Cpos, st),
+                       "unslot_grad_time")
+        _lib.check(L.swnerf_unslot_grad(_lib.ptr(s["c9s"]), 32, 64, 64, 32, Lp, Ld, g[20].data_ptr(), g[20].stride(0), 128, st), "unslot_grad")
+        f32 = lambda p_: p_.detach() if (p_.dtype == torch.float32 and p_.is_contiguous()) else p_.detach().float().contiguous()
+        W9, Wf, bf = f32(self.params[20]), f32(self.params[18]), f32(self.params[19])
+        _lib.check(L.swnerf_tnerf_feature_finish(_lib.ptr(s["gfeat"]), _lib.ptr(g[21]), _lib.ptr(W9), W9.stride(0), _lib.ptr(Wf), _lib.ptr(bf),
+                                                 _lib.ptr(s["a4w"]), _lib.ptr(s["a4b"]), _lib.ptr(g[20]), g[20].stride(0), _lib.ptr(g[18]), _lib.ptr(g[19]),
+                                                 _lib.ptr(g[16]), _lib.ptr(g[17]), st), "tnerf_feature_finish")
+        return self.g
+
     # -- after the last chunk ----------------------------------------------------------------------------------------------
     def finish(self, st):
         L, g, s = self.L, self.g, self.s
         Lp, Ld, Lt = self.bands
+        if self.kind == "tnerf":
+            return self._finish_tnerf(st)
         if self.fused:                                           # slot-ordered columns to their reference columns
             jobs = [(s["c0s"], 64, 0, g[0], 0), (s["c5s"], 64, 0, g[10], 0)]
             if self.kind == "canon":

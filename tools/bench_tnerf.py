@@ -4,7 +4,10 @@
   for a 400x400 frame (t_nerf/configs/lego.txt: half_res, 64 samples, white_bkgd); the fused pass's fraction of the fp32 MFMA
   roofline (157.3 TF) counted on the EXECUTED MACs (139 264 per sample + the per-ray prefix), the reference's count beside it;
   the op-path training step (ms, peak GiB) at N_rand 500 and 4096.
-Run: python tools/bench_tnerf.py [--reps 20]"""
+  --train: the training step alone, the op path and the fused training pass (render_tnerf.fused_train) side by side in the same
+  process at N_rand 500 and 4096 x 64 samples: median of --reps steps after 3 warm-up steps, peak memory of each, their ratio, and
+  the fused step's share of the fp32 MFMA roofline on its EXECUTED MACs (forward + dX chain + weight-gradient GEMMs).
+Run: python tools/bench_tnerf.py [--reps 20] [--train]"""
 import argparse
 import json
 import os
@@ -18,11 +21,14 @@ PEAK = 157.3e12
 MACS_EXEC = 139264            # per sample: layer 0 64x128, 6 x 128x128, layer 5 192x128, folded layer_9 128x64
 MACS_PREFIX = 2 * 32 * 128 + 32 * 64   # per ray: the gamma(t) columns of layers 0 and 5, the gamma(d) columns of layer_9 (padded k-tiles)
 MACS_REF = 162816             # the reference's per-sample count
+MACS_BWD_DX = 480 * 4 * 2048 // 32     # per sample: the dX chain's 480 steps (W9f^T 4x2, layers.7..1 4x4) of four 32x32x2 MFMAs per 32-sample tile
+MACS_BWD_DW = 7 * 128 * 128 + 2 * 128 * 96 + 64 * 128 + 64 * 32 + 4 * 128 + 4 * 64   # per sample: the weight-gradient GEMMs (wgrad.py kind "tnerf")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--train", action="store_true", help="time the op-path and the fused training step side by side")
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -58,6 +64,31 @@ def main():
             ts.append(time.perf_counter() - t0)
         return float(np.median(ts))
 
+    if a.train:
+        res = {"metric": "tnerf_train", "reps": a.reps, "macs_exec_per_sample_step": MACS_EXEC + MACS_BWD_DX + MACS_BWD_DW}
+        opt = torch.optim.Adam(net.parameters(), lr=5e-4)
+        for n in (500, 4096):
+            rb = rays(n, seed=2)
+            tgt = torch.full((n, 3), 0.5, device=dev)
+
+            def step(fused):
+                with render_tnerf.fused_train(fused):
+                    out = render_tnerf.render_rays(rb, net, q, 64, perturb=1., white_bkgd=True)
+                loss = ((out["rgb_map"] - tgt) ** 2).mean()
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+            for tag, fused in (("op", False), ("fused", True)):
+                for _ in range(3):
+                    step(fused)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                res[f"{tag}_{n}_ms"] = timeit(lambda: step(fused), a.reps) * 1e3
+                res[f"{tag}_{n}_peak_gib"] = torch.cuda.max_memory_allocated() / 2 ** 30
+            res[f"speedup_{n}"] = res[f"op_{n}_ms"] / res[f"fused_{n}_ms"]
+            res[f"fused_{n}_roofline"] = 2 * (MACS_EXEC + MACS_BWD_DX + MACS_BWD_DW) * 64 * n / (res[f"fused_{n}_ms"] * 1e-3) / PEAK
+        print(json.dumps(res), flush=True)
+        return
     res = {"metric": "tnerf", "macs_exec_per_sample": MACS_EXEC, "macs_ref_per_sample": MACS_REF}
     # the op path in ONE network call (netchunk None): with the reference's 65536 a 400x400 frame's 10.24 M rows leave a ragged
     # last chunk, which batchify's torch.cat rejects exactly as the reference does
