@@ -7,7 +7,6 @@ hidden_dim 256 / output_dim 3 / input_dimension 4L + 2 (L <= 23) is one fused la
 next Linear (swnerf_pack_fit2d, swnerf_fit2d_forward / swnerf_fit2d_picture); any other eval shape runs layer by layer
 (linear with the ReLU epilogue, then swnerf_bn_apply).  Parameters on the CPU are an error: there is no CPU fallback.
 AdamW and ExponentialLR stay torch's (plumbing, like Adam in every runner)."""
-import ctypes
 import os
 import time
 
@@ -15,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, generic
+from . import _lib, generic, packing
 from .png import write_png
 
 MAX_L = 23
@@ -111,7 +110,7 @@ class Model(nn.Module):
         self._initialize_weights()
         self.input_dimension, self.layer_num, self.hidden_dim, self.output_dim = input_dimension, layer_num, hidden_dim, output_dim
         self._stats_version = 0          # bumped by every training forward: the kernels write the running buffers through raw
-        self._pack = None                # pointers, so torch's _version does not see them.  _pack = (key, blob)
+        self._pack_cache = {}            # pointers, so torch's _version does not see them
 
     def _initialize_weights(self):
         for layer in self.modules():
@@ -137,32 +136,21 @@ class Model(nn.Module):
         return (d - 2) // 4
 
     # -- the packed stream, cached
-    def _pack_key(self):
-        return (self._stats_version,) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
-
     def packed(self):
+        """The fused pass's weight stream (swnerf_pack_fit2d), cached by swnerf.packing on every parameter and buffer plus
+        _stats_version."""
         L = self.fused_L()
         if L is None:
             raise RuntimeError("swnerf.fit2d: this Model has no fused form (hidden_dim 256, output_dim 3, input_dimension 4L + 2, L <= 23)")
-        key = self._pack_key()
-        if self._pack is not None and self._pack[0] == key:
-            return self._pack[1]
-        lib = _lib.lib()
         blocks, head = self._blocks()
-        ts = []
-        for lin, bn in blocks:
-            ts += [lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        ts += [head.weight, head.bias]
-        ts = [generic._c32(t.detach()) for t in ts]
         eps = {float(bn.eps) for _, bn in blocks}
         if len(eps) != 1:
             raise NotImplementedError("swnerf.fit2d: BatchNorm1d layers with different eps")
-        dev = ts[0].device
-        blob = torch.empty((lib.swnerf_fit2d_packed_floats(self.layer_num),), dtype=torch.float32, device=dev)
-        arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.check(lib.swnerf_pack_fit2d(arr, self.layer_num, L, eps.pop(), _lib.ptr(blob), _lib.stream_of(blob)), "pack_fit2d")
-        self._pack = (key, blob)
-        return blob
+        ts = [t for lin, bn in blocks for t in (lin.weight, lin.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        return packing.pack_weights(self._pack_cache, "fwd", ts + [head.weight, head.bias],
+                                    lambda lib: lib.swnerf_fit2d_packed_floats(self.layer_num),
+                                    lambda lib, arr, blob, st: lib.swnerf_pack_fit2d(arr, self.layer_num, L, eps.pop(), blob, st), "pack_fit2d",
+                                    extra=(self._stats_version,), keyed_on=list(self.parameters()) + list(self.buffers()))
 
     # -- forward
     def forward_layers(self, x):

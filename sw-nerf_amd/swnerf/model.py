@@ -14,14 +14,13 @@ Training: with grad enabled, forward saves the act
 register-resident dX chain + TN MFMA GEMMs (`_MlpTrain`, `_DnerfTrain`); gradients w.r.t. the embedded inputs are
 not produced (rays are data in the reference's train()).
 """
-import ctypes
 import os
 import torch
 import torch.nn as nn
 import torch.nn.functional as F  # noqa: F401
 import numpy as np
 
-from . import _lib
+from . import _lib, packing
 from .embedder import img2mse, mse2psnr, to8b  # noqa: F401
 
 _CANON_ORDER = ([f"pts_linears.{i}.{p}" for i in range(8) for p in ("weight", "bias")]
@@ -168,29 +167,22 @@ def _tag_no_backward(out, module):
     return out
 
 
-class _PackedMixin:
-    """Caches the MFMA-ordered weight stream; repacks when any parameter changed in place
-    (optimizer step, load_state_dict) or moved."""
+def _named(module, names):
+    sd = dict(module.named_parameters())
+    return [sd[n] for n in names]
 
-    def _init_pack(self):
-        self._pack_key = None
-        self._packed = None
-        self._pack_bwd = {}
+
+class _PackedMixin:
+    """The MFMA-ordered weight streams of a net, each cached in self._pack_cache by swnerf.packing: repacked, into a new
+    tensor, when a parameter it is built from changed in place (optimizer step, load_state_dict) or moved."""
 
     def packed_bwd(self, bwd_kind=0):
         """A transposed weight stream of the backward dX chains (include/swnerf.h SWNERF_BWD_*), cached like packed()."""
         kind, names, Lp, Ld, Lt = self._pack_params()
-        sd = dict(self.named_parameters())
-        ps = [sd[n] for n in (_DEFORM_ORDER if bwd_kind == _lib.BWD_DEFORM else (names if bwd_kind == _lib.BWD_DNERF_FUSED else names[:24]))]
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._pack_bwd.get(bwd_kind, (None, None))[0] != key:
-            L = _lib.lib()
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_bwd_floats_kind(bwd_kind), dtype=torch.float32, device=ps[0].device)
-            _lib.check(L.swnerf_pack_net_bwd_kind(bwd_kind, arr, Lp, Ld, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net_bwd")
-            self._pack_bwd[bwd_kind] = (key, buf)
-        return self._pack_bwd[bwd_kind][1]
+        names = _DEFORM_ORDER if bwd_kind == _lib.BWD_DEFORM else (names if bwd_kind == _lib.BWD_DNERF_FUSED else names[:24])
+        return packing.pack_weights(self._pack_cache, ("bwd", bwd_kind), _named(self, names),
+                                    lambda L: L.swnerf_packed_bwd_floats_kind(bwd_kind),
+                                    lambda L, arr, buf, st: L.swnerf_pack_net_bwd_kind(bwd_kind, arr, Lp, Ld, buf, st), "pack_net_bwd")
 
     def _wants_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -203,8 +195,7 @@ class _PackedMixin:
         flat = x.reshape(-1, x.shape[-1])
         if flat.shape[0] == 0:
             return torch.empty((*lead, 4), dtype=torch.float32, device=x.device)
-        sd = dict(self.named_parameters())
-        out = _MlpTrain.apply(self, flat, *[sd[n] for n in names[:24]])
+        out = _MlpTrain.apply(self, flat, *_named(self, names[:24]))
         return out.reshape(*lead, 4)
 
     def _is_fused_arch(self):
@@ -246,67 +237,31 @@ class _PackedMixin:
     def packed_noview(self):
         """(packed float tensor of kind SWNERF_NET_NOVIEW, L_pos, out_ch), cached like packed()."""
         names, Lp, out_ch = self._noview_params()
-        sd = dict(self.named_parameters())
-        ps = [sd[n] for n in names]
-        if not ps[0].is_cuda:
-            raise RuntimeError("swnerf: module parameters must be on the GPU (call .to('cuda')); no CPU fallback")
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self._pack_key:
-            L = _lib.lib()
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_floats(_lib.NET_NOVIEW), dtype=torch.float32, device=ps[0].device)
-            _lib.check(L.swnerf_pack_net_noview(arr, Lp, out_ch, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net_noview")
-            self._packed, self._pack_key = buf, key
-        return self._packed, Lp, out_ch
+        buf = packing.pack_weights(self._pack_cache, "noview", _named(self, names), lambda L: L.swnerf_packed_floats(_lib.NET_NOVIEW),
+                                   lambda L, arr, buf, st: L.swnerf_pack_net_noview(arr, Lp, out_ch, buf, st), "pack_net_noview")
+        return buf, Lp, out_ch
 
     def packed_bwd_noview(self):
         """The transposed stream of the NOVIEW net's dX chain (swnerf_pack_net_bwd_noview), cached like packed_bwd()."""
         names, Lp, out_ch = self._noview_params()
-        sd = dict(self.named_parameters())
-        ps = [sd[n] for n in names]
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if self._pack_bwd.get("noview", (None, None))[0] != key:
-            L = _lib.lib()
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_bwd_noview_floats(), dtype=torch.float32, device=ps[0].device)
-            _lib.check(L.swnerf_pack_net_bwd_noview(arr, Lp, out_ch, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net_bwd_noview")
-            self._pack_bwd["noview"] = (key, buf)
-        return self._pack_bwd["noview"][1]
+        return packing.pack_weights(self._pack_cache, "bwd_noview", _named(self, names), lambda L: L.swnerf_packed_bwd_noview_floats(),
+                                    lambda L, arr, buf, st: L.swnerf_pack_net_bwd_noview(arr, Lp, out_ch, buf, st), "pack_net_bwd_noview")
 
     def packed(self):
         """(kind, packed float tensor, L_pos, L_dir, L_time)"""
         kind, names, Lp, Ld, Lt = self._pack_params()
-        sd = dict(self.named_parameters())
-        ps = [sd[n] for n in names]
-        dev = ps[0].device
-        if not ps[0].is_cuda:
-            raise RuntimeError("swnerf: module parameters must be on the GPU (call .to('cuda')); no CPU fallback")
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self._pack_key:
-            L = _lib.lib()
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_floats(kind), dtype=torch.float32, device=dev)
-            _lib.check(L.swnerf_pack_net(kind, arr, Lp, Ld, Lt, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net")
-            self._packed, self._pack_key = buf, key
-        return kind, self._packed, Lp, Ld, Lt
+        buf = packing.pack_weights(self._pack_cache, "fwd", _named(self, names), lambda L: L.swnerf_packed_floats(kind),
+                                   lambda L, arr, buf, st: L.swnerf_pack_net(kind, arr, Lp, Ld, Lt, buf, st), "pack_net")
+        return kind, buf, Lp, Ld, Lt
 
     def packed_x3(self):
-        """The bf16x3 weight stream of this net (include/swnerf.h swnerf_pack_net_x3_kind), cached like packed()."""
+        """The bf16x3 weight stream of this net (include/swnerf.h swnerf_pack_net_x3_kind): built from the fp32 stream of packed()
+        and keyed on the same parameters, so both repack together."""
         kind, packed, Lp, Ld, Lt = self.packed()
-        if getattr(self, "_pack_x3_key", None) != self._pack_key:
-            L = _lib.lib()
-            _, names, _, _, _ = self._pack_params()
-            sd = dict(self.named_parameters())
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous()
-                    for p in (sd[n] for n in names)]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_x3_floats_kind(kind), dtype=torch.float32, device=packed.device)
-            _lib.check(L.swnerf_pack_net_x3_kind(kind, arr, Lp, Ld, Lt, _lib.ptr(packed), _lib.ptr(buf), _lib.stream_of(buf)), "pack_net_x3")
-            self._pack_x3, self._pack_x3_key = buf, self._pack_key
-        return self._pack_x3, Lp, Ld
+        buf = packing.pack_weights(self._pack_cache, "x3", _named(self, self._pack_params()[1]), lambda L: L.swnerf_packed_x3_floats_kind(kind),
+                                   lambda L, arr, buf, st: L.swnerf_pack_net_x3_kind(kind, arr, Lp, Ld, Lt, _lib.ptr(packed), buf, st),
+                                   "pack_net_x3")
+        return buf, Lp, Ld
 
     def _forward_hip(self, x, t_emb=None, run_deform=0, want_dx=False):
         kind, packed, Lp, Ld, Lt = self.packed()
@@ -345,7 +300,7 @@ class vallina_NeRF(nn.Module, _PackedMixin):
         self.D, self.W, self.input_ch, self.input_ch_views = D, W, input_ch, input_ch_views
         self.skips, self.use_viewdirs = skips, use_viewdirs
         _build_layers(self, D, W, input_ch, input_ch_views, output_ch, skips, use_viewdirs)
-        self._init_pack()
+        self._pack_cache = {}
 
     def _pack_params(self):
         Lp, Ld = self._check_arch()
@@ -386,7 +341,7 @@ class NeRFOriginal(nn.Module, _PackedMixin):
         for m in self.modules():
             if isinstance(m, nn.Linear):
                 nn.init.kaiming_normal_(m.weight, a=0, mode='fan_in')  # model.py:270-272
-        self._init_pack()
+        self._pack_cache = {}
 
     def _pack_params(self):
         Lp, Ld = self._check_arch()
@@ -419,7 +374,7 @@ class DirectTemporalNeRF(nn.Module, _PackedMixin):
             layers.append(nn.Linear(W + input_ch if i in skips else W, W))
         self._time = nn.ModuleList(layers)
         self._time_out = nn.Linear(W, 3)
-        self._init_pack()
+        self._pack_cache = {}
 
     def _pack_params(self):
         Lp, Ld = self._check_arch()
@@ -455,8 +410,7 @@ class DirectTemporalNeRF(nn.Module, _PackedMixin):
             if flat.shape[0] == 0:
                 return (torch.empty((*lead, 4), dtype=torch.float32, device=x.device),
                         torch.empty((*lead, 3), dtype=torch.float32, device=x.device))
-            sd = dict(self.named_parameters())
-            out, dx = _DnerfTrain.apply(self, flat, te, *[sd[n] for n in names])
+            out, dx = _DnerfTrain.apply(self, flat, te, *_named(self, names))
             return out.reshape(*lead, 4), dx.reshape(*lead, 3)
         out, dx = self._forward_hip(x, t_emb=t, run_deform=run_deform, want_dx=True)
         return out, dx
@@ -504,8 +458,7 @@ class TNeRF(nn.Module):
         self.feature = nn.Sequential(nn.Linear(in_features=net_dim, out_features=net_dim))
         self.layer_9 = nn.Sequential(nn.Linear(in_features=net_dim + dir_feat, out_features=net_dim // 2), nn.ELU())
         self.color = nn.Sequential(nn.Linear(in_features=net_dim // 2, out_features=3), nn.ReLU())
-        self._pack_key, self._packed = None, None
-        self._pack_bwd_key, self._packed_bwd = None, None
+        self._pack_cache = {}
 
     def packed_bwd(self):
         """The transposed weight stream of the fused backward's dX chain (include/swnerf.h swnerf_pack_net_bwd_tnerf), cached like
@@ -513,17 +466,8 @@ class TNeRF(nn.Module):
         bands = self.fused_bands()
         if bands is None:
             raise NotImplementedError("swnerf: the fused T-NeRF training pass is built for depth 8, net_dim 128, skip_layer 4")
-        sd = dict(self.named_parameters())
-        ps = [sd[n] for n in _TNERF_ORDER]
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self._pack_bwd_key:
-            L = _lib.lib()
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_bwd_tnerf_floats(), dtype=torch.float32, device=ps[0].device)
-            _lib.check(L.swnerf_pack_net_bwd_tnerf(arr, *bands, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net_bwd_tnerf")
-            self._packed_bwd, self._pack_bwd_key = buf, key
-        return self._packed_bwd
+        return packing.pack_weights(self._pack_cache, "bwd", _named(self, _TNERF_ORDER), lambda L: L.swnerf_packed_bwd_tnerf_floats(),
+                                    lambda L, arr, buf, st: L.swnerf_pack_net_bwd_tnerf(arr, *bands, buf, st), "pack_net_bwd_tnerf")
 
     def forward(self, inp, vdir, dyn_t):
         from .generic import tnerf_forward
@@ -545,16 +489,6 @@ class TNeRF(nn.Module):
         if bands is None:
             raise NotImplementedError("swnerf: the fused T-NeRF pass is built for depth 8, net_dim 128, skip_layer 4 with "
                                       "get_embedder-sized inputs (L_pos, L_time <= 10, 1 <= L_dir <= 4)")
-        sd = dict(self.named_parameters())
-        ps = [sd[n] for n in _TNERF_ORDER]
-        if not ps[0].is_cuda:
-            raise RuntimeError("swnerf: module parameters must be on the GPU (call .to('cuda')); no CPU fallback")
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self._pack_key:
-            L = _lib.lib()
-            ps32 = [p.detach() if (p.dtype == torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in ps]
-            arr = (ctypes.c_void_p * len(ps32))(*[p.data_ptr() for p in ps32])
-            buf = torch.empty(L.swnerf_packed_floats(_lib.NET_TNERF), dtype=torch.float32, device=ps[0].device)
-            _lib.check(L.swnerf_pack_net(_lib.NET_TNERF, arr, *bands, _lib.ptr(buf), _lib.stream_of(buf)), "pack_net")
-            self._packed, self._pack_key = buf, key
-        return (_lib.NET_TNERF, self._packed) + bands
+        buf = packing.pack_weights(self._pack_cache, "fwd", _named(self, _TNERF_ORDER), lambda L: L.swnerf_packed_floats(_lib.NET_TNERF),
+                                   lambda L, arr, buf, st: L.swnerf_pack_net(_lib.NET_TNERF, arr, *bands, buf, st), "pack_net")
+        return (_lib.NET_TNERF, buf) + bands

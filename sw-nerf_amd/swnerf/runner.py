@@ -6,11 +6,13 @@ written against the reference only swaps its imports.  `args` is any object with
 `render.fused_plan` finds the encoders and sends `render_rays` to the fused HIP pass.
 `render_test` and `evaluate_dir` are what follows the render path: the reference's scoring of test renders
 (nerf/run.py:557-596 with calculate_metrics :49-61, and the last cell of d_nerf/metrics.ipynb) on the GPU metrics.
-`train` and `train_dnerf` are the two runners' training loops from `create_nerf` on, with the batch and the loss made on the
-device (swnerf.batching)."""
+`train`, `train_dnerf` and `train_tnerf` are the runners' training loops from `create_nerf` on, with the batch and the loss made
+on the device (swnerf.batching): one loop (`_train_loop`), and per runner its draw, render, extra loss and test-set
+render."""
 import json
 import os
 import random
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -23,14 +25,12 @@ from .embedder import get_embedder
 from .model import vallina_NeRF, NeRF, TNeRF
 
 
-def _render_kwargs(args, network_query_fn, model, model_fine, extra=None):
+def _render_kwargs(args, network_query_fn, nets, extra=None):
+    """(train, test) dictionaries.  nets: the runner's entries between 'perturb' and 'use_viewdirs', in its key order."""
     kw = {
         'network_query_fn': network_query_fn,
         'perturb': args.perturb,
-        'N_importance': args.N_importance,
-        'network_fine': model_fine,
-        'N_samples': args.N_samples,
-        'network_fn': model,
+        **nets,
         'use_viewdirs': args.use_viewdirs,
         'white_bkgd': args.white_bkgd,
         'raw_noise_std': args.raw_noise_std,
@@ -43,6 +43,35 @@ def _render_kwargs(args, network_query_fn, model, model_fine, extra=None):
     test['perturb'] = False                                      # nerf/run.py:301-303
     test['raw_noise_std'] = 0.
     return kw, test
+
+
+def _coarse_fine(args, model, model_fine):
+    return {'N_importance': args.N_importance, 'network_fine': model_fine, 'N_samples': args.N_samples, 'network_fn': model}
+
+
+def _refuse_half_precision(args, creator):
+    if getattr(args, "do_half_precision", False):
+        raise NotImplementedError(f"swnerf.{creator}: do_half_precision (apex amp) is not built; the HIP path is fp32")
+
+
+def _timed_encoders(args, pos, time, views):
+    """The encoders of a runner with frame times, each from (multires, i_embed); `views` is a callable: its options are read
+    only with use_viewdirs.  -> embed_fn, embedtime_fn, embeddirs_fn, input_ch, input_ch_time, input_ch_views"""
+    embed_fn, input_ch = get_embedder(pos[0], 3, pos[1])
+    embedtime_fn, input_ch_time = get_embedder(time[0], 1, time[1])
+    input_ch_views, embeddirs_fn = 0, None
+    if args.use_viewdirs:
+        multires_views, i_embed = views()
+        embeddirs_fn, input_ch_views = get_embedder(multires_views, 3, i_embed)
+    return embed_fn, embedtime_fn, embeddirs_fn, input_ch, input_ch_time, input_ch_views
+
+
+def _timed_query_fn(run_network, embed_fn, embeddirs_fn, embedtime_fn, netchunk, discr):
+    # render.closure_embedders and render_tnerf._time_discr read embed_fn, embeddirs_fn, embedtime_fn and discr out of this lambda's
+    # closure BY NAME: renaming one sends every render to the op path without an error
+    return lambda inputs, viewdirs, ts, network_fn: run_network(
+        inputs, viewdirs, ts, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, embedtime_fn=embedtime_fn,
+        netchunk=netchunk, embd_time_discr=discr)
 
 
 def _device(device):
@@ -74,21 +103,13 @@ def create_nerf(args, device=None):
     optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start, _ = reload_latest(args.basedir, args.expname, model, model_fine, optimizer, ft_path=args.ft_path,
                              no_reload=args.no_reload, map_location=device)
-    train, test = _render_kwargs(args, network_query_fn, model, model_fine)
+    train, test = _render_kwargs(args, network_query_fn, _coarse_fine(args, model, model_fine))
     return train, test, start, grad_vars, optimizer
 
 
-def create_dnerf(args, device=None):
-    """d_nerf/run_dnerf.py:238-352 (`create_nerf` of the D-NeRF runner): `NeRF.get_by_name(args.nerf_type, ...)`,
-    the time encoder, `use_two_models_for_fine`.  fp32 only: `do_half_precision` (apex amp) is refused."""
-    if getattr(args, "do_half_precision", False):
-        raise NotImplementedError("swnerf.create_dnerf: do_half_precision (apex amp) is not built; the HIP path is fp32")
-    device = _device(device)
-    embed_fn, input_ch = get_embedder(args.multires, 3, args.i_embed)
-    embedtime_fn, input_ch_time = get_embedder(args.multires, 1, args.i_embed)
-    input_ch_views, embeddirs_fn = 0, None
-    if args.use_viewdirs:
-        embeddirs_fn, input_ch_views = get_embedder(args.multires_views, 3, args.i_embed)
+def _create_dnerf(args, device, encoders, load, reproducible_wgrad=None):
+    """The D-NeRF pair behind create_dnerf and every level of create_multires.  load(model, model_fine, optimizer) -> start."""
+    embed_fn, embedtime_fn, embeddirs_fn, input_ch, input_ch_time, input_ch_views = encoders
     output_ch = 5 if args.N_importance > 0 else 4
     skips = [4]
     make = lambda D, W: NeRF.get_by_name(args.nerf_type, D=D, W=W, input_ch=input_ch, output_ch=output_ch, skips=skips,
@@ -101,56 +122,50 @@ def create_dnerf(args, device=None):
     if args.use_two_models_for_fine:
         model_fine = make(args.netdepth_fine, args.netwidth_fine)
         grad_vars += list(model_fine.parameters())
-    netchunk, discr = args.netchunk, args.nerf_type != "temporal"
-    network_query_fn = lambda inputs, viewdirs, ts, network_fn: render_dnerf.run_network(
-        inputs, viewdirs, ts, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, embedtime_fn=embedtime_fn,
-        netchunk=netchunk, embd_time_discr=discr)
+    network_query_fn = _timed_query_fn(render_dnerf.run_network, embed_fn, embeddirs_fn, embedtime_fn, args.netchunk,
+                                       args.nerf_type != "temporal")
+    if reproducible_wgrad is not None:                       # generic.py: weight gradients summed in a fixed order, equal bits every pass
+        for net in (model, model_fine):
+            if net is not None:
+                net.reproducible_wgrad = reproducible_wgrad
     optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
-    start, _ = reload_latest(args.basedir, args.expname, model, model_fine, optimizer, ft_path=args.ft_path,
-                             no_reload=args.no_reload, map_location=device)
-    train, test = _render_kwargs(args, network_query_fn, model, model_fine,
+    start = load(model, model_fine, optimizer)
+    train, test = _render_kwargs(args, network_query_fn, _coarse_fine(args, model, model_fine),
                                  {'use_two_models_for_fine': args.use_two_models_for_fine})
     return train, test, start, grad_vars, optimizer
+
+
+def _reload(args, device):
+    return lambda model, model_fine, optimizer: reload_latest(args.basedir, args.expname, model, model_fine, optimizer, ft_path=args.ft_path,
+                                                              no_reload=args.no_reload, map_location=device)[0]
+
+
+def create_dnerf(args, device=None):
+    """d_nerf/run_dnerf.py:238-352 (`create_nerf` of the D-NeRF runner): `NeRF.get_by_name(args.nerf_type, ...)`,
+    the time encoder, `use_two_models_for_fine`.  fp32 only: `do_half_precision` (apex amp) is refused."""
+    _refuse_half_precision(args, "create_dnerf")
+    device = _device(device)
+    pos = (args.multires, args.i_embed)
+    return _create_dnerf(args, device, _timed_encoders(args, pos, pos, lambda: (args.multires_views, args.i_embed)), _reload(args, device))
 
 
 def create_tnerf(args, device=None):
     """t_nerf/run_tnerf.py:238-345 (`create_nerf` of the T-NeRF runner): one TNeRF (width 128, skip_layer 4, depth
     args.netdepth), the time encoder at args.multires, N_importance forced to 0.  fp32 only: `do_half_precision` is refused."""
-    if getattr(args, "do_half_precision", False):
-        raise NotImplementedError("swnerf.create_tnerf: do_half_precision (apex amp) is not built; the HIP path is fp32")
+    _refuse_half_precision(args, "create_tnerf")
     device = _device(device)
-    embed_fn, input_ch = get_embedder(args.multires, 3, args.i_embed)
-    embedtime_fn, input_ch_time = get_embedder(args.multires, 1, args.i_embed)
-    input_ch_views, embeddirs_fn = 0, None
-    if args.use_viewdirs:
-        embeddirs_fn, input_ch_views = get_embedder(args.multires_views, 3, args.i_embed)
+    pos = (args.multires, args.i_embed)
+    embed_fn, embedtime_fn, embeddirs_fn, input_ch, input_ch_time, input_ch_views = _timed_encoders(
+        args, pos, pos, lambda: (args.multires_views, args.i_embed))
     model = TNeRF(depth=args.netdepth, in_feat=input_ch, dir_feat=input_ch_views, time_feat=input_ch_time, net_dim=128,
                   skip_layer=4).to(device)
     grad_vars = list(model.parameters())
-    netchunk, discr = args.netchunk, args.nerf_type != "temporal"
-    network_query_fn = lambda inputs, viewdirs, ts, network_fn: render_tnerf.run_network(
-        inputs, viewdirs, ts, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, embedtime_fn=embedtime_fn,
-        netchunk=netchunk, embd_time_discr=discr)
+    network_query_fn = _timed_query_fn(render_tnerf.run_network, embed_fn, embeddirs_fn, embedtime_fn, args.netchunk,
+                                       args.nerf_type != "temporal")
     optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
-    start, _ = reload_latest(args.basedir, args.expname, model, None, optimizer, ft_path=args.ft_path,
-                             no_reload=args.no_reload, map_location=device)
-    kw = {
-        'network_query_fn': network_query_fn,
-        'perturb': args.perturb,
-        'N_importance': 0,
-        'network_fn': model,
-        'N_samples': args.N_samples,
-        'use_viewdirs': args.use_viewdirs,
-        'white_bkgd': args.white_bkgd,
-        'raw_noise_std': args.raw_noise_std,
-    }
-    if args.dataset_type != 'llff' or args.no_ndc:               # run_tnerf.py:336-338
-        kw['ndc'] = False
-        kw['lindisp'] = args.lindisp
-    test = {k: kw[k] for k in kw}
-    test['perturb'] = False
-    test['raw_noise_std'] = 0.
-    return kw, test, start, grad_vars, optimizer
+    start = _reload(args, device)(model, None, optimizer)
+    train, test = _render_kwargs(args, network_query_fn, {'N_importance': 0, 'network_fn': model, 'N_samples': args.N_samples})
+    return train, test, start, grad_vars, optimizer
 
 
 def create_fit2d(args, device=None):
@@ -181,55 +196,22 @@ def create_multires(args, device=None):
     shape: they run layer by layer on the generic kernels (swnerf/generic.py).  args.reproducible_wgrad (extra, optional,
     default False): the nets' weight gradients add their row slices in a fixed order (swnerf_gemm_tn_ordered) instead of with
     float atomics, so that a backward pass repeats bit for bit - slower on large batches.  fp32 only."""
-    if getattr(args, "do_half_precision", False):
-        raise NotImplementedError("swnerf.create_multires: do_half_precision (apex amp) is not built; the HIP path is fp32")
+    _refuse_half_precision(args, "create_multires")
     if not 1 <= args.layer_num <= len(MULTIRES_CHANNELS):
         raise ValueError(f"swnerf.create_multires: layer_num must be 1..{len(MULTIRES_CHANNELS)}, got {args.layer_num}")
     device = _device(device)
     ckpts = find_checkpoints(args.basedir, args.expname, args.ft_path)
     trains, tests, starts, grads, optimizers = [], [], [], [], []
-    for layer in range(args.layer_num):
-        train, test, start, grad_vars, optimizer = _create_multires_level(args, MULTIRES_CHANNELS[layer], layer, device, ckpts)
-        trains.append(train)
-        tests.append(test)
-        starts.append(start)
-        grads.append(grad_vars)
-        optimizers.append(optimizer)
+    for layer, (L_pos, L_time, L_views) in enumerate(MULTIRES_CHANNELS[:args.layer_num]):
+        def load(model, model_fine, optimizer):
+            if len(ckpts) > 0 and not args.no_reload:
+                return load_multires(ckpts[-1], layer, model, model_fine, optimizer, map_location=device)
+            return 0
+        encoders = _timed_encoders(args, (L_pos, L_pos), (L_time, L_time), lambda: (L_views, L_views))
+        level = _create_dnerf(args, device, encoders, load, bool(getattr(args, "reproducible_wgrad", False)))
+        for out, part in zip((trains, tests, starts, grads, optimizers), level):
+            out.append(part)
     return trains, tests, starts, grads, optimizers
-
-
-def _create_multires_level(args, channels, layer, device, ckpts):
-    embed_fn, input_ch = get_embedder(channels[0], 3, channels[0])
-    embedtime_fn, input_ch_time = get_embedder(channels[1], 1, channels[1])
-    input_ch_views, embeddirs_fn = 0, None
-    if args.use_viewdirs:
-        embeddirs_fn, input_ch_views = get_embedder(channels[2], 3, channels[2])
-    output_ch = 5 if args.N_importance > 0 else 4
-    skips = [4]
-    make = lambda D, W: NeRF.get_by_name(args.nerf_type, D=D, W=W, input_ch=input_ch, output_ch=output_ch, skips=skips,
-                                         input_ch_views=input_ch_views, input_ch_time=input_ch_time,
-                                         use_viewdirs=args.use_viewdirs, embed_fn=embed_fn,
-                                         zero_canonical=not args.not_zero_canonical).to(device)
-    model = make(args.netdepth, args.netwidth)
-    grad_vars = list(model.parameters())
-    model_fine = None
-    if args.use_two_models_for_fine:
-        model_fine = make(args.netdepth_fine, args.netwidth_fine)
-        grad_vars += list(model_fine.parameters())
-    netchunk, discr = args.netchunk, args.nerf_type != "temporal"
-    network_query_fn = lambda inputs, viewdirs, ts, network_fn: render_dnerf.run_network(
-        inputs, viewdirs, ts, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, embedtime_fn=embedtime_fn,
-        netchunk=netchunk, embd_time_discr=discr)
-    for net in (model, model_fine):
-        if net is not None:                                  # generic.py: weight gradients summed in a fixed order, equal bits every pass
-            net.reproducible_wgrad = bool(getattr(args, "reproducible_wgrad", False))
-    optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
-    start = 0
-    if len(ckpts) > 0 and not args.no_reload:
-        start = load_multires(ckpts[-1], layer, model, model_fine, optimizer, map_location=device)
-    train, test = _render_kwargs(args, network_query_fn, model, model_fine,
-                                 {'use_two_models_for_fine': args.use_two_models_for_fine})
-    return train, test, start, grad_vars, optimizer
 
 
 def pyramid_hwf(hwf, layer_num):
@@ -451,7 +433,7 @@ def _opt(args, name, default):
 
 def _train_common(args, d, device, sampler, loss_fn, create, timed):
     """create: the runner's creator (create_nerf / create_dnerf / create_tnerf); timed: the D-NeRF and T-NeRF runners build rays
-    from hwf's focal and carry the frame time in column 8."""
+    from hwf's focal and carry the frame time in column 8.  -> what the loop and its four callables work on."""
     from . import batching
     if sampler not in ("device", "numpy"):
         raise ValueError(f"swnerf.runner.train: sampler must be 'device' or 'numpy', got {sampler!r}")
@@ -466,7 +448,9 @@ def _train_common(args, d, device, sampler, loss_fn, create, timed):
                                   ndc=train_kw.get('ndc', True), use_viewdirs=train_kw['use_viewdirs'], white_bkgd=args.white_bkgd,
                                   seed=_opt(args, 'seed', 0), device=device)
     rays_kw = {k: v for k, v in train_kw.items() if k not in _RENDER_ONLY_KEYS}
-    return device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, (loss_fn or batching.photometric_loss)
+    return SimpleNamespace(device=device, train_kw=train_kw, test_kw=test_kw, start=start, optimizer=optimizer, i_train=i_train,
+                           batcher=batcher, rays_kw=rays_kw, loss_fn=loss_fn or batching.photometric_loss, sampler=sampler,
+                           chunk=_opt(args, 'chunk', 1024 * 32))
 
 
 def _image_draw(args, batcher, i, img_i, sampler, N_rand):
@@ -498,6 +482,49 @@ def _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw
         hooks['on_step'](i, optimizer)
 
 
+def _curriculum_draw(args, s):
+    """draw(i) of the runners with frame times: one image among the first frames the time curriculum admits at iteration i
+    (run_dnerf.py:650-655), then a no_batching batch of it."""
+    from .batching import time_curriculum_max
+
+    def draw(i):
+        max_sample = time_curriculum_max(i, _opt(args, 'precrop_iters_time', 0), len(s.i_train))
+        img_i = np.random.choice(s.i_train if max_sample is None else s.i_train[:max_sample])
+        return (img_i,) + _image_draw(args, s.batcher, i, img_i, s.sampler, args.N_rand)
+    return draw
+
+
+def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset, extra_loss=None):
+    """Iterations s.start + 1 .. last_iter of the three runners.  What differs between them comes as callables:
+    draw(i) -> (img_i, ray_batch, target, ids); render_batch(i, img_i, ray_batch) -> (rgb, rgb0 for loss_fn, state);
+    extra_loss(state) -> a term added to loss_fn's loss before backward, or None for none; render_testset(i_test, poses_test, gt_imgs,
+    savedir) under no_grad every i_testset iterations.  -> the per-step record."""
+    hooks = hooks or {}
+    i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
+    global_step = s.start
+    record = _Record()
+    for i in range(s.start + 1, last_iter + 1):
+        img_i, ray_batch, target_s, ids = draw(i)
+        if 'on_batch' in hooks:
+            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
+        rgb, rgb0, state = render_batch(i, img_i, ray_batch)
+        s.optimizer.zero_grad()
+        loss, img_loss, img_loss0 = s.loss_fn(rgb, target_s, rgb0)
+        if extra_loss is not None:
+            loss = loss + extra_loss(state)
+        loss.backward()
+        s.optimizer.step()
+        _step_tail(args, i, global_step, s.optimizer, record, loss, img_loss, s.train_kw, hooks)
+        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
+            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
+            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(s.device)
+            with torch.no_grad():
+                render_testset(i_test, poses_test, _gt_rgb(d['images'], i_test, args.white_bkgd), testsavedir)
+            print('Saved test set')
+        global_step += 1
+    return record.flush()
+
+
 def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
     """The training loop of nerf/run.py:598-796 from `create_nerf` on: a batch from swnerf.batching.RayBatcher (use_batching
     over all training rays, or no_batching from one image with the precrop window), the render of the PACKED batch
@@ -513,39 +540,22 @@ def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
     hooks: {'on_batch': f(i, img_i, ray_batch, target, ids), 'on_step': f(i, optimizer)}.
     -> the per-step record: a list of {'step', 'loss', 'psnr', 'lr'}."""
     d = _train_data(data, False)
-    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, create_nerf, False)
-    H, W, focal = d['hwf']
-    N_rand = args.N_rand
-    use_batching = not args.no_batching
-    N_iters = _opt(args, 'N_iters', 200000) + 1
-    global_step = start
-    record = _Record()
-    for i in range(start + 1, N_iters):
-        if use_batching:
-            img_i = None
-            ray_batch, target_s, ids = batcher.global_batch(N_rand, return_ids=True)
-        else:
-            img_i = np.random.choice(i_train)
-            ray_batch, target_s, ids = _image_draw(args, batcher, i, img_i, sampler, N_rand)
-        if hooks and 'on_batch' in hooks:
-            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
-        all_ret = render.batchify_rays(ray_batch, _opt(args, 'chunk', 1024 * 32), retraw=True, **rays_kw)
+    s = _train_common(args, d, device, sampler, loss_fn, create_nerf, False)
+
+    def draw(i):
+        if not args.no_batching:
+            return (None,) + s.batcher.global_batch(args.N_rand, return_ids=True)
+        img_i = np.random.choice(s.i_train)
+        return (img_i,) + _image_draw(args, s.batcher, i, img_i, s.sampler, args.N_rand)
+
+    def render_batch(i, img_i, ray_batch):
+        all_ret = render.batchify_rays(ray_batch, s.chunk, retraw=True, **s.rays_kw)
         rgb, disp, acc, extras = render.image_outputs(all_ret, (ray_batch.shape[0], 3))
-        optimizer.zero_grad()
-        loss, img_loss, img_loss0 = loss_fn(rgb, target_s, extras.get('rgb0'))
-        loss.backward()
-        optimizer.step()
-        _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks)
-        i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
-        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
-            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
-            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
-            with torch.no_grad():
-                render_test(poses_test, d['hwf'], d['K'], _opt(args, 'chunk', 1024 * 32), test_kw,
-                            _gt_rgb(d['images'], i_test, args.white_bkgd), testsavedir)
-            print('Saved test set')
-        global_step += 1
-    return record.flush()
+        return rgb, extras.get('rgb0'), None
+
+    def render_testset(i_test, poses_test, gt_imgs, savedir):
+        render_test(poses_test, d['hwf'], d['K'], s.chunk, s.test_kw, gt_imgs, savedir)
+    return _train_loop(args, d, s, _opt(args, 'N_iters', 200000), hooks, draw, render_batch, render_testset)
 
 
 def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
@@ -556,34 +566,23 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  args.N_iter is the last iteration.
     hooks: those of `train`, and 'on_tv': f(i, which, ray_batch_other, z_vals) before each prev / next render."""
     d = _train_data(data, True)
-    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, create_dnerf, True)
-    N_rand = args.N_rand
     if not args.no_batching:
         raise NotImplementedError("Time not implemented")                        # run_dnerf.py:634
-    N_iters = _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)) + 1
-    times = batcher.times_host
-    chunk = _opt(args, 'chunk', 1024 * 32)
+    s = _train_common(args, d, device, sampler, loss_fn, create_dnerf, True)
+    times = s.batcher.times_host
     add_tv = bool(_opt(args, 'add_tv_loss', False))
-    from .batching import time_curriculum_max
 
     def render_packed(rb, t_host, **more):
         # the frame time is known here as the kernels read it (float32): no device->host read per chunk (render_dnerf._TIME_HINT)
         token = render_dnerf._TIME_HINT.set((rb.untyped_storage().data_ptr(), float(t_host)))
         try:
-            all_ret = render_dnerf.batchify_rays(rb, chunk, retraw=True, **more, **rays_kw)
+            all_ret = render_dnerf.batchify_rays(rb, s.chunk, retraw=True, **more, **s.rays_kw)
         finally:
             render_dnerf._TIME_HINT.reset(token)
         return render.image_outputs(all_ret, (rb.shape[0], 3))
 
-    global_step = start
-    record = _Record()
-    for i in range(start + 1, N_iters):
-        max_sample = time_curriculum_max(i, _opt(args, 'precrop_iters_time', 0), len(i_train))
-        img_i = np.random.choice(i_train if max_sample is None else i_train[:max_sample])
-        ray_batch, target_s, ids = _image_draw(args, batcher, i, img_i, sampler, N_rand)
+    def render_batch(i, img_i, ray_batch):
         frame_time = times[img_i]
-        if hooks and 'on_batch' in hooks:
-            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
         rgb, disp, acc, extras = render_packed(ray_batch, frame_time)
         others = []
         if add_tv:
@@ -599,33 +598,27 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
                     continue
                 u = np.float32(torch.rand(1)[0].item())
                 rand_time = other + (frame_time - other) * u if which == 'prev' else frame_time + (other - frame_time) * u
-                rb_other = batcher.with_time(ray_batch, float(rand_time))
+                rb_other = s.batcher.with_time(ray_batch, float(rand_time))
                 z = extras['z_vals'].detach()
                 if hooks and 'on_tv' in hooks:
                     hooks['on_tv'](i, which, rb_other, z)
                 others.append(render_packed(rb_other, np.float32(rand_time), z_vals=z)[3])
-        optimizer.zero_grad()
-        loss, img_loss, img_loss0 = loss_fn(rgb, target_s, extras.get('rgb0'))
-        if add_tv:
-            tv_loss = 0
-            for ex in others:
-                tv_loss = tv_loss + ((extras['position_delta'] - ex['position_delta']).pow(2)).sum()
-                if 'position_delta_0' in extras:
-                    tv_loss = tv_loss + ((extras['position_delta_0'] - ex['position_delta_0']).pow(2)).sum()
-            loss = loss + tv_loss * args.tv_loss_weight
-        loss.backward()
-        optimizer.step()
-        _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks)
-        i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
-        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
-            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
-            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
-            with torch.no_grad():
-                render_dnerf.render_path(poses_test, torch.as_tensor(times[i_test]).to(device), d['hwf'], chunk, test_kw,
-                                         gt_imgs=_gt_rgb(d['images'], i_test, args.white_bkgd), savedir=testsavedir)
-            print('Saved test set')
-        global_step += 1
-    return record.flush()
+        return rgb, extras.get('rgb0'), (extras, others)
+
+    def tv_loss(state):
+        extras, others = state
+        tv = 0
+        for ex in others:
+            tv = tv + ((extras['position_delta'] - ex['position_delta']).pow(2)).sum()
+            if 'position_delta_0' in extras:
+                tv = tv + ((extras['position_delta_0'] - ex['position_delta_0']).pow(2)).sum()
+        return tv * args.tv_loss_weight
+
+    def render_testset(i_test, poses_test, gt_imgs, savedir):
+        render_dnerf.render_path(poses_test, torch.as_tensor(times[i_test]).to(s.device), d['hwf'], s.chunk, s.test_kw,
+                                 gt_imgs=gt_imgs, savedir=savedir)
+    return _train_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks, _curriculum_draw(args, s), render_batch,
+                       render_testset, tv_loss if add_tv else None)
 
 
 def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
@@ -640,35 +633,15 @@ def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     if not args.no_batching:
         raise NotImplementedError("swnerf.runner.train_tnerf: use_batching is not built - the reference's branch (run_tnerf.py:631-642) "
                                   "draws rays that carry no frame time and cannot run; pass no_batching=True")
-    device, train_kw, test_kw, start, optimizer, i_train, batcher, rays_kw, loss_fn = _train_common(args, d, device, sampler, loss_fn, create_tnerf, True)
-    N_rand = args.N_rand
-    N_iters = _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)) + 1
-    times = batcher.times_host
-    chunk = _opt(args, 'chunk', 1024 * 32)
+    s = _train_common(args, d, device, sampler, loss_fn, create_tnerf, True)
+    times = s.batcher.times_host
     fused = bool(_opt(args, 'fused_train', True))
-    from .batching import time_curriculum_max
-    global_step = start
-    record = _Record()
-    for i in range(start + 1, N_iters):
-        max_sample = time_curriculum_max(i, _opt(args, 'precrop_iters_time', 0), len(i_train))
-        img_i = np.random.choice(i_train if max_sample is None else i_train[:max_sample])
-        ray_batch, target_s, ids = _image_draw(args, batcher, i, img_i, sampler, N_rand)
-        if hooks and 'on_batch' in hooks:
-            hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
-        all_ret = render_tnerf.batchify_rays(ray_batch, chunk, retraw=True, fused_train=fused, **rays_kw)
-        rgb, disp, acc, extras = render.image_outputs(all_ret, (ray_batch.shape[0], 3))
-        optimizer.zero_grad()
-        loss, img_loss, img_loss0 = loss_fn(rgb, target_s, None)
-        loss.backward()
-        optimizer.step()
-        _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks)
-        i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
-        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
-            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
-            poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(device)
-            with torch.no_grad():
-                render_tnerf.render_path(poses_test, [float(t) for t in times[i_test]], d['hwf'], chunk, test_kw,
-                                         gt_imgs=_gt_rgb(d['images'], i_test, args.white_bkgd), savedir=testsavedir)
-            print('Saved test set')
-        global_step += 1
-    return record.flush()
+
+    def render_batch(i, img_i, ray_batch):
+        all_ret = render_tnerf.batchify_rays(ray_batch, s.chunk, retraw=True, fused_train=fused, **s.rays_kw)
+        return render.image_outputs(all_ret, (ray_batch.shape[0], 3))[0], None, None
+
+    def render_testset(i_test, poses_test, gt_imgs, savedir):
+        render_tnerf.render_path(poses_test, [float(t) for t in times[i_test]], d['hwf'], s.chunk, s.test_kw, gt_imgs=gt_imgs, savedir=savedir)
+    return _train_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks, _curriculum_draw(args, s), render_batch,
+                       render_testset)
