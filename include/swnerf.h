@@ -613,6 +613,35 @@ int swnerf_train_batch(const void* images, int images_u8, int channels, int64_t 
 int swnerf_photo_loss(const float* rgb, const float* rgb0 /* may be NULL */, const float* target, int64_t N, double* sums,
                       float* losses /* may be NULL */, float* d_rgb /* may be NULL */, float* d_rgb0 /* may be NULL */, void* stream);
 
+/* ---- the optimizer: one Adam / AdamW step over a list of tensors (csrc/optim_kernels.hip) ---------------------
+ * adam_step: tensor i of the list is p[i], g[i], m[i] (exp_avg), v[i] (exp_avg_sq): DEVICE float [n[i]], fp32, dense; the pointer
+ *   arrays, n, step, lr and weight_decay are HOST arrays of n_tensors entries.  step[i] >= 1 is tensor i's step count INCLUDING this
+ *   update (torch's state['step'] after its increment); the bias corrections are formed from it in double.  In fp32, each operation
+ *   rounded, the lines of torch's single-tensor Adam:
+ *     g' = g * grad_scale;   decoupled != 0 (AdamW): p = p (1 - lr wd)   else with wd != 0 (L2): g' = g' + wd p
+ *     m = m + (g' - m)(1 - beta1);   v = beta2 v + (1 - beta2) g' g'
+ *     p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   amsgrad, maximize and capturable are not built.  The list is cut into launches of at most SWNERF_ADAM_MAX_TENSORS tensors and
+ *   SWNERF_ADAM_MAX_BLOCKS blocks of SWNERF_ADAM_CHUNK elements each (a launch that one tensor fills alone: up to 16 x that), each
+ *   launch described by ONE by-value kernel argument; nothing is copied to the device.  A thread moves 4 floats per 16-byte access
+ *   when p, g, m and v of its tensor are all 16-byte aligned, else 1; tails are masked.  n_tensors == 0 and n[i] == 0 launch nothing.
+ *   SWNERF_E_ARG before anything touches the device: NULL pointer (of a tensor with n[i] > 0), negative count, n[i] > 2^40, lr,
+ *   weight_decay or eps negative or not finite, beta outside [0, 1), step < 1, grad_scale not finite.
+ * adam_plan: the same cut without a device, one row per block: launch[r], tensor[r], start[r] (first element), count[r] (elements).
+ *   Returns the number of rows (rows beyond `capacity` are counted, not written), or SWNERF_E_ARG.
+ * adam_caps: the three constants below and the size of the kernel argument in bytes (each pointer may be NULL). */
+#define SWNERF_ADAM_MAX_TENSORS 32
+#define SWNERF_ADAM_MAX_BLOCKS  320
+#define SWNERF_ADAM_CHUNK       4096
+#define SWNERF_ADAM_MAX_ELEMS   ((int64_t)1 << 40)
+int swnerf_adam_step(int n_tensors, float* const* p /*HOST*/, const float* const* g /*HOST*/, float* const* m /*HOST*/,
+                     float* const* v /*HOST*/, const int64_t* n /*HOST*/, const double* step /*HOST*/, const double* lr /*HOST*/,
+                     const double* weight_decay /*HOST*/, double beta1, double beta2, double eps, int decoupled, float grad_scale,
+                     void* stream);
+int64_t swnerf_adam_plan(int n_tensors, const int64_t* n /*HOST*/, int64_t capacity, int32_t* launch, int32_t* tensor, int64_t* start,
+                         int64_t* count);
+void swnerf_adam_caps(int* max_tensors, int* max_blocks, int64_t* chunk, size_t* descriptor_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,8 @@ EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swner
            "swnerf_fit2d_loss", "swnerf_fit2d_packed_floats", "swnerf_pack_fit2d", "swnerf_fit2d_forward", "swnerf_fit2d_picture",
            "swnerf_perm_indices", "swnerf_train_batch", "swnerf_photo_loss",
            "swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_render_pass_train_tnerf",
-           "swnerf_packed_bwd_tnerf_floats", "swnerf_pack_net_bwd_tnerf", "swnerf_render_pass_backward_tnerf", "swnerf_tnerf_feature_finish"]
+           "swnerf_packed_bwd_tnerf_floats", "swnerf_pack_net_bwd_tnerf", "swnerf_render_pass_backward_tnerf", "swnerf_tnerf_feature_finish",
+           "swnerf_adam_step", "swnerf_adam_plan", "swnerf_adam_caps"]
 BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
 
 
@@ -203,6 +204,11 @@ def lib():
                         "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes", "swnerf_gemm_tn_ordered_ws_floats",
                         "swnerf_bn_workspace_bytes", "swnerf_fit2d_packed_floats"):
             getattr(L, name).restype = c_int
+    L.swnerf_adam_step.argtypes = [c_int] + [c_void_p] * 8 + [c_double, c_double, c_double, c_int, ctypes.c_float, c_void_p]
+    L.swnerf_adam_plan.restype = c_int64
+    L.swnerf_adam_plan.argtypes = [c_int, c_void_p, c_int64] + [c_void_p] * 4
+    L.swnerf_adam_caps.restype = None
+    L.swnerf_adam_caps.argtypes = [POINTER(c_int), POINTER(c_int), POINTER(c_int64), POINTER(c_size_t)]
     if L.swnerf_version() != 112:
         raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 112 - rebuild it "
                            "(python __graft_entry__.py)")

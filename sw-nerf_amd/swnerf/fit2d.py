@@ -6,7 +6,7 @@ in front).  There is no fused training pass: batch statistics couple all rows of
 hidden_dim 256 / output_dim 3 / input_dimension 4L + 2 (L <= 23) is one fused launch with every BatchNorm1d folded into the
 next Linear (swnerf_pack_fit2d, swnerf_fit2d_forward / swnerf_fit2d_picture); any other eval shape runs layer by layer
 (linear with the ReLU epilogue, then swnerf_bn_apply).  Parameters on the CPU are an error: there is no CPU fallback.
-AdamW and ExponentialLR stay torch's (plumbing, like Adam in every runner)."""
+ExponentialLR stays torch's, and AdamW by default (runner.create_fit2d with args.optimizer = "fused": swnerf.optim.AdamW)."""
 import os
 import time
 

@@ -80,6 +80,19 @@ def _device(device):
     return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
 
 
+def _make_optimizer(args, creator, params, adamw=False, **kw):
+    """Adam (AdamW with adamw) over `params`: torch.optim's, or with args.optimizer == "fused" (extra, default "torch") the
+    multi-tensor HIP step of swnerf.optim - the same arithmetic, state and checkpoints."""
+    which = _opt(args, 'optimizer', 'torch')
+    if which == 'torch':
+        mod = torch.optim
+    elif which == 'fused':
+        from . import optim as mod
+    else:
+        raise ValueError(f"swnerf.{creator}: optimizer must be 'torch' or 'fused', got {which!r}")
+    return (mod.AdamW if adamw else mod.Adam)(params, **kw)
+
+
 def create_nerf(args, device=None):
     """nerf/run.py:222-313 (static NeRF: coarse `vallina_NeRF` + fine one when N_importance > 0)."""
     device = _device(device)
@@ -100,14 +113,14 @@ def create_nerf(args, device=None):
     netchunk = args.netchunk
     network_query_fn = lambda inputs, viewdirs, network_fn: render.run_network(
         inputs, viewdirs, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, netchunk=netchunk)
-    optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
+    optimizer = _make_optimizer(args, "create_nerf", grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start, _ = reload_latest(args.basedir, args.expname, model, model_fine, optimizer, ft_path=args.ft_path,
                              no_reload=args.no_reload, map_location=device)
     train, test = _render_kwargs(args, network_query_fn, _coarse_fine(args, model, model_fine))
     return train, test, start, grad_vars, optimizer
 
 
-def _create_dnerf(args, device, encoders, load, reproducible_wgrad=None):
+def _create_dnerf(args, device, encoders, load, reproducible_wgrad=None, creator="create_dnerf"):
     """The D-NeRF pair behind create_dnerf and every level of create_multires.  load(model, model_fine, optimizer) -> start."""
     embed_fn, embedtime_fn, embeddirs_fn, input_ch, input_ch_time, input_ch_views = encoders
     output_ch = 5 if args.N_importance > 0 else 4
@@ -128,7 +141,7 @@ def _create_dnerf(args, device, encoders, load, reproducible_wgrad=None):
         for net in (model, model_fine):
             if net is not None:
                 net.reproducible_wgrad = reproducible_wgrad
-    optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
+    optimizer = _make_optimizer(args, creator, grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start = load(model, model_fine, optimizer)
     train, test = _render_kwargs(args, network_query_fn, _coarse_fine(args, model, model_fine),
                                  {'use_two_models_for_fine': args.use_two_models_for_fine})
@@ -162,7 +175,7 @@ def create_tnerf(args, device=None):
     grad_vars = list(model.parameters())
     network_query_fn = _timed_query_fn(render_tnerf.run_network, embed_fn, embeddirs_fn, embedtime_fn, args.netchunk,
                                        args.nerf_type != "temporal")
-    optimizer = torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))
+    optimizer = _make_optimizer(args, "create_tnerf", grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start = _reload(args, device)(model, None, optimizer)
     train, test = _render_kwargs(args, network_query_fn, {'N_importance': 0, 'network_fn': model, 'N_samples': args.N_samples})
     return train, test, start, grad_vars, optimizer
@@ -175,7 +188,7 @@ def create_fit2d(args, device=None):
     from . import fit2d
     device = _device(device)
     model = fit2d.Model(input_dimension=2 + 4 * args.L, layer_num=args.layer_num).to(device)
-    optimizer = torch.optim.AdamW(model.parameters(), lr=0.001)
+    optimizer = _make_optimizer(args, "create_fit2d", model.parameters(), adamw=True, lr=0.001)
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.95)
     start, metrics = 0, {"MSE": [], "PSNR": []}
     if getattr(args, "checkpoint_load", None):
@@ -208,7 +221,7 @@ def create_multires(args, device=None):
                 return load_multires(ckpts[-1], layer, model, model_fine, optimizer, map_location=device)
             return 0
         encoders = _timed_encoders(args, (L_pos, L_pos), (L_time, L_time), lambda: (L_views, L_views))
-        level = _create_dnerf(args, device, encoders, load, bool(getattr(args, "reproducible_wgrad", False)))
+        level = _create_dnerf(args, device, encoders, load, bool(getattr(args, "reproducible_wgrad", False)), "create_multires")
         for out, part in zip((trains, tests, starts, grads, optimizers), level):
             out.append(part)
     return trains, tests, starts, grads, optimizers
