@@ -1,65 +1,87 @@
-"""ctypes binding of libswnerf_hip.so (include/swnerf.h).  There is NO fallback: if the
-shared library is missing or a GPU is absent, every op raises - the product path never
-routes through a CPU implementation."""
+"""ctypes binding of libswnerf_hip.so, derived from include/swnerf.h: the header is the only place a signature, struct field,
+constant or version number is written.  There is NO fallback: if the shared library is missing or a GPU is absent, every op
+raises - the product path never routes through a CPU implementation."""
 import ctypes
 import os
-from ctypes import c_int, c_int64, c_double, c_void_p, c_size_t, c_char_p, POINTER, Structure
+import re
+from ctypes import c_void_p, c_char_p, POINTER, Structure
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libswnerf_hip.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "swnerf.h"))
 
-NET_CANON, NET_DNERF, NET_NOVIEW, NET_TNERF = 0, 1, 2, 3
-ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
-SSIM_SKIMAGE, SSIM_GAUSS11 = 0, 1
-RANGE_FIXED, RANGE_GT, RANGE_PRED_RULE = 0, 1, 2
-
-EXPORTS = ["swnerf_version", "swnerf_last_error", "swnerf_packed_floats", "swnerf_pack_net", "swnerf_pack_net_noview", "swnerf_mlp_forward_noview",
-           "swnerf_get_rays", "swnerf_ndc_rays", "swnerf_pack_ray_batch", "swnerf_raw2outputs", "swnerf_raw2outputs_backward",
-           "swnerf_sample_pdf", "swnerf_sample_coarse", "swnerf_embed", "swnerf_mlp_forward", "swnerf_query_points", "swnerf_render_pass",
-           "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row", "swnerf_mask_floats", "swnerf_mlp_forward_train", "swnerf_pack_net_bwd",
-           "swnerf_mlp_backward_dx", "swnerf_gemm_tn", "swnerf_gemm_tn_fused", "swnerf_gemm_tn_group", "swnerf_feature_finish", "swnerf_canon_narrow_grads", "swnerf_deform_narrow_grads",
-           "swnerf_packed_bwd_floats_kind", "swnerf_pack_net_bwd_kind", "swnerf_deform_forward_train",
-           "swnerf_mlp_backward_dx_pts", "swnerf_deform_backward_dx",
-           "swnerf_train_rows", "swnerf_xs_floats_per_row", "swnerf_render_pass_train", "swnerf_render_pass_backward", "swnerf_unslot_grad",
-           "swnerf_render_pass_train_dnerf", "swnerf_render_pass_backward_dnerf", "swnerf_unslot_grad_time",
-           "swnerf_packed_bwd_noview_floats", "swnerf_pack_net_bwd_noview", "swnerf_render_pass_backward_noview",
-           "swnerf_linear", "swnerf_gemm_nn", "swnerf_relu_mask",
-           "swnerf_packed_x3_floats", "swnerf_pack_net_x3", "swnerf_render_pass_x3",
-           "swnerf_packed_x3_floats_kind", "swnerf_pack_net_x3_kind",
-           "swnerf_mc_workspace_bytes", "swnerf_mc_count", "swnerf_mc_emit",
-           "swnerf_linear_act", "swnerf_elu_grad",
-           "swnerf_metrics_workspace_bytes", "swnerf_image_metrics",
-           "swnerf_pyramid_down", "swnerf_pyramid_up_axpy", "swnerf_pyramid_up_adjoint",
-           "swnerf_gemm_tn_ordered_ws_floats", "swnerf_gemm_tn_ordered",
-           "swnerf_encode2d", "swnerf_bn_workspace_bytes", "swnerf_bn_forward_train", "swnerf_bn_backward", "swnerf_bn_apply",
-           "swnerf_fit2d_loss", "swnerf_fit2d_packed_floats", "swnerf_pack_fit2d", "swnerf_fit2d_forward", "swnerf_fit2d_picture",
-           "swnerf_perm_indices", "swnerf_train_batch", "swnerf_photo_loss",
-           "swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_render_pass_train_tnerf",
-           "swnerf_packed_bwd_tnerf_floats", "swnerf_pack_net_bwd_tnerf", "swnerf_render_pass_backward_tnerf", "swnerf_tnerf_feature_finish",
-           "swnerf_adam_step", "swnerf_adam_plan", "swnerf_adam_caps"]
-BWD_CANON, BWD_CANON_INPUT_GRAD, BWD_DEFORM, BWD_DNERF_FUSED = 0, 1, 2, 3
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+             "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+_STRUCT_POINTERS = {}                      # "const swnerf_pass_args*" -> POINTER(PassArgs), filled below
 
 
-class GemmItem(Structure):
-    """struct swnerf_gemm_item (include/swnerf.h)"""
-    _fields_ = [("A", c_void_p), ("lda", c_int), ("B", c_void_p), ("ldb", c_int), ("C", c_void_p), ("ldc", c_int), ("bias", c_void_p),
-                ("B2", c_void_p), ("ldb2", c_int), ("Ni2", c_int), ("C2", c_void_p), ("ldc2", c_int),
-                ("A2", c_void_p), ("lda2", c_int), ("No2", c_int), ("C3", c_void_p), ("ldc3", c_int), ("bias3", c_void_p)]
+def _c_type(text):
+    return re.sub(r"\s+\*", "*", " ".join(text.split()))
 
 
-class PassArgs(Structure):
-    """struct swnerf_pass_args (include/swnerf.h)"""
-    _fields_ = [
-        ("ray_batch", c_void_p), ("n_rays", c_int64), ("cols", c_int), ("kind", c_int),
-        ("packed", c_void_p), ("run_deform", c_int), ("L_pos", c_int), ("L_dir", c_int), ("L_time", c_int),
-        ("n_samples", c_int), ("z_vals", c_void_p), ("lindisp", c_int), ("t_rand", c_void_p),
-        ("noise", c_void_p), ("white_bkgd", c_int),
-        ("rgb_map", c_void_p), ("disp_map", c_void_p), ("acc_map", c_void_p), ("depth_map", c_void_p),
-        ("weights", c_void_p), ("raw", c_void_p), ("dx", c_void_p), ("z_out", c_void_p),
-        ("n_importance", c_int), ("u", c_void_p), ("z_fine", c_void_p), ("z_std", c_void_p),
-        ("out_ch", c_int),
-    ]
+def _declarator(decl, where):
+    """'const float* A' / 'int L_pos, L_dir' -> (C type, [names])"""
+    m = re.fullmatch(r"(.*?[\s*])(\w+(?:\s*,\s*\w+)*)", decl.strip(), re.S)
+    if not m:
+        raise RuntimeError(f"swnerf.h: cannot read the declaration '{' '.join(decl.split())}' of {where}")
+    return _c_type(m[1]), re.split(r"\s*,\s*", m[2])
 
+
+def parse_header(text):
+    """Text of swnerf.h -> (signatures {name: (return C type, [argument C types])} in header order, structs {C name: [(C type,
+    field)]}, defines {name minus SWNERF_: int}).  A few regular expressions, not a C front end - so it refuses what it cannot
+    read: a swnerf_x( that no parsed prototype accounts for raises and names x."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {m[1]: int(m[2]) for m in re.finditer(r"^#define SWNERF_(\w+)[ \t]+\(?([-+]?\d+)\)?[ \t]*$", text, re.M)}
+    structs = {}
+    for m in re.finditer(r"typedef struct (swnerf_\w+)\s*\{(.*?)\}\s*\1\s*;", text, re.S):
+        decls = [_declarator(d, m[1]) for d in m[2].split(";") if d.strip()]
+        structs[m[1]] = [(c, f) for c, names in decls for f in names]
+    signatures = {}
+    for m in re.finditer(r"^([A-Za-z_][\w \t*]*?)\s*\b(swnerf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text, re.M):
+        args = [] if m[3].strip() == "void" else [_declarator(a, m[2]) for a in m[3].split(",")]
+        if any(len(names) != 1 for _, names in args):
+            raise RuntimeError(f"swnerf.h: cannot read the argument list of {m[2]}")
+        signatures[m[2]] = (_c_type(m[1]), [c for c, _ in args])
+    unread = sorted(set(re.findall(r"\b(swnerf_[a-z_0-9]+)\s*\(", text)) - set(signatures))
+    if unread:
+        raise RuntimeError(f"swnerf.h: no prototype could be parsed for {', '.join(unread)}")
+    return signatures, structs, defines
+
+
+def ctype_of(c, ret=False):
+    """The one rule from C type text to ctypes: the scalars of C_SCALARS; as a return type void -> None and const char* -> c_char_p;
+    a pointer to one of the two structs -> POINTER(its Structure), so callers pass the Structure (or an array of them) and get the
+    automatic by-reference; EVERY other pointer, device or host, -> c_void_p, whose from_param takes a ctypes array, byref(),
+    a typed pointer, a c_void_p, an int and None.  Anything else is an error."""
+    if c in C_SCALARS:
+        return C_SCALARS[c]
+    if ret and c in ("void", "const char*"):
+        return None if c == "void" else c_char_p
+    if c in _STRUCT_POINTERS:
+        return _STRUCT_POINTERS[c]
+    if c.endswith("*") and not re.search(r"\bswnerf_", c):
+        return c_void_p
+    raise RuntimeError(f"swnerf.h: no ctypes mapping for the C type '{c}'")
+
+
+def _structure(name, c_name):
+    cls = type(name, (Structure,), {"__doc__": f"struct {c_name} (include/swnerf.h)",
+                                    "_fields_": [(f, ctype_of(c)) for c, f in STRUCTS[c_name]]})
+    _STRUCT_POINTERS[f"const {c_name}*"] = POINTER(cls)
+    return cls
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(f"swnerf: {HEADER_PATH} not found - the ctypes binding is derived from it")
+with open(HEADER_PATH) as _f:
+    SIGNATURES, STRUCTS, DEFINES = parse_header(_f.read())
+# the header's integer constants under their names minus SWNERF_: VERSION, E_*, NET_*, ACT_*, SSIM_*, RANGE_*, BWD_*, ADAM_*
+globals().update(DEFINES)
+EXPORTS = list(SIGNATURES)
+GemmItem = _structure("GemmItem", "swnerf_gemm_item")
+PassArgs = _structure("PassArgs", "swnerf_pass_args")
+_PROTOTYPES = {name: (ctype_of(ret, True), [ctype_of(a) for a in args]) for name, (ret, args) in SIGNATURES.items()}
 
 _lib = None
 
@@ -77,140 +99,11 @@ def lib():
     # ("no ROCm-capable device is detected").  So: torch first, always.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    L.swnerf_version.restype = c_int
-    L.swnerf_last_error.restype = c_char_p
-    L.swnerf_packed_floats.restype = c_size_t
-    L.swnerf_packed_floats.argtypes = [c_int]
-    L.swnerf_pack_net.argtypes = [c_int, POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_pack_net_noview.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_mlp_forward_noview.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_get_rays.argtypes = [c_int, c_int, c_double, c_double, c_double, c_double, c_int,
-                                  POINTER(ctypes.c_float), c_int64, c_int64, c_void_p, c_void_p, c_void_p]
-    L.swnerf_ndc_rays.argtypes = [c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_int64,
-                                  c_void_p, c_void_p, c_void_p]
-    L.swnerf_pack_ray_batch.argtypes = [c_void_p, c_void_p, c_int64, c_double, c_double, c_int, c_double,
-                                        c_int, c_int, c_int, c_double, c_void_p, c_void_p]
-    L.swnerf_raw2outputs.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_raw2outputs_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
-                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_sample_pdf.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p]
-    L.swnerf_sample_coarse.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_embed.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_mlp_forward.argtypes = [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int,
-                                     c_int, c_void_p, c_void_p, c_void_p]
-    L.swnerf_query_points.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_render_pass.argtypes = [POINTER(PassArgs), c_void_p]
-    L.swnerf_packed_bwd_floats.restype = c_size_t
-    L.swnerf_packed_bwd_floats.argtypes = []
-    L.swnerf_act_floats_per_row.restype = c_size_t
-    L.swnerf_act_floats_per_row.argtypes = []
-    L.swnerf_mask_floats.restype = c_size_t
-    L.swnerf_mask_floats.argtypes = [c_int64]
-    L.swnerf_mlp_forward_train.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_pack_net_bwd.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_mlp_backward_dx.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-    L.swnerf_gemm_tn.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]
-    L.swnerf_gemm_tn_ordered_ws_floats.restype = c_size_t
-    L.swnerf_gemm_tn_ordered_ws_floats.argtypes = [c_int64, c_int, c_int]
-    L.swnerf_gemm_tn_ordered.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p,
-                                         c_void_p, c_size_t, c_void_p]
-    L.swnerf_gemm_tn_fused.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p,
-                                       c_void_p, c_int, c_int, c_void_p, c_int,
-                                       c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]
-    L.swnerf_gemm_tn_group.argtypes = [POINTER(GemmItem), c_int, c_int64, c_void_p]
-    L.swnerf_canon_narrow_grads.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 10
-    L.swnerf_deform_narrow_grads.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6
-    L.swnerf_feature_finish.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_packed_bwd_floats_kind.restype = c_size_t
-    L.swnerf_packed_bwd_floats_kind.argtypes = [c_int]
-    L.swnerf_pack_net_bwd_kind.argtypes = [c_int, POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_deform_forward_train.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_mlp_backward_dx_pts.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]
-    L.swnerf_deform_backward_dx.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-    L.swnerf_train_rows.restype = c_int64
-    L.swnerf_train_rows.argtypes = [c_int64, c_int]
-    L.swnerf_xs_floats_per_row.argtypes = []
-    L.swnerf_render_pass_train.argtypes = [POINTER(PassArgs), c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_render_pass_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_packed_bwd_noview_floats.restype = c_size_t
-    L.swnerf_packed_bwd_noview_floats.argtypes = []
-    L.swnerf_pack_net_bwd_noview.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_render_pass_backward_noview.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int,
-                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_render_pass_train_dnerf.argtypes = [POINTER(PassArgs)] + [c_void_p] * 7
-    L.swnerf_render_pass_backward_dnerf.argtypes = [c_void_p] * 6 + [c_int] + [c_void_p] * 3 + [c_int64, c_int, c_int, c_int] + [c_void_p] * 9
-    L.swnerf_unslot_grad_time.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
-    L.swnerf_unslot_grad.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]
-    L.swnerf_linear.argtypes = [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
-    L.swnerf_gemm_nn.argtypes = [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
-    L.swnerf_relu_mask.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
-    L.swnerf_linear_act.argtypes = [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
-    L.swnerf_elu_grad.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
-    L.swnerf_packed_x3_floats.restype = c_size_t
-    L.swnerf_packed_x3_floats.argtypes = []
-    L.swnerf_pack_net_x3.argtypes = [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.swnerf_render_pass_x3.argtypes = [POINTER(PassArgs), c_int, c_void_p]
-    L.swnerf_packed_x3_floats_kind.restype = c_size_t
-    L.swnerf_packed_x3_floats_kind.argtypes = [c_int]
-    L.swnerf_pack_net_x3_kind.argtypes = [c_int, POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.swnerf_mc_workspace_bytes.restype = c_size_t
-    L.swnerf_mc_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
-    L.swnerf_mc_count.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int64, ctypes.c_float, c_void_p, c_void_p, c_void_p]
-    L.swnerf_mc_emit.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, ctypes.c_float,
-                                 POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p, c_int64, c_int64,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_metrics_workspace_bytes.restype = c_size_t
-    L.swnerf_metrics_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int]
-    L.swnerf_image_metrics.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_double, c_int, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_pyramid_down.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]
-    L.swnerf_pyramid_up_axpy.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, ctypes.c_float, c_int64, c_int64,
-                                         c_void_p, c_void_p]
-    L.swnerf_pyramid_up_adjoint.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p]
-    L.swnerf_encode2d.argtypes = [c_void_p, c_int64, ctypes.c_float, ctypes.c_float, c_int, c_void_p, c_void_p]
-    L.swnerf_bn_workspace_bytes.restype = c_size_t
-    L.swnerf_bn_workspace_bytes.argtypes = [c_int64, c_int]
-    L.swnerf_bn_forward_train.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_double, c_double] + [c_void_p] * 7
-    L.swnerf_bn_backward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8
-    L.swnerf_bn_apply.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]
-    L.swnerf_fit2d_loss.argtypes = [c_void_p, c_void_p, c_int64, ctypes.c_float, c_void_p, c_void_p, c_void_p]
-    L.swnerf_fit2d_packed_floats.restype = c_size_t
-    L.swnerf_fit2d_packed_floats.argtypes = [c_int]
-    L.swnerf_pack_fit2d.argtypes = [POINTER(c_void_p), c_int, c_int, c_double, c_void_p, c_void_p]
-    L.swnerf_fit2d_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_fit2d_picture.argtypes = [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.swnerf_perm_indices.argtypes = [ctypes.c_uint64, c_int64, c_int64, c_int64, c_void_p, c_void_p]
-    L.swnerf_train_batch.argtypes = ([c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
-                                      c_double, c_double, c_double, c_double, c_int, c_double, c_double, c_int, c_int, c_double, c_int,
-                                      ctypes.c_uint64, c_int64, c_int64, c_void_p] + [c_void_p] * 4)
-    L.swnerf_photo_loss.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_void_p] * 5
-    for name in ("swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_packed_bwd_tnerf_floats"):
-        getattr(L, name).restype = c_size_t
-        getattr(L, name).argtypes = []
-    L.swnerf_render_pass_train_tnerf.argtypes = [POINTER(PassArgs), c_void_p, c_void_p, c_void_p]
-    L.swnerf_pack_net_bwd_tnerf.argtypes = [POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_void_p]
-    L.swnerf_render_pass_backward_tnerf.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
-                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.swnerf_tnerf_feature_finish.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    for name in EXPORTS:
-        if name not in ("swnerf_tnerf_act_floats_per_row", "swnerf_tnerf_xs_floats_per_row", "swnerf_packed_bwd_tnerf_floats",
-                        "swnerf_last_error", "swnerf_packed_floats", "swnerf_packed_bwd_floats", "swnerf_act_floats_per_row",
-                        "swnerf_packed_bwd_floats_kind", "swnerf_mask_floats", "swnerf_train_rows", "swnerf_packed_bwd_noview_floats",
-                        "swnerf_mc_workspace_bytes", "swnerf_metrics_workspace_bytes", "swnerf_gemm_tn_ordered_ws_floats",
-                        "swnerf_bn_workspace_bytes", "swnerf_fit2d_packed_floats"):
-            getattr(L, name).restype = c_int
-    L.swnerf_adam_step.argtypes = [c_int] + [c_void_p] * 8 + [c_double, c_double, c_double, c_int, ctypes.c_float, c_void_p]
-    L.swnerf_adam_plan.restype = c_int64
-    L.swnerf_adam_plan.argtypes = [c_int, c_void_p, c_int64] + [c_void_p] * 4
-    L.swnerf_adam_caps.restype = None
-    L.swnerf_adam_caps.argtypes = [POINTER(c_int), POINTER(c_int), POINTER(c_int64), POINTER(c_size_t)]
-    if L.swnerf_version() != 112:
-        raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected 112 - rebuild it "
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if L.swnerf_version() != DEFINES["VERSION"]:
+        raise RuntimeError(f"swnerf: {LIB_PATH} has version {L.swnerf_version()}, expected {DEFINES['VERSION']} - rebuild it "
                            "(python __graft_entry__.py)")
     _lib = L
     return L

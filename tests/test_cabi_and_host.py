@@ -1,5 +1,6 @@
 """CPU-only checks: the C-ABI library loads and exports every symbol include/swnerf.h declares,
-the ctypes mirror of swnerf_pass_args has the C layout, and the host-side logic (shards,
+the binding that swnerf/_lib.py derives from that header is the one gcc reads out of it (prototypes, struct layouts, type
+sizes), and the host-side logic (shards,
 fused-dispatch detection, argument validation, loud failure without a GPU) behaves."""
 import ctypes
 import os
@@ -35,18 +36,95 @@ def test_library_exports_every_declared_symbol(built):
     assert L.swnerf_version() == int(re.search(r"#define SWNERF_VERSION (\d+)", text).group(1))
 
 
-def test_pass_args_layout_matches_c(built, tmp_path):
-    """sizeof / offsetof of swnerf_pass_args as gcc sees them == the ctypes Structure."""
-    fields = [f for f, _ in built.PassArgs._fields_]
+def _layout_matches_c(tmp_path, c_name, cls):
+    fields = [f for f, _ in cls._fields_]
     src = tmp_path / "layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "swnerf.h"\nint main(){\n'
-                   'printf("%zu\\n", sizeof(swnerf_pass_args));\n'
-                   + "".join(f'printf("%zu\\n", offsetof(swnerf_pass_args, {f}));\n' for f in fields) + "return 0;}\n")
+                   f'printf("%zu\\n", sizeof({c_name}));\n'
+                   + "".join(f'printf("%zu\\n", offsetof({c_name}, {f}));\n' for f in fields) + "return 0;}\n")
     exe = tmp_path / "layout"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     nums = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert nums[0] == ctypes.sizeof(built.PassArgs)
-    assert nums[1:] == [getattr(built.PassArgs, f).offset for f in fields]
+    assert nums[0] == ctypes.sizeof(cls)
+    assert nums[1:] == [getattr(cls, f).offset for f in fields]
+
+
+def test_pass_args_layout_matches_c(built, tmp_path):
+    """sizeof / offsetof of swnerf_pass_args as gcc sees them == the ctypes Structure."""
+    assert len(built.PassArgs._fields_) == 28
+    _layout_matches_c(tmp_path, "swnerf_pass_args", built.PassArgs)
+
+
+def test_gemm_item_layout_matches_c(built, tmp_path):
+    assert len(built.GemmItem._fields_) == 18
+    _layout_matches_c(tmp_path, "swnerf_gemm_item", built.GemmItem)
+
+
+def test_parsed_prototypes_are_the_headers(built, tmp_path):
+    """The compiler is the referee: every (return type, argument types) that _lib parsed out of swnerf.h is compatible with the
+    declaration gcc sees.  A wrongly split argument list, a dropped const or a misread return type fails here, and the message
+    names the function."""
+    lines = [f'_Static_assert(__builtin_types_compatible_p(__typeof__(&{name}), {ret} (*)({", ".join(args) or "void"})), "{name}");\n'
+             for name, (ret, args) in built.SIGNATURES.items()]
+    assert len(lines) == len(set(re.findall(r"\b(swnerf_[a-z_0-9]+)\s*\(", open(HEADER).read())))
+    src = tmp_path / "prototypes.c"
+    src.write_text('#include "swnerf.h"\n' + "".join(lines))
+    r = subprocess.run(["gcc", "-std=c11", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_type_mapping_sizes_match_c(built, tmp_path):
+    """sizeof of every C type the binding maps, as gcc prints it == ctypes.sizeof of what it is mapped to; every pointer type
+    the header uses (arguments, struct fields, the const char* return) has the size of c_void_p."""
+    used = {c for ret, args in built.SIGNATURES.values() for c in [ret] + args} | {c for fs in built.STRUCTS.values() for c, _ in fs}
+    assert used - {"void"} - set(built.C_SCALARS) == {c for c in used if c.endswith("*")}
+    types = sorted(set(built.C_SCALARS) | used - {"void"})
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include "swnerf.h"\nint main(){\n'
+                   + "".join(f'printf("%zu\\n", sizeof({c}));\n' for c in types) + "return 0;}\n")
+    exe = tmp_path / "sizes"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    sizes = dict(zip(types, (int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())))
+    assert len(sizes) == len(types)
+    for c, n in sizes.items():
+        mapped = built.ctype_of(c, ret=(c == "const char*"))
+        assert n == ctypes.sizeof(mapped), c
+        if c.endswith("*"):
+            assert n == ctypes.sizeof(ctypes.c_void_p), c
+    assert built.ctype_of("void", ret=True) is None and built.ctype_of("const char*", ret=True) is ctypes.c_char_p
+    assert built.ctype_of("const swnerf_pass_args*") is ctypes.POINTER(built.PassArgs)
+    assert built.ctype_of("const swnerf_gemm_item*") is ctypes.POINTER(built.GemmItem)
+    for unmapped in ("long", "char", "void", "swnerf_pass_args*", "swnerf_pass_args"):
+        with pytest.raises(RuntimeError, match=re.escape(unmapped)):
+            built.ctype_of(unmapped)
+
+
+def test_return_types_follow_the_header(built):
+    """No function that returns size_t, int64_t or void is read back as an int (the names come from the header text here, not
+    from the parser)."""
+    L = built.lib()
+    assert L.swnerf_packed_x3_floats.restype is ctypes.c_size_t and L.swnerf_packed_x3_floats_kind.restype is ctypes.c_size_t
+    want = {"size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64, "void": None, "int": ctypes.c_int, "const char*": ctypes.c_char_p}
+    declared = re.findall(r"^(size_t|int64_t|void|int|const char\*)\s+(swnerf_[a-z_0-9]+)\s*\(", open(HEADER).read(), re.M)
+    assert sorted(n for _, n in declared) == sorted(built.EXPORTS)
+    assert all(sum(r == k for r, _ in declared) >= n for k, n in (("size_t", 16), ("int64_t", 2), ("void", 1)))
+    for ret, name in declared:
+        assert getattr(L, name).restype is want[ret], name
+        assert len(getattr(L, name).argtypes) == len(built.SIGNATURES[name][1]), name
+
+
+def test_header_parser_fails_loudly(built):
+    """A declaration the prototype pattern cannot consume is an error that names the symbol, never a silent skip."""
+    ok = "#define SWNERF_A (-3)\n#define SWNERF_B ((int64_t)1 << 4)\nint swnerf_ok(const float* const* p /*HOST, (x)*/, int64_t n);  // swnerf_no(\n"
+    sigs, structs, defines = built.parse_header(ok + "typedef struct swnerf_s { int a, b; float* c; } swnerf_s;\nsize_t swnerf_n(void);\n")
+    assert sigs == {"swnerf_ok": ("int", ["const float* const*", "int64_t"]), "swnerf_n": ("size_t", [])} and list(sigs) == ["swnerf_ok", "swnerf_n"]
+    assert structs == {"swnerf_s": [("int", "a"), ("int", "b"), ("float*", "c")]} and defines == {"A": -3}
+    with pytest.raises(RuntimeError, match="swnerf_cb"):
+        built.parse_header(ok + "int swnerf_cb(void (*f)(int), void* stream);\n")
+    with pytest.raises(RuntimeError, match="swnerf_unnamed"):
+        built.parse_header(ok + "int swnerf_unnamed(int, void* stream);\n")
+    with pytest.raises(RuntimeError, match="swnerf_unfinished"):
+        built.parse_header(ok + "int swnerf_unfinished(int a,\n")
 
 
 def test_packed_sizes_and_argument_errors_without_gpu(built):
