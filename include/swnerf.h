@@ -642,6 +642,37 @@ int64_t swnerf_adam_plan(int n_tensors, const int64_t* n /*HOST*/, int64_t capac
                          int64_t* count);
 void swnerf_adam_caps(int* max_tensors, int* max_blocks, int64_t* chunk, size_t* descriptor_bytes);
 
+/* ---- the joint iteration of the MultiRes D-NeRF runner (csrc/patch_kernels.hip, DESIGN.md 6g "Training") ---------------------
+ * Both take the levels of the pyramid, finest first, as HOST arrays of n_levels entries (1 <= n_levels <= SWNERF_PATCH_MAX_LEVELS)
+ * whose pointer entries are DEVICE pointers; the levels reach the kernel as one by-value argument.  One launch each.
+ * patch_batch: for every level l the patch of frame img_i with corner (y, x) = corner[2l], corner[2l+1] and side patch[l], CLIPPED to
+ *   the level as a slice is: ph = min(patch[l], H_l - y), pw = min(patch[l], W_l - x), (H_l, W_l) = level_hw[2l], level_hw[2l+1].
+ *   ray_batches[l] [ph * pw, 12] = the rows of pack_ray_batch (origin, direction, near, far, times[img_i], unit direction) of the
+ *   pixels (y .. y + ph - 1) x (x .. x + pw - 1), row-major, of get_rays(H_l, W_l, focal[l], c2w[img_i]) - the focal branch, the
+ *   same device code (csrc/ray_rows.h), bit for bit.  targets[l] [ph, pw, 3] = that window of pyr_images[l] [n_images, H_l, W_l, 3];
+ *   full_patch [ph_0, pw_0, 3] = the level-0 window of images [n_images, H_0, W_0, 3].  c2w [n_images, 3, 4], times [n_images].
+ *   SWNERF_E_ARG: a corner outside its level, an empty level, a patch side outside 1..4096, img_i outside the table, NULL pointer.
+ * multires_loss: level l has rgb[l], targets[l], d_rgb[l] [ph_l * pw_l, 3] (patch_hw[2l], patch_hw[2l+1] = ph_l, pw_l, each
+ *   1..SWNERF_PATCH_MAX_SIDE) and optionally rgb0[l] with d_rgb0[l] (rgb0 may be NULL, and so may any entry).
+ *   m_l = mean (rgb_l - target_l)^2, m0_l likewise; r = rgb_{L-1}, r = rgb_l + up(r) for l = L-2 .. 0, up = the bilinear upsample of
+ *   swnerf_pyramid_up_axpy between the patch sizes (bit for bit that kernel); g = mean (r - full_patch)^2.
+ *   losses (DEVICE float [SWNERF_MULTIRES_LOSSES]) = [sum_l (m_l + m0_l) + (add_global ? g : 0), g, 10 log10(1 / g), m_0 .. m_3,
+ *   m0_0 .. m0_3] (absent entries 0), sums in fp64 in a fixed order, each value rounded once.  reconstructed [ph_0, pw_0, 3] = r.
+ *   d_rgb[l] = 2 (rgb_l - target_l) / (3 ph_l pw_l), formed in fp64 and rounded once, plus, with add_global, (up^T)^l of
+ *   2 (r - full_patch) / (3 ph_0 pw_0) (up^T = the gather of swnerf_pyramid_up_adjoint), added in fp32; d_rgb0[l] likewise without
+ *   the second term: the gradient of losses[0].  One workgroup, no atomics: equal bits on every run. */
+#define SWNERF_PATCH_MAX_LEVELS 4
+#define SWNERF_PATCH_MAX_SIDE   32
+#define SWNERF_MULTIRES_LOSSES  11
+int swnerf_patch_batch(int n_levels, const float* const* pyr_images /*HOST*/, const int* level_hw /*HOST*/, const double* focal /*HOST*/,
+                       const int* corner /*HOST*/, const int* patch /*HOST*/, const float* images, int64_t n_images, const float* c2w,
+                       const float* times, int64_t img_i, double near, double far, float* const* ray_batches /*HOST*/,
+                       float* const* targets /*HOST*/, float* full_patch, void* stream);
+int swnerf_multires_loss(int n_levels, const int* patch_hw /*HOST*/, const float* const* rgb /*HOST*/,
+                         const float* const* rgb0 /*HOST, may be NULL*/, const float* const* targets /*HOST*/, const float* full_patch,
+                         int add_global, float* losses, float* reconstructed, float* const* d_rgb /*HOST*/,
+                         float* const* d_rgb0 /*HOST, may be NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

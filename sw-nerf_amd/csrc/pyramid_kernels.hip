@@ -12,31 +12,18 @@
 //   up_adjoint  g_coarse[N,h,w,C] = up^T(g_out[N,H,W,C]) as a gather: a coarse pixel sums, rows ascending and columns
 //               ascending inside a row, the fine pixels whose i0 or i1 it is - the same fp32 source coordinate as up, so
 //               the two are exact transposes - and is therefore bit-identical from run to run.
-// Source coordinate per axis, as torch forms it in fp32: s = max(scale * (d + 0.5) - 0.5, 0), scale = (float)n_in / n_out,
-// i0 = (int)s, i1 = min(i0 + 1, n_in - 1), lambda = s - i0.  All element offsets are 64-bit.
+// The source coordinate, the four-tap blend and the gather of the transpose are pyramid_interp.h (shared with patch_kernels.hip).
+// All element offsets are 64-bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/swnerf.h"
 #include "host_util.h"
+#include "pyramid_interp.h"
 
 #define PY_THREADS 256
 #define PY_MAX_BLOCKS (1 << 22)        // above this many blocks a kernel strides over its work
 #define PY_MAX_SIDE (1 << 20)
 #define PY_MAX_K 7
-
-struct PyAxis { int i0, i1; float l0, l1; };
-
-__device__ __forceinline__ PyAxis py_axis(int d, float scale, int n_in) {
-    float s = scale * ((float)d + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    PyAxis a;
-    a.i0 = (int)s;
-    if (a.i0 > n_in - 1) a.i0 = n_in - 1;                    // never taken for n_in <= 2^20 (s < n_in); keeps every index inside
-    a.i1 = a.i0 + (a.i0 < n_in - 1 ? 1 : 0);
-    a.l1 = s - (float)a.i0;
-    a.l0 = 1.f - a.l1;
-    return a;
-}
 
 // ---- down ------------------------------------------------------------------------------------------------------------
 template <int K, int C>
@@ -90,13 +77,7 @@ template <int C>
 __device__ __forceinline__ float py_up_one(const float* __restrict__ coarse, int64_t img, int h, int w, const PyAxis& ay,
                                            int f, float sx) {
     const int x = f / C, c = f - x * C;
-    const PyAxis ax = py_axis(x, sx, w);
-    const float* P = coarse + img * (int64_t)h * w * C + c;
-    const float* r0 = P + (int64_t)ay.i0 * w * C;
-    const float* r1 = P + (int64_t)ay.i1 * w * C;
-    const float top = ax.l0 * r0[(int64_t)ax.i0 * C] + ax.l1 * r0[(int64_t)ax.i1 * C];
-    const float bot = ax.l0 * r1[(int64_t)ax.i0 * C] + ax.l1 * r1[(int64_t)ax.i1 * C];
-    return ay.l0 * top + ay.l1 * bot;
+    return py_up_pixel<C>(coarse + img * (int64_t)h * w * C, w, ay, x, c, sx);
 }
 
 template <int C, int VEC, int SAME>
@@ -159,19 +140,6 @@ __global__ __launch_bounds__(PY_THREADS) void py_up_axpy_kernel(const float* __r
 }
 
 // ---- up_adjoint ------------------------------------------------------------------------------------------------------
-// the fine indices d whose i0 or i1 can be coarse index i: s(d) in (i - 1, i + 1), widened by 2 against fp32 rounding of the
-// estimate; every candidate is then tested with py_axis itself
-__device__ __forceinline__ void py_range(int i, float scale, int n_out, int& lo, int& hi) {
-    const float a = ((float)i - 0.5f) / scale - 0.5f, b = ((float)i + 1.5f) / scale - 0.5f;
-    const float fl = floorf(a) - 2.f, fh = ceilf(b) + 2.f;
-    lo = fl < 0.f ? 0 : (fl > (float)(n_out - 1) ? n_out - 1 : (int)fl);
-    hi = fh < 0.f ? 0 : (fh > (float)(n_out - 1) ? n_out - 1 : (int)fh);
-}
-
-__device__ __forceinline__ float py_weight(const PyAxis& a, int i) {
-    return (a.i0 == i ? a.l0 : 0.f) + (a.i1 == i ? a.l1 : 0.f);
-}
-
 template <int C>
 __global__ __launch_bounds__(PY_THREADS) void py_up_adjoint_kernel(const float* __restrict__ g_out, int64_t n, int H, int W,
                                                                    int h, int w, float* __restrict__ g_coarse) {
@@ -185,22 +153,7 @@ __global__ __launch_bounds__(PY_THREADS) void py_up_adjoint_kernel(const float* 
         const int i = (int)(row - img * h);
         const int j = f / C, c = f - j * C;
         const float* G = g_out + img * (int64_t)H * W * C + c;
-        int ylo, yhi, xlo, xhi;
-        py_range(i, sy, H, ylo, yhi);
-        py_range(j, sx, W, xlo, xhi);
-        float acc = 0.f;
-        for (int y = ylo; y <= yhi; ++y) {
-            const float wy = py_weight(py_axis(y, sy, h), i);
-            if (wy == 0.f) continue;
-            const float* gr = G + (int64_t)y * W * C;
-            float rs = 0.f;
-            for (int x = xlo; x <= xhi; ++x) {
-                const float wx = py_weight(py_axis(x, sx, w), j);
-                if (wx != 0.f) rs += wx * gr[(int64_t)x * C];
-            }
-            acc += wy * rs;
-        }
-        g_coarse[e] = acc;
+        g_coarse[e] = py_adjoint_pixel<C>(G, H, W, h, w, i, j, sy, sx);
     }
 }
 

@@ -4,6 +4,10 @@ photometric loss with its gradient by one more (swnerf_photo_loss).  Nothing of 
 `use_batching` keeps no table of rays: a batch is the image of a run of consecutive integers under a keyed permutation of the
 pixel ids, and an epoch is that permutation walked from 0 to its end.  DESIGN.md 6i.
 
+The joint iteration of the MultiRes runner has the same two launches (csrc/patch_kernels.hip): `PatchBatcher` makes
+every level's patch rows and targets, `multires_loss` the per-level losses, the reconstruction, the global loss and the gradients;
+`key_randint` / `key_normal` / `patch_corner(s)` are its host-side keyed draws.
+
 `perm_index_np` defines the permutation; the device function must equal it bit for bit (tests/test_gpu_batching.py)."""
 import ctypes
 
@@ -255,3 +259,204 @@ def photometric_loss(rgb, target, rgb0=None):
         raise ValueError(f"swnerf.batching.photometric_loss: rgb, rgb0 and target must all be [N >= 1, 3], got {tuple(rgb.shape)} / {tuple(target.shape)}")
     loss, img_loss, img_loss0, _ = _PhotoLoss.apply(rgb, target.detach(), rgb0)
     return loss, img_loss, (img_loss0 if rgb0 is not None else None)
+
+
+# ---- the joint iteration of the MultiRes D-NeRF runner (multires_dnerf.py:905-996; csrc/patch_kernels.hip) ------
+PATCH_MAX_LEVELS = _lib.PATCH_MAX_LEVELS
+PATCH_MAX_SIDE = _lib.PATCH_MAX_SIDE
+
+
+def key_word(key, j):
+    """Word j of the stream of a 64-bit key (batch_key): mix64(key + (j + 1) * golden), the construction of perm_index_np's round keys."""
+    return mix64((int(key) & _M64) + (int(j) + 1) * _GOLDEN)
+
+
+def key_uniform(key, j):
+    """A float64 in [0, 1): the top 53 bits of word j."""
+    return (key_word(key, j) >> 11) * (1.0 / (1 << 53))
+
+
+def key_randint(key, j, lo, hi):
+    """An integer in [lo, hi], both ends included as in random.randint: lo + word j mod (hi - lo + 1).  The modulo bias is below
+    (hi - lo + 1) / 2^64."""
+    lo, hi = int(lo), int(hi)
+    if hi < lo:
+        raise ValueError(f"swnerf.batching.key_randint: empty range [{lo}, {hi}]")
+    return lo + key_word(key, j) % (hi - lo + 1)
+
+
+def key_normal(key, j, mean, std):
+    """A normal draw (Box-Muller on words j and j + 1): mean + std * sqrt(-2 ln(1 - u1)) * cos(2 pi u2), float64."""
+    u1, u2 = key_uniform(key, j), key_uniform(key, j + 1)
+    return float(mean) + float(std) * float(np.sqrt(-2.0 * np.log1p(-u1)) * np.cos(2.0 * np.pi * u2))
+
+
+def patch_corner(key, H, W, patch_size, current_iter, n=4000, sigma_factor=4):
+    """runner.get_random_patch_coords (multires_dnerf.py:500-561) as a pure function of `key`: before iteration n uniform over the
+    central region (key_randint on words 0 and 1), from then on normal around the centre (key_normal on words 0..1 and 2..3) and
+    clipped into the image.  An image that is not larger than the patch gives (0, 0)."""
+    if H <= patch_size or W <= patch_size:
+        return 0, 0
+    center_y = (H - patch_size) / 2
+    center_x = (W - patch_size) / 2
+    if current_iter < n:
+        min_y = max(0, int(center_y - H / 4 / 2))
+        max_y = min(int(center_y + H / 4 / 2), H - patch_size)
+        min_x = max(0, int(center_x - W / 4 / 2))
+        max_x = min(int(center_x + W / 4 / 2), W - patch_size)
+        return key_randint(key, 0, min_y, max_y), key_randint(key, 1, min_x, max_x)
+    y = int(key_normal(key, 0, center_y, H / sigma_factor))
+    x = int(key_normal(key, 2, center_x, W / sigma_factor))
+    return max(0, min(y, H - patch_size)), max(0, min(x, W - patch_size))
+
+
+def patch_corners(key, pyr_hwf, base_patch_size=4, cur_iter=0):
+    """runner.initialize_patches (multires_dnerf.py:562-585) on patch_corner: one (y, x) per level, finest first - drawn at the
+    coarsest level and doubled level by level."""
+    H, W = int(pyr_hwf[-1][0]), int(pyr_hwf[-1][1])
+    y, x = patch_corner(key, H, W, base_patch_size, cur_iter)
+    n = len(pyr_hwf)
+    return [(y << (n - 1 - l), x << (n - 1 - l)) for l in range(n)]
+
+
+def clipped_patch_sizes(pyr_hwf, patch_coords, patch_size_list):
+    """(ph, pw) per level of the slice target[y:y + ps, x:x + ps] the reference takes (multires_dnerf.py:932): the patch clipped to
+    the level, ph = min(ps, H - y), pw = min(ps, W - x)."""
+    if not (len(pyr_hwf) == len(patch_coords) == len(patch_size_list)):
+        raise ValueError(f"swnerf.batching.clipped_patch_sizes: {len(pyr_hwf)} levels, {len(patch_coords)} corners, {len(patch_size_list)} patch sizes")
+    out = []
+    for l, ((H, W, _), (y, x), ps) in enumerate(zip(pyr_hwf, patch_coords, patch_size_list)):
+        H, W, y, x, ps = int(H), int(W), int(y), int(x), int(ps)
+        if ps < 1 or not (0 <= y < H and 0 <= x < W):
+            raise ValueError(f"swnerf.batching.clipped_patch_sizes: level {l}: patch {ps} at ({y}, {x}) of a {H} x {W} image")
+        out.append((min(ps, H - y), min(ps, W - x)))
+    return out
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class PatchBatcher:
+    """The data of a joint MultiRes iteration, made on the device by ONE launch (swnerf_patch_batch) for all levels.
+
+    images [N,H,W,3] float32 (the full-resolution frames), pyr_images: per level [N,H_l,W_l,3] float32 as
+    pyramid.generate_laplacian_pyramid_batch returns them, poses [N,>=3,4], times [N], pyr_hwf: [H_l, W_l, focal_l] per level
+    (runner.pyramid_hwf), at most PATCH_MAX_LEVELS levels.  Everything lives on the GPU; there is no CPU path."""
+
+    def __init__(self, images, pyr_images, poses, times, pyr_hwf, near, far, device=None):
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise RuntimeError(f"swnerf.batching.PatchBatcher: batches are made on the GPU (got device {dev}); there is no CPU path")
+        self.pyr_hwf = [(int(H), int(W), float(f)) for H, W, f in pyr_hwf]
+        n_levels = len(self.pyr_hwf)
+        if not 1 <= n_levels <= PATCH_MAX_LEVELS or len(pyr_images) != n_levels:
+            raise ValueError(f"swnerf.batching.PatchBatcher: {n_levels} levels in pyr_hwf (1..{PATCH_MAX_LEVELS} are built), {len(pyr_images)} in pyr_images")
+        images = torch.as_tensor(images)
+        if images.dim() != 4 or images.shape[-1] != 3 or images.dtype != torch.float32:
+            raise ValueError(f"swnerf.batching.PatchBatcher: images must be [N,H,W,3] float32, got {tuple(images.shape)} {images.dtype}")
+        self.n_images = int(images.shape[0])
+        if tuple(images.shape[1:3]) != self.pyr_hwf[0][:2]:
+            raise ValueError(f"swnerf.batching.PatchBatcher: images are {tuple(images.shape[1:3])}, level 0 of pyr_hwf is {self.pyr_hwf[0][:2]}")
+        self.images = images.to(dev).contiguous()
+        self.pyr_images = []
+        for l, (p, (H, W, _)) in enumerate(zip(pyr_images, self.pyr_hwf)):
+            p = torch.as_tensor(p)
+            if tuple(p.shape) != (self.n_images, H, W, 3) or p.dtype != torch.float32:
+                raise ValueError(f"swnerf.batching.PatchBatcher: pyr_images[{l}] must be {(self.n_images, H, W, 3)} float32, got {tuple(p.shape)} {p.dtype}")
+            self.pyr_images.append(p.to(dev).contiguous())
+        poses = torch.as_tensor(np.asarray(poses.cpu() if isinstance(poses, torch.Tensor) else poses, dtype=np.float32))
+        if poses.dim() != 3 or poses.shape[0] != self.n_images or poses.shape[1] < 3 or poses.shape[2] != 4:
+            raise ValueError(f"swnerf.batching.PatchBatcher: poses must be [{self.n_images},>=3,4], got {tuple(poses.shape)}")
+        self.c2w = poses[:, :3, :4].contiguous().to(dev)
+        self.times_host = np.asarray(times.cpu() if isinstance(times, torch.Tensor) else times, dtype=np.float32).reshape(-1)
+        if self.times_host.shape[0] != self.n_images:
+            raise ValueError(f"swnerf.batching.PatchBatcher: times must have {self.n_images} entries, got {self.times_host.shape[0]}")
+        self.times = torch.from_numpy(self.times_host.copy()).to(dev)
+        self.near, self.far, self.device = float(near), float(far), dev
+        self._pyr_ptrs = _ptr_array(self.pyr_images)
+        self._level_hw = _int_array([v for H, W, _ in self.pyr_hwf for v in (H, W)])
+        self._focal = (ctypes.c_double * n_levels)(*[f for _, _, f in self.pyr_hwf])
+
+    def batch(self, img_i, patch_coords, patch_size_list):
+        """-> (ray_batches, target_patches, full_patch): per level the packed rows [ph_l * pw_l, 12] of the patch with corner
+        patch_coords[l] = (y, x) and side patch_size_list[l], clipped to the level (clipped_patch_sizes), and that patch of
+        pyr_images[l] [ph_l, pw_l, 3]; full_patch [ph_0, pw_0, 3] is the level-0 patch of images."""
+        img_i = int(img_i)
+        if not 0 <= img_i < self.n_images:
+            raise ValueError(f"swnerf.batching.PatchBatcher.batch: image {img_i} of {self.n_images}")
+        sizes = clipped_patch_sizes(self.pyr_hwf, patch_coords, patch_size_list)
+        rows = [torch.empty((ph * pw, 12), dtype=torch.float32, device=self.device) for ph, pw in sizes]
+        targets = [torch.empty((ph, pw, 3), dtype=torch.float32, device=self.device) for ph, pw in sizes]
+        full = torch.empty((sizes[0][0], sizes[0][1], 3), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().swnerf_patch_batch(
+            len(sizes), self._pyr_ptrs, self._level_hw, self._focal, _int_array([v for yx in patch_coords for v in yx]),
+            _int_array(patch_size_list), _lib.ptr(self.images), self.n_images, _lib.ptr(self.c2w), _lib.ptr(self.times), img_i,
+            self.near, self.far, _ptr_array(rows), _ptr_array(targets), _lib.ptr(full), _lib.stream_of(full)), "patch_batch")
+        return rows, targets, full
+
+
+class _MultiresLoss(torch.autograd.Function):
+    """forward(add_global, n_levels, full_patch, *targets, *rgbs, *rgb0s) -> (loss, losses, reconstructed); the forward computes the
+    gradients of `loss`, the backward scales them.  losses and reconstructed carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, add_global, n, full, *ts):
+        targets, rgbs, rgb0s = ts[:n], ts[n:2 * n], ts[2 * n:]
+        dev = full.device
+        losses = torch.empty((_lib.MULTIRES_LOSSES,), dtype=torch.float32, device=dev)
+        recon = torch.empty_like(full)
+        d_rgb = [torch.empty_like(r) for r in rgbs]
+        d_rgb0 = [None if r is None else torch.empty_like(r) for r in rgb0s]
+        _lib.check(_lib.lib().swnerf_multires_loss(
+            n, _int_array([v for t in targets for v in t.shape[:2]]), _ptr_array(rgbs), _ptr_array(rgb0s), _ptr_array(targets),
+            _lib.ptr(full), int(bool(add_global)), _lib.ptr(losses), _lib.ptr(recon), _ptr_array(d_rgb), _ptr_array(d_rgb0),
+            _lib.stream_of(full)), "multires_loss")
+        ctx.n, ctx.has0 = n, [r is not None for r in rgb0s]
+        ctx.save_for_backward(*d_rgb, *[d for d in d_rgb0 if d is not None])
+        ctx.mark_non_differentiable(losses, recon)
+        return losses[0], losses, recon
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_losses, _g_recon):
+        n, saved = ctx.n, list(ctx.saved_tensors)
+        d_rgb, rest = saved[:n], saved[n:]
+        d_rgb0 = [rest.pop(0) if has else None for has in ctx.has0]
+        return (None, None, None) + (None,) * n + tuple(d * g_loss for d in d_rgb) + tuple(None if d is None else d * g_loss for d in d_rgb0)
+
+
+def multires_loss(rgbs, rgb0s, target_patches, full_patch, add_global):
+    """The loss of a joint MultiRes iteration (multires_dnerf.py:950-996) and its gradients in ONE launch (swnerf_multires_loss):
+    per level mse(rgb_l, target_l) [+ mse(rgb0_l, target_l)], the patches reconstructed through the pyramid, the mse of the
+    reconstruction against full_patch, added to the loss with add_global.  rgbs[l] / rgb0s[l]: [ph_l * pw_l, 3] or [ph_l, pw_l, 3];
+    rgb0s: None, or a list whose entries may be None; target_patches[l] [ph_l, pw_l, 3] (sides up to PATCH_MAX_SIDE);
+    full_patch [ph_0, pw_0, 3].
+    -> (loss, per_level, per_level0, global_loss, global_psnr, reconstructed).  Only `loss` is differentiable (with respect to every
+    rgb and rgb0): the other values are for the log.  Sums are fp64 in a fixed order: equal bits on every run."""
+    n = len(rgbs)
+    if not 1 <= n <= PATCH_MAX_LEVELS or len(target_patches) != n or (rgb0s is not None and len(rgb0s) != n):
+        raise ValueError(f"swnerf.batching.multires_loss: {n} levels of rgb (1..{PATCH_MAX_LEVELS} are built), {len(target_patches)} of targets")
+    rgb0s = [None] * n if rgb0s is None else list(rgb0s)
+    targets = [_lib.dev_f32(t, f"target_patches[{l}]", 3).detach() for l, t in enumerate(target_patches)]
+    full = _lib.dev_f32(full_patch, "full_patch", 3).detach()
+    rs, r0s = [], []
+    for l, t in enumerate(targets):
+        if t.dim() != 3 or not (1 <= t.shape[0] <= PATCH_MAX_SIDE and 1 <= t.shape[1] <= PATCH_MAX_SIDE):
+            raise ValueError(f"swnerf.batching.multires_loss: target_patches[{l}] must be [ph, pw, 3] with sides 1..{PATCH_MAX_SIDE}, got {tuple(t.shape)}")
+        for name, r, out in (("rgbs", rgbs[l], rs), ("rgb0s", rgb0s[l], r0s)):
+            if r is not None:
+                r = _lib.dev_f32(r, f"{name}[{l}]", 3)
+                if r.numel() != t.numel():
+                    raise ValueError(f"swnerf.batching.multires_loss: {name}[{l}] is {tuple(r.shape)}, its target patch {tuple(t.shape)}")
+            out.append(r)
+    if full.shape != targets[0].shape:
+        raise ValueError(f"swnerf.batching.multires_loss: full_patch is {tuple(full.shape)}, the level-0 patch {tuple(targets[0].shape)}")
+    loss, losses, recon = _MultiresLoss.apply(bool(add_global), n, full, *targets, *rs, *r0s)
+    L = PATCH_MAX_LEVELS
+    per_level = [losses[3 + l] for l in range(n)]
+    per_level0 = [None if r0s[l] is None else losses[3 + L + l] for l in range(n)]
+    return loss, per_level, per_level0, losses[1], losses[2], recon

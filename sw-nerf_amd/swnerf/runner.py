@@ -8,7 +8,8 @@ written against the reference only swaps its imports.  `args` is any object with
 (nerf/run.py:557-596 with calculate_metrics :49-61, and the last cell of d_nerf/metrics.ipynb) on the GPU metrics.
 `train`, `train_dnerf` and `train_tnerf` are the runners' training loops from `create_nerf` on, with the batch and the loss made
 on the device (swnerf.batching): one loop (`_train_loop`), and per runner its draw, render, extra loss and test-set
-render."""
+render.  `train_multires` is the MultiRes runner's: per level the D-NeRF iterations on that loop, then the joint iterations on
+`multires_train_loss` with a `PatchBatcher` (DESIGN.md 6g "Training")."""
 import json
 import os
 import random
@@ -19,7 +20,7 @@ import torch
 
 from . import metrics, pyramid, render, render_dnerf, render_tnerf
 from .png import read_png, write_png
-from .checkpoint import reload_latest, find_checkpoints, load_multires, to8b
+from .checkpoint import reload_latest, find_checkpoints, load_multires, save_multires, to8b
 from .ray import get_rays
 from .embedder import get_embedder
 from .model import vallina_NeRF, NeRF, TNeRF
@@ -279,15 +280,34 @@ def initialize_patches(pyr_hwf, base_patch_size=4, cur_iter=0):
 
 
 def multires_train_loss(i, img_i, images, pyr_images, poses, times, pyr_hwf, patch_size_list, render_kwargs_train_list, args,
-                        base_patch_size=32, patch_coords=None):
+                        base_patch_size=32, patch_coords=None, batcher=None):
     """The body of the reference's joint iteration (multires_dnerf.py:909-996) up to, and excluding, backward(): per level a
     patch of rays of frame img_i rendered by that level's nets against the same patch of that level of the pyramid
     (mse of rgb, plus mse of rgb0 when present), then the levels' patches reconstructed through the pyramid against the
     patch of the full image, added to the loss once i >= args.global_optimization_epoch.  near / far come with the
     render kwargs.  `patch_coords` (extra, optional) fixes the per-level corners instead of drawing them.
+    `batcher` (extra, optional): a swnerf.batching.PatchBatcher over the same images, pyramid, poses and times - every level's rows
+    and targets then come from one launch and the whole loss with its gradients from one more (DESIGN.md 6g "Training"); of the
+    returned values only `loss` then carries a gradient.
     -> (loss, per_level_losses, global_loss, global_psnr, reconstructed)."""
     if patch_coords is None:
         patch_coords = initialize_patches(pyr_hwf, base_patch_size=base_patch_size, cur_iter=i)
+    if batcher is not None:
+        from . import batching
+        ray_batches, target_patches, full_patch = batcher.batch(img_i, patch_coords, patch_size_list)
+        rgbs, rgb0s = [], []
+        for rb, render_kwargs_train in zip(ray_batches, render_kwargs_train_list):
+            rays_kw = {k: v for k, v in render_kwargs_train.items() if k not in _RENDER_ONLY_KEYS}
+            if render_kwargs_train.get('ndc', True):
+                raise NotImplementedError("swnerf.runner.multires_train_loss: a PatchBatcher makes no NDC rows (the MultiRes runner is blender-only)")
+            if not render_kwargs_train.get('use_viewdirs', False):
+                rb = rb[:, :9].contiguous()                              # run_dnerf.py:153-159
+            rgb, disp, acc, extras = _render_packed_dnerf(rb, batcher.times_host[int(img_i)], args.chunk, rays_kw)
+            rgbs.append(rgb)
+            rgb0s.append(extras.get('rgb0'))
+        loss, per_level, _, global_loss, global_psnr, reconstructed = batching.multires_loss(
+            rgbs, rgb0s, target_patches, full_patch, i >= args.global_optimization_epoch)
+        return loss, per_level, global_loss, global_psnr, reconstructed
     pyramid_outputs, per_level = [], []
     loss = 0
     for layer, render_kwargs_train in enumerate(render_kwargs_train_list):
@@ -444,9 +464,11 @@ def _opt(args, name, default):
     return getattr(args, name, default)
 
 
-def _train_common(args, d, device, sampler, loss_fn, create, timed):
-    """create: the runner's creator (create_nerf / create_dnerf / create_tnerf); timed: the D-NeRF and T-NeRF runners build rays
-    from hwf's focal and carry the frame time in column 8.  -> what the loop and its four callables work on."""
+def _train_common(args, d, device, sampler, loss_fn, create, timed, images=None, hwf=None, seed=None):
+    """create: the runner's creator (create_nerf / create_dnerf / create_tnerf), or a callable that hands over nets that exist
+    (a level of create_multires); timed: the D-NeRF and T-NeRF runners build rays from hwf's focal and carry the frame time in
+    column 8.  images / hwf / seed: what the batcher draws from instead of d['images'], d['hwf'] and args.seed (a pyramid level).
+    -> what the loop and its four callables work on."""
     from . import batching
     if sampler not in ("device", "numpy"):
         raise ValueError(f"swnerf.runner.train: sampler must be 'device' or 'numpy', got {sampler!r}")
@@ -456,10 +478,11 @@ def _train_common(args, d, device, sampler, loss_fn, create, timed):
     train_kw.update(bds)
     test_kw.update(bds)
     i_train = np.asarray(d['i_split'][0]).reshape(-1)
-    batcher = batching.RayBatcher(d['images'], d['poses'], d['hwf'] if timed else d['K'],        # the runners' own get_rays calls: focal there, K here
+    batcher = batching.RayBatcher(d['images'] if images is None else images, d['poses'],
+                                  (d['hwf'] if hwf is None else hwf) if timed else d['K'],       # the runners' own get_rays calls: focal there, K here
                                   i_train, d['near'], d['far'], times=d.get('times') if timed else None,
                                   ndc=train_kw.get('ndc', True), use_viewdirs=train_kw['use_viewdirs'], white_bkgd=args.white_bkgd,
-                                  seed=_opt(args, 'seed', 0), device=device)
+                                  seed=_opt(args, 'seed', 0) if seed is None else seed, device=device)
     rays_kw = {k: v for k, v in train_kw.items() if k not in _RENDER_ONLY_KEYS}
     return SimpleNamespace(device=device, train_kw=train_kw, test_kw=test_kw, start=start, optimizer=optimizer, i_train=i_train,
                            batcher=batcher, rays_kw=rays_kw, loss_fn=loss_fn or batching.photometric_loss, sampler=sampler,
@@ -495,6 +518,17 @@ def _step_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw
         hooks['on_step'](i, optimizer)
 
 
+def _render_packed_dnerf(rb, t_host, chunk, rays_kw, **more):
+    """render_dnerf's rays pass on a PACKED batch of one frame time.  The time is known here as the kernels read it (float32): no
+    device->host read per chunk (render_dnerf._TIME_HINT).  -> (rgb, disp, acc, extras)"""
+    token = render_dnerf._TIME_HINT.set((rb.untyped_storage().data_ptr(), float(t_host)))
+    try:
+        all_ret = render_dnerf.batchify_rays(rb, chunk, retraw=True, **more, **rays_kw)
+    finally:
+        render_dnerf._TIME_HINT.reset(token)
+    return render.image_outputs(all_ret, (rb.shape[0], 3))
+
+
 def _curriculum_draw(args, s):
     """draw(i) of the runners with frame times: one image among the first frames the time curriculum admits at iteration i
     (run_dnerf.py:650-655), then a no_batching batch of it."""
@@ -507,8 +541,11 @@ def _curriculum_draw(args, s):
     return draw
 
 
-def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset, extra_loss=None):
-    """Iterations s.start + 1 .. last_iter of the three runners.  What differs between them comes as callables:
+def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset, extra_loss=None, first_iter=None, step_tail=None,
+                advance=True):
+    """Iterations s.start + 1 .. last_iter of the three runners (first_iter .. last_iter when given; step_tail: what follows
+    optimizer.step() instead of _step_tail; advance=False: global_step stays at s.start; render_testset None: no test-set render -
+    the private phase of train_multires).  What differs between the runners comes as callables:
     draw(i) -> (img_i, ray_batch, target, ids); render_batch(i, img_i, ray_batch) -> (rgb, rgb0 for loss_fn, state);
     extra_loss(state) -> a term added to loss_fn's loss before backward, or None for none; render_testset(i_test, poses_test, gt_imgs,
     savedir) under no_grad every i_testset iterations.  -> the per-step record."""
@@ -516,7 +553,8 @@ def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset
     i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
     global_step = s.start
     record = _Record()
-    for i in range(s.start + 1, last_iter + 1):
+    step_tail = step_tail or _step_tail
+    for i in range(s.start + 1 if first_iter is None else first_iter, last_iter + 1):
         img_i, ray_batch, target_s, ids = draw(i)
         if 'on_batch' in hooks:
             hooks['on_batch'](i, img_i, ray_batch, target_s, ids)
@@ -527,14 +565,14 @@ def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset
             loss = loss + extra_loss(state)
         loss.backward()
         s.optimizer.step()
-        _step_tail(args, i, global_step, s.optimizer, record, loss, img_loss, s.train_kw, hooks)
-        if i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
+        step_tail(args, i, global_step, s.optimizer, record, loss, img_loss, s.train_kw, hooks)
+        if render_testset is not None and i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
             testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
             poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(s.device)
             with torch.no_grad():
                 render_testset(i_test, poses_test, _gt_rgb(d['images'], i_test, args.white_bkgd), testsavedir)
             print('Saved test set')
-        global_step += 1
+        global_step += int(advance)
     return record.flush()
 
 
@@ -582,17 +620,17 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     if not args.no_batching:
         raise NotImplementedError("Time not implemented")                        # run_dnerf.py:634
     s = _train_common(args, d, device, sampler, loss_fn, create_dnerf, True)
+    return _dnerf_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks)
+
+
+def _dnerf_loop(args, d, s, last_iter, hooks, testset=True, **loop_kw):
+    """The D-NeRF iterations on what _train_common prepared: train_dnerf, and each level of train_multires' private phase
+    (testset=False: no test-set render; loop_kw: _train_loop's first_iter, step_tail, advance)."""
     times = s.batcher.times_host
     add_tv = bool(_opt(args, 'add_tv_loss', False))
 
     def render_packed(rb, t_host, **more):
-        # the frame time is known here as the kernels read it (float32): no device->host read per chunk (render_dnerf._TIME_HINT)
-        token = render_dnerf._TIME_HINT.set((rb.untyped_storage().data_ptr(), float(t_host)))
-        try:
-            all_ret = render_dnerf.batchify_rays(rb, s.chunk, retraw=True, **more, **s.rays_kw)
-        finally:
-            render_dnerf._TIME_HINT.reset(token)
-        return render.image_outputs(all_ret, (rb.shape[0], 3))
+        return _render_packed_dnerf(rb, t_host, s.chunk, s.rays_kw, **more)
 
     def render_batch(i, img_i, ray_batch):
         frame_time = times[img_i]
@@ -630,8 +668,8 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     def render_testset(i_test, poses_test, gt_imgs, savedir):
         render_dnerf.render_path(poses_test, torch.as_tensor(times[i_test]).to(s.device), d['hwf'], s.chunk, s.test_kw,
                                  gt_imgs=gt_imgs, savedir=savedir)
-    return _train_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks, _curriculum_draw(args, s), render_batch,
-                       render_testset, tv_loss if add_tv else None)
+    return _train_loop(args, d, s, last_iter, hooks, _curriculum_draw(args, s), render_batch, render_testset if testset else None,
+                       tv_loss if add_tv else None, **loop_kw)
 
 
 def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
@@ -658,3 +696,154 @@ def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
         render_tnerf.render_path(poses_test, [float(t) for t in times[i_test]], d['hwf'], s.chunk, s.test_kw, gt_imgs=gt_imgs, savedir=savedir)
     return _train_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks, _curriculum_draw(args, s), render_batch,
                        render_testset)
+
+
+# ---- train() of the MultiRes runner (multires_dnerf/multires_dnerf.py:612-1068) -----------------------------------------------
+MULTIRES_BASE_PATCH = 32                                                         # multires_dnerf.py:726
+
+
+def multires_patch_sizes(layer_num, base_patch_size=MULTIRES_BASE_PATCH):
+    """multires_dnerf.py:726-732: [base // 2^l] per level."""
+    return [base_patch_size // (2 ** layer) for layer in range(layer_num)]
+
+
+def _multires_draw(sampler, seed, i, pyr_hwf, i_train):
+    """(patch_coords, img_i) of joint iteration i.  "numpy": initialize_patches (random.randint below iteration 4000, torch.normal
+    from it on), THEN np.random.choice(i_train) - the reference's streams in the reference's order (multires_dnerf.py:909-914).
+    "device": both from batching.batch_key(seed, i, 2) on the host - two scalars, so no launch and no sync: the corner from words
+    0..3 (batching.patch_corners), the frame from word 4."""
+    if sampler == "numpy":
+        patch_coords = initialize_patches(pyr_hwf, base_patch_size=MULTIRES_BASE_PATCH, cur_iter=i)
+        return patch_coords, np.random.choice(i_train)
+    from . import batching
+    key = batching.batch_key(seed, i, 2)
+    patch_coords = batching.patch_corners(key, pyr_hwf, base_patch_size=MULTIRES_BASE_PATCH, cur_iter=i)
+    return patch_coords, i_train[batching.key_randint(key, 4, 0, len(i_train) - 1)]
+
+
+def train_multires(args, data, device=None, sampler="device", hooks=None, private_target="reference"):
+    """The training loop of multires_dnerf/multires_dnerf.py:612-1068 from its `create_nerf` calls on (`create_multires`).
+
+    Setup: the frames as float32 RGB (RGBA composited on white with white_bkgd, else cut), their Laplacian pyramid of
+    args.layer_num levels, pyramid_hwf, patch sizes [32 // 2^l].
+    Private phase (:761-904), for the levels from the coarsest to the finest: iterations 0 .. global_optimization_epoch - 1 of
+    the D-NeRF step of `train_dnerf` (`_dnerf_loop`: time curriculum, precrop, TV loss) on that level's nets, rays from
+    pyramid_hwf[l] through a RayBatcher of the level.  As in the reference the learning rate is that of the level's starting
+    global_step throughout (its counter does not advance in this phase), a MultiRes checkpoint {i:06d}.tar is written when
+    i % i_weights == 0 (i = 0 included) and a line goes to log.txt when i % i_print == 0.  A resumed run repeats this phase.
+    private_target="reference": the target of level l is what the reference reads, images[img_i] indexed with LEVEL coordinates -
+    the top-left H_l x W_l window of the full-resolution frame, not the level of the pyramid.  "pyramid": pyr_images[l].
+    Joint phase (:905-1068), iterations start_list[0] + 1 .. args.N_iter: the patch corners and one frame (`sampler`), every
+    level's patch rendered by its nets, the fused loss (`multires_train_loss` with a PatchBatcher: two launches for data, loss and
+    gradients), one backward(), every optimizer's step() and zero_grad(), each level's learning rate from its own step counter,
+    `save_multires` every i_weights, `render_path_multires` of the test poses (every level at hwf, as the reference; no gt) every
+    i_testset, lines in log.txt every i_print.
+    Not written: video, TensorBoard, the i_img panels, args.txt / config.txt; do_half_precision is refused.
+
+    args: the reference's option names (layer_num, global_optimization_epoch, N_iter, N_rand, precrop_*, add_tv_loss, lrate,
+    lrate_decay, i_print, i_weights, i_testset, ...; seed - extra, default 0; optimizer - extra, "torch" or "fused").
+    data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  sampler: "numpy" consumes random, torch.normal
+    and np.random as the reference does; "device" keys every draw by (seed, iteration).
+    hooks: those of `train_dnerf` in the private phase (on_step gets the level's optimizer), and 'on_joint':
+    f(i, img_i, patch_coords, loss) after each joint step.
+    -> {'private': [per-step record of each level, finest first], 'joint': [{'step', 'loss', 'global_loss', 'levels'}]}."""
+    from . import batching
+    if private_target not in ("reference", "pyramid"):
+        raise ValueError(f"swnerf.runner.train_multires: private_target must be 'reference' or 'pyramid', got {private_target!r}")
+    if sampler not in ("device", "numpy"):
+        raise ValueError(f"swnerf.runner.train_multires: sampler must be 'device' or 'numpy', got {sampler!r}")
+    d = _train_data(data, True)
+    device = _device(device)
+    hooks = hooks or {}
+    n_levels = args.layer_num
+    n_all = int(torch.as_tensor(d['images']).shape[0])
+    images = torch.from_numpy(np.ascontiguousarray(_gt_rgb(d['images'], np.arange(n_all), args.white_bkgd), dtype=np.float32)).to(device)
+    pyr_images = pyramid.generate_laplacian_pyramid_batch(images, levels=n_levels)
+    pyr_hwf = pyramid_hwf(d['hwf'], n_levels)
+    patch_size_list = multires_patch_sizes(n_levels)
+    trains, tests, start_list, grad_vars_list, optimizers = create_multires(args, device=device)
+    nets = [kw['network_fn'] for kw in trains]
+    fines = [kw.get('network_fine') for kw in trains]
+    i_train = np.asarray(d['i_split'][0]).reshape(-1)
+    seed = _opt(args, 'seed', 0)
+    i_print, i_weights = _opt(args, 'i_print', 100), _opt(args, 'i_weights', 10000)
+    os.makedirs(os.path.join(args.basedir, args.expname), exist_ok=True)
+    log = os.path.join(args.basedir, args.expname, 'log.txt')
+
+    def save(i):
+        print('Saved checkpoints at', save_multires(args.basedir, args.expname, i, i, nets, fines, optimizers))
+
+    def write_log(lines):
+        with open(log, 'a') as f:
+            f.write(''.join(line + '\n' for line in lines))
+
+    def private_tail(args, i, global_step, optimizer, record, loss, img_loss, train_kw, hooks):
+        new_lrate = batching.lr_at(args.lrate, args.lrate_decay, global_step)
+        for param_group in optimizer.param_groups:
+            param_group['lr'] = new_lrate
+        record.add(i, loss, img_loss, new_lrate)
+        if i % i_weights == 0:
+            save(i)
+        if i % i_print == 0:
+            last = record.flush()[-1]
+            write_log([f"[TRAIN] Iter: {i} Loss_fine: {last['loss']} PSNR: {last['psnr']}"])
+        if hooks and 'on_step' in hooks:
+            hooks['on_step'](i, optimizer)
+
+    # the private phase
+    private = [None] * n_levels
+    for model_idx in reversed(range(n_levels)):
+        H_l, W_l, focal_l = pyr_hwf[model_idx]
+        level_images = pyr_images[model_idx] if private_target == "pyramid" else images[:, :H_l, :W_l]
+        level = (trains[model_idx], tests[model_idx], start_list[model_idx], grad_vars_list[model_idx], optimizers[model_idx])
+        s = _train_common(args, d, device, sampler, None, lambda args, device: level, True, images=level_images,
+                          hwf=[H_l, W_l, focal_l], seed=batching.mix64(int(seed) + model_idx + 1))
+        private[model_idx] = _dnerf_loop(args, d, s, args.global_optimization_epoch - 1, hooks, testset=False, first_iter=0,
+                                         step_tail=private_tail, advance=False)
+
+    # the joint phase
+    batcher = batching.PatchBatcher(images, pyr_images, d['poses'], d['times'], pyr_hwf, d['near'], d['far'], device=device)
+    poses_dev = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)).to(device)
+    i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
+    global_steps = list(start_list)
+    for optimizer in optimizers:
+        optimizer.zero_grad()                                                    # (the reference does it per level inside the iteration)
+    joint, pending = [], []
+    for i in range(start_list[0] + 1, args.N_iter + 1):
+        patch_coords, img_i = _multires_draw(sampler, seed, i, pyr_hwf, i_train)
+        loss, per_level, global_loss, global_psnr, _ = multires_train_loss(
+            i, img_i, images, pyr_images, poses_dev, batcher.times, pyr_hwf, patch_size_list, trains, args,
+            base_patch_size=MULTIRES_BASE_PATCH, patch_coords=patch_coords, batcher=batcher)
+        for layer, optimizer in enumerate(optimizers):
+            new_lrate = batching.lr_at(args.lrate, args.lrate_decay, global_steps[layer])
+            for param_group in optimizer.param_groups:
+                param_group['lr'] = new_lrate
+            global_steps[layer] += 1
+        loss.backward()
+        for optimizer in optimizers:
+            optimizer.step()
+            optimizer.zero_grad()
+        pending.append((i, loss.detach(), global_loss, torch.stack(per_level)))
+        if 'on_joint' in hooks:
+            hooks['on_joint'](i, img_i, patch_coords, loss)
+        if i % i_weights == 0:
+            save(i)
+        if i % i_print == 0 or i == args.N_iter:                                 # the losses leave the device here, not per step
+            for step, l, g, levels in pending:
+                joint.append({'step': step, 'loss': float(l), 'global_loss': float(g), 'levels': levels.tolist()})
+            pending = []
+        if i % i_print == 0:
+            last = joint[-1]
+            y, x = patch_coords[0]
+            lines = [f"[TRAIN] Layer: {layer} Iter: {i} Loss_fine: {m:.6f} PSNR: {-10. * np.log10(m) if m > 0 else float('inf'):.2f}"
+                     for layer, m in enumerate(last['levels'])]
+            lines.append(f"[GLOBAL OPT] Iter: {i} Global Loss: {last['global_loss']:.6f} Global PSNR: {float(global_psnr):.2f}, Coords:{(y, x)}")
+            write_log(lines)
+            print(lines[-1])
+        if i % _opt(args, 'i_testset', 50000) == 0 and i_test.size:
+            testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
+            with torch.no_grad():
+                render_path_multires(poses_dev[i_test], batcher.times[i_test], d['hwf'], _opt(args, 'chunk', 1024 * 32), tests,
+                                     level_hwf="reference", savedir=testsavedir)
+            print('Saved test set')
+    return {'private': private, 'joint': joint}
