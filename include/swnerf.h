@@ -237,6 +237,21 @@ int swnerf_deform_backward_dx(const float* packed_bwd, const float* bits_d, cons
 int swnerf_query_points(const float* packed, const float* pts, int64_t M, const float* dirs, int64_t n_dirs,
                         int shared_dirs, int L_pos, int L_dir, float* out /*[M,4]*/, void* stream);
 
+/* The same query for the two time-conditioned nets at ONE frame time (a grid of a dynamic scene at time t: nerf/extract_mesh.py
+ * sample_grid :27-90 with the runner's own query in place of the static one).  frame_time is a constant of the call, the
+ * reference's "Only accepts all points from same time" (d_nerf/run_dnerf.py:53, t_nerf/run_tnerf.py:52).
+ *   SWNERF_NET_DNERF  run_network (d_nerf/run_dnerf.py:46-83) + DirectTemporalNeRF.forward (model.py:128-151): the deformation
+ *                     net -> dx, gamma(x + dx), the canonical trunk and the density once per point, the view branch once per
+ *                     direction.  run_deform == 0 takes the `t == 0 and zero_canonical` branch (model.py:143-145: the canonical
+ *                     net alone, dx = 0).  dx_out [M,3] (position_delta) may be NULL.  dirs / shared_dirs / out as above.
+ *   SWNERF_NET_TNERF  run_network (t_nerf/run_tnerf.py:48-87) + TNeRF.forward (model.py:192-210): out [M,4] = [mean over the V
+ *                     directions of rgb (after `color`'s ReLU), density].  Shared directions only (shared_dirs == 0 is
+ *                     SWNERF_E_UNSUPP), no dx_out (non-NULL is SWNERF_E_ARG), run_deform is ignored, L_dir >= 1.
+ * Any other kind is SWNERF_E_ARG.  Limits: L_pos <= 10, L_dir <= 4, L_time <= 10 (else SWNERF_E_UNSUPP). */
+int swnerf_query_points_time(int kind, const float* packed, const float* pts, int64_t M, const float* dirs, int64_t n_dirs,
+                             int shared_dirs, double frame_time, int run_deform, int L_pos, int L_dir, int L_time,
+                             float* out /*[M,4]*/, float* dx_out /*[M,3] or NULL*/, void* stream);
+
 /* Marching cubes (nerf/extract_mesh.py generate_mesh :92-131, in place of skimage.measure.marching_cubes): the iso-surface
  * f = level of a scalar field of nx * ny * nz points in C order (i slowest), consecutive points `ld` floats apart (ld = 1: a
  * dense [nx,ny,nz] array; ld = 4: the sigma column of swnerf_query_points' [M,4] output).  A corner is inside iff f > level

@@ -7,7 +7,10 @@ an OBJ writer, in place of skimage.measure.marching_cubes and trimesh (DESIGN.md
 
 `swnerf_query_points` evaluates the positional encodings in registers and - for V view
 directions shared by every grid point - the 8-layer trunk and the density ONCE per point and
-only the view branch V times: 8832 + 640 V MFMAs per 32 points instead of 9472 V."""
+only the view branch V times: 8832 + 640 V MFMAs per 32 points instead of 9472 V.
+`swnerf_query_points_time` does the same for the two time-conditioned nets at one frame time (`frame_time=`):
+DirectTemporalNeRF (deformation net, gamma(x + dx), canonical trunk once per point; d_nerf/run_dnerf.py:46-83) and TNeRF
+(t_nerf/run_tnerf.py:48-87); `mesh_sequence` meshes a list of times."""
 import ctypes
 
 import numpy as np
@@ -24,26 +27,80 @@ def generate_viewdirs(num_views=100):
     return np.stack([np.cos(theta) * np.sin(phi), np.sin(theta) * np.sin(phi), np.cos(phi)], axis=1)
 
 
-def query_points(net, pts, viewdirs, shared_dirs=None):
+def _single_time(frame_time):
+    """frame_time as the kernels read it (one float32 value): a Python number, or a tensor whose values are all equal - the
+    reference's "Only accepts all points from same time" (d_nerf/run_dnerf.py:53, t_nerf/run_tnerf.py:52)."""
+    if isinstance(frame_time, torch.Tensor):
+        if frame_time.numel() == 0:
+            raise ValueError("swnerf.mesh.query_points: frame_time is an empty tensor")
+        lo, hi = torch.aminmax(frame_time.detach().float())
+        lo, hi = float(lo), float(hi)
+        if lo != hi:
+            raise ValueError("swnerf.mesh.query_points: Only accepts all points from same time "
+                             f"(frame_time spans [{lo}, {hi}]; per-point times are not built)")
+        return lo
+    return float(np.float32(frame_time))
+
+
+def _query_tnerf_rows(net, pts, dirs, t):
+    """T-NeRF with one direction per point: the op path (embedders, then TNeRF.forward) - the fused stream has no per-row
+    direction columns."""
+    from .embedder import get_embedder
+    bands = net.fused_bands()
+    if bands is None:
+        net.packed()                                       # raises, naming the shapes that are built
+    Lp, Ld, Lt = bands
+    tt = torch.full((pts.shape[0], 1), t, dtype=torch.float32, device=pts.device)
+    ex, ed, et = get_embedder(Lp, 3)[0](pts), get_embedder(Ld, 3)[0](dirs), get_embedder(Lt, 1)[0](tt)
+    return net(torch.cat([ex, ed], -1), ed, et).reshape(-1, 4)
+
+
+def query_points(net, pts, viewdirs, shared_dirs=None, frame_time=None, return_dx=False):
     """pts [M,3]; viewdirs [M,3] (one per point -> raw [M,4], what network_query_fn(positions, viewdirs, fn)
     returns) or [V,3] shared (-> [M,4] = [mean_v raw rgb, sigma]).  `shared_dirs` defaults to
-    `viewdirs.shape[0] != M`."""
-    kind, packed, Lp, Ld, _ = net.packed()
-    if kind != _lib.NET_CANON:
-        raise NotImplementedError("swnerf.mesh.query_points: static NeRF nets only (the mesh tool is nerf/ only)")
+    `viewdirs.shape[0] != M`.
+    A time-conditioned net (DirectTemporalNeRF, TNeRF) is queried at ONE `frame_time`: a Python float, or a tensor whose values
+    are all equal (swnerf_query_points_time; for TNeRF rgb is what `color` returns, after its ReLU).  return_dx=True
+    (DirectTemporalNeRF only) -> (out [M,4], position_delta [M,3])."""
+    from .model import TNeRF
+    tnerf = isinstance(net, TNeRF)
+    kind = _lib.NET_TNERF if tnerf else net._pack_params()[0]          # refusals first: they need neither the GPU nor a packed blob
+    timed = kind in (_lib.NET_DNERF, _lib.NET_TNERF)
+    if kind != _lib.NET_CANON and not timed:
+        raise NotImplementedError("swnerf.mesh.query_points: nets with view directions only (8x256 static, DirectTemporalNeRF, TNeRF)")
+    if not timed and frame_time is not None:
+        raise ValueError("swnerf.mesh.query_points: a static net takes no frame_time")
+    if timed and frame_time is None:
+        raise NotImplementedError("swnerf.mesh.query_points: a time-conditioned net is queried at one frame time - pass frame_time")
+    if return_dx and kind != _lib.NET_DNERF:
+        raise ValueError("swnerf.mesh.query_points: return_dx is the position_delta of a DirectTemporalNeRF")
+    t = _single_time(frame_time) if timed else None
     pts = _lib.dev_f32(pts, "pts", 3).reshape(-1, 3)
     dirs = _lib.dev_f32(viewdirs, "viewdirs", 3).reshape(-1, 3)
     M = pts.shape[0]
     if shared_dirs is None:
         shared_dirs = dirs.shape[0] != M
     out = torch.empty((M, 4), dtype=torch.float32, device=pts.device)
-    _lib.check(_lib.lib().swnerf_query_points(_lib.ptr(packed), _lib.ptr(pts), M, _lib.ptr(dirs), dirs.shape[0],
-                                              int(bool(shared_dirs)), Lp, Ld, _lib.ptr(out), _lib.stream_of(pts)),
-               "query_points")
-    return out
+    if tnerf and not shared_dirs:
+        if dirs.shape[0] != M:
+            raise RuntimeError(f"swnerf.mesh.query_points: need one direction per point, got {dirs.shape[0]} for {M} points")
+        return _query_tnerf_rows(net, pts, dirs, t) if M else out
+    kind, packed, Lp, Ld, Lt = net.packed()
+    if not timed:
+        _lib.check(_lib.lib().swnerf_query_points(_lib.ptr(packed), _lib.ptr(pts), M, _lib.ptr(dirs), dirs.shape[0],
+                                                  int(bool(shared_dirs)), Lp, Ld, _lib.ptr(out), _lib.stream_of(pts)),
+                   "query_points")
+        return out
+    run_deform = 0 if tnerf else int(not (t == 0. and net.zero_canonical))
+    dx = torch.empty((M, 3), dtype=torch.float32, device=pts.device) if return_dx else None
+    _lib.check(_lib.lib().swnerf_query_points_time(kind, _lib.ptr(packed), _lib.ptr(pts), M, _lib.ptr(dirs), dirs.shape[0],
+                                                   int(bool(shared_dirs)), t, run_deform, Lp, Ld, Lt, _lib.ptr(out), _lib.ptr(dx),
+                                                   _lib.stream_of(pts)), "query_points_time")
+    return (out, dx) if return_dx else out
 
 
-def sample_grid(bounds, resolution, net, num_views=100, batch_size=1 << 20, sharded=None, group=None, query=None, on_device=False):
+def sample_grid(bounds, resolution, net, num_views=100, batch_size=1 << 20, sharded=None, group=None, query=None, on_device=False,
+                frame_time=None, points_device=None):
     """extract_mesh.py:27-90 with the network in place of `nerf_function`:
     -> (density_field [R,R,R], color_field [R,R,R,3], (X, Y, Z)), float64 numpy like the reference.
     `color` is the view-average of the RAW rgb and `density` of the raw sigma (batch_query_fn :155-175
@@ -52,7 +109,10 @@ def sample_grid(bounds, resolution, net, num_views=100, batch_size=1 << 20, shar
     defaults to that) every rank queries its contiguous shard of the R^3 points and ONE all-gather of the [n,4] results
     returns the whole field to every rank - points are independent, exactly like rays (swnerf.parallel).
     `query(points [n,3] tensor, dirs [V,3] tensor) -> [n,4]` defaults to the fused HIP query of `net`.
-    on_device=True returns the [R,R,R,4] float32 device tensor [rgb, sigma] instead (no host copy), for marching_cubes."""
+    on_device=True returns the [R,R,R,4] float32 device tensor [rgb, sigma] instead (no host copy), for marching_cubes.
+    frame_time: the one time a time-conditioned net (DirectTemporalNeRF, TNeRF) is queried at (query_points); an injected
+    `query` keeps its two-argument form and never sees it.  points_device: the [R^3,3] float32 grid points already on the
+    net's device (mesh_sequence uploads them once for all its times)."""
     import torch.distributed as dist
     from .parallel import gather_pixels
     from .synth import shard_range
@@ -64,7 +124,7 @@ def sample_grid(bounds, resolution, net, num_views=100, batch_size=1 << 20, shar
     dev = next(net.parameters()).device if net is not None else torch.device("cpu")
     dirs = torch.tensor(generate_viewdirs(num_views), dtype=torch.float32, device=dev)
     if query is None:
-        query = lambda p, d: query_points(net, p, d, shared_dirs=True)
+        query = lambda p, d: query_points(net, p, d, shared_dirs=True, frame_time=frame_time)
     on = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     if sharded is None:
         sharded = on
@@ -74,7 +134,8 @@ def sample_grid(bounds, resolution, net, num_views=100, batch_size=1 << 20, shar
     outs = []
     with torch.no_grad():
         for s in range(lo, hi, batch_size):
-            p = torch.tensor(points[s:min(hi, s + batch_size)], dtype=torch.float32, device=dev)
+            e = min(hi, s + batch_size)
+            p = points_device[s:e] if points_device is not None else torch.tensor(points[s:e], dtype=torch.float32, device=dev)
             outs.append(query(p, dirs))
     local = torch.cat(outs, 0) if outs else torch.empty((0, 4), dtype=torch.float32, device=dev)
     out = gather_pixels(local, [b - a for a, b in ranges], group) if world > 1 else local
@@ -216,11 +277,39 @@ def generate_mesh(density_field, color_field, xyz_coords, density_threshold=0.5,
     return _to_mesh(marching_cubes(d, density_threshold, spacing, origin, c))
 
 
-def nerf_to_mesh(net, bounds, resolution=64, density_threshold=8, num_views=100, batch_size=1 << 20):
-    """extract_mesh.py:133-145 with the network in place of `nerf_function`: grid query and marching cubes on the net's
-    device, no host round trip of the field (the [R,R,R,4] query output is read in place) -> Mesh."""
-    q = sample_grid(bounds, resolution, net, num_views=num_views, batch_size=batch_size, on_device=True, sharded=False)
+def _grid_spacing_origin(bounds, resolution):
     axes = [np.linspace(b[0], b[1], resolution) for b in bounds]
-    spacing = tuple(float(a[1] - a[0]) for a in axes)
-    origin = tuple(float(a[0]) for a in axes)
+    return tuple(float(a[1] - a[0]) for a in axes), tuple(float(a[0]) for a in axes)
+
+
+def nerf_to_mesh(net, bounds, resolution=64, density_threshold=8, num_views=100, batch_size=1 << 20, frame_time=None):
+    """extract_mesh.py:133-145 with the network in place of `nerf_function`: grid query and marching cubes on the net's
+    device, no host round trip of the field (the [R,R,R,4] query output is read in place) -> Mesh.  frame_time: the time a
+    time-conditioned net is meshed at (sample_grid)."""
+    q = sample_grid(bounds, resolution, net, num_views=num_views, batch_size=batch_size, on_device=True, sharded=False,
+                    frame_time=frame_time)
+    spacing, origin = _grid_spacing_origin(bounds, resolution)
     return _to_mesh(marching_cubes(q[..., 3], density_threshold, spacing, origin, q[..., :3]))
+
+
+def mesh_sequence(net, bounds, times, resolution=64, density_threshold=8, num_views=100, out_dir=None, basename="mesh_{:03d}.obj"):
+    """The surface of a time-conditioned net (DirectTemporalNeRF, TNeRF) at every time of `times` -> [Mesh, ...]: one grid
+    query and one marching-cubes pass per time on the net's device, the R^3 grid points uploaded once.  With `out_dir` mesh i is
+    also written to out_dir/basename.format(i) (Wavefront OBJ, Mesh.export)."""
+    import os
+    axes = [np.linspace(b[0], b[1], resolution) for b in bounds]
+    X, Y, Z = np.meshgrid(*axes, indexing='ij')
+    dev = next(net.parameters()).device
+    pts = torch.tensor(np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=-1), dtype=torch.float32, device=dev)
+    spacing, origin = _grid_spacing_origin(bounds, resolution)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+    meshes = []
+    for i, t in enumerate(times):
+        q = sample_grid(bounds, resolution, net, num_views=num_views, on_device=True, sharded=False, frame_time=float(t),
+                        points_device=pts)
+        m = _to_mesh(marching_cubes(q[..., 3], density_threshold, spacing, origin, q[..., :3]))
+        if out_dir is not None:
+            m.export(os.path.join(out_dir, basename.format(i)))
+        meshes.append(m)
+    return meshes

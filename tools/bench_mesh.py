@@ -4,7 +4,9 @@
 loop structure (one full network query per view direction) on the same kernels; then marching cubes (swnerf_mc_count /
 swnerf_mc_emit) per pass on a sphere and a noise field, and nerf_to_mesh against the query alone.
   python tools/bench_mesh.py              everything
-  python tools/bench_mesh.py --mc 512     only the marching-cubes passes at 512^3 (for a rocprofv3 --kernel-trace --stats run)"""
+  python tools/bench_mesh.py --mc 512     only the marching-cubes passes at 512^3 (for a rocprofv3 --kernel-trace --stats run)
+  python tools/bench_mesh.py --dnerf      only the grid query of the seeded DirectTemporalNeRF at t = 0.5 (swnerf_query_points_time) against
+  python tools/bench_mesh.py --tnerf      / TNeRF                    the op path (embed + one full network call per direction)"""
 import os
 import sys
 import time
@@ -28,6 +30,70 @@ pts = torch.tensor(np.stack([X.ravel(), Y.ravel(), Z.ravel()], -1), dtype=torch.
 dirs = torch.tensor(mesh.generate_viewdirs(V), dtype=torch.float32, device=dev)
 M = pts.shape[0]
 MC_ONLY = [int(sys.argv[sys.argv.index("--mc") + 1])] if "--mc" in sys.argv else None
+
+# ---------------------------------------------------------------- time-conditioned nets at one frame time (swnerf_query_points_time)
+PEAK_TFLOPS = 157.3                                                              # fp32 MFMA, 2.4 GHz
+MFMA_FLOP = 32 * 32 * 2 * 2                                                      # one v_mfma_f32_32x32x2_f32
+
+
+def timed_query_row(which, t=0.5):
+    """fused query, then - same process, after a shared warm-up - the op path (what the parent of this feature had to run): the
+    embedders and one full network call per direction, on 1/16 of the grid, extrapolated"""
+    from swnerf import embedder
+    e10, e4, et = embedder.get_embedder(10, 3, 0)[0], embedder.get_embedder(4, 3, 0)[0], embedder.get_embedder(10, 1, 0)[0]
+    if which == "dnerf":
+        tnet = model.DirectTemporalNeRF(D=8, W=256, input_ch=63, input_ch_views=27, input_ch_time=21, output_ch=5, skips=[4],
+                                        use_viewdirs=True, embed_fn=e10, zero_canonical=True)
+        tnet.load_state_dict({k: torch.from_numpy(v) for k, v in synth.dnerf_state_dict(synth.NET_DNERF[0], alpha_bias=synth.NET_DNERF[1]).items()})
+        # per 32 points (swnerf_common.h): TIME 32 + deformation (SW_DEFORM_STEPS - 32) 1920 + canonical trunk 1920 steps, views loop 144 per direction
+        mfma = 4 * (32 + 1920 + 1920) + 4 * 144 * V
+    else:
+        tnet = model.TNeRF(depth=8, in_feat=63, dir_feat=27, time_feat=21, net_dim=128, skip_layer=4)
+        tnet.load_state_dict({k: torch.from_numpy(v) for k, v in synth.tnerf_state_dict(141).items()})
+        # T0 16 + T5 16 + MAIN without layer_9 (544 - 32) steps, DIR 8 + layer_9 32 per direction
+        mfma = 4 * (16 + 16 + 512) + 4 * (8 + 32) * V
+    tnet = tnet.to(dev).eval()
+    sub = pts[:M // 16]
+
+    def op_path(v):
+        d = dirs[v:v + 1].expand(sub.shape[0], 3)
+        te = et(torch.full((sub.shape[0], 1), t, device=dev))
+        if which == "dnerf":
+            return tnet(torch.cat([e10(sub), e4(d)], -1), [te, te])[0]
+        ed = e4(d)
+        return tnet(torch.cat([e10(sub), ed], -1), ed, te).reshape(-1, 4)
+
+    with torch.no_grad():
+        mesh.query_points(tnet, pts[:4096], dirs, True, frame_time=t)             # shared warm-up: pack, kernels, allocator
+        op_path(0)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            out = mesh.query_points(tnet, pts, dirs, True, frame_time=t)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        t_fused = min(ts)
+        t0 = time.perf_counter()
+        acc = torch.zeros((sub.shape[0], 4), device=dev)
+        for v in range(V):
+            acc += op_path(v)
+        torch.cuda.synchronize()
+        t_loop = (time.perf_counter() - t0) * 16
+        err = float((acc[:, :3] / V - out[:M // 16, :3]).abs().max())
+    tf = (M / 32) * mfma * MFMA_FLOP / t_fused / 1e12
+    print(f"| {which} grid {R}^3 = {M:,} points x {V} view directions at t = {t} | fused query (swnerf_query_points_time) | {t_fused*1e3:.1f} ms | "
+          f"{M*V/t_fused/1e6:.0f} M point-views/s | {mfma} MFMAs per 32 points: {tf:.1f} TFLOP/s executed = {tf / PEAK_TFLOPS * 100:.1f} % of the fp32-MFMA peak |")
+    print(f"| same, op path: embed + one full network call per direction (extrapolated from 1/16 of the grid) | | {t_loop*1e3:.0f} ms | "
+          f"{M*V/t_loop/1e6:.0f} M point-views/s | {t_loop / t_fused:.1f} x the fused query |")
+    print(f"| max abs difference of the view-averaged colours between the two | {err:.2e} | | | |")
+
+
+if "--dnerf" in sys.argv or "--tnerf" in sys.argv:
+    for which in ("dnerf", "tnerf"):
+        if "--" + which in sys.argv:
+            timed_query_row(which)
+    sys.exit(0)
 if not MC_ONLY:
     with torch.no_grad():
         mesh.query_points(net, pts[:4096], dirs, True)
