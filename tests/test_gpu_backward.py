@@ -289,7 +289,8 @@ def _dnerf_net(dev, sd_np):
 @pytest.mark.parametrize("M", [300, 32, 1])
 def test_dnerf_mlp_backward_matches_autograd(dev, M):
     """DirectTemporalNeRF.forward at t != 0 with gradients on BOTH outputs (out and dx = position_delta, the TV-loss
-    operand of d_nerf/run_dnerf.py:690-725): every parameter gradient of `_time`, `_time_out` and `_occ`."""
+    operand of d_nerf/run_dnerf.py:690-725): every parameter gradient of `_time`, `_time_out` and `_occ`.
+    (The same inputs against float64 with exact ReLU-flip accounting, at 2e-5: tests/test_gpu_dnerf_train.py.)"""
     sd_np = cases.weights_dnerf()
     x = T(cases.g4_inputs()["x"][:M])
     t_emb = O.embed(torch.full((M, 1), 0.5), 10)
@@ -343,7 +344,8 @@ def test_dnerf_training_step_with_tv_loss(dev):
     """The D-NeRF training loss (d_nerf/run_dnerf.py:690-725): image loss at the frame's time plus the TV term between
     position_delta at two times on the SAME depths (`z_vals=extras['z_vals'].detach()`), through render_rays on the
     differentiable op path.  Compared with autograd through the CPU oracle; the tolerance is set by gamma()'s top
-    band, which turns the oracle's 1e-7 difference in dx into ~5e-5 in the re-embedded features."""
+    band, which turns the oracle's 1e-7 difference in dx into ~5e-5 in the re-embedded features.
+    (tests/test_gpu_dnerf_train.py holds the same loss to 2e-5 of a float64 evaluation at the kernel's own x + dx.)"""
     import swnerf.embedder as embedder, swnerf.render_dnerf as rd
     sd_np = cases.weights_dnerf()
     g = cases.g8_inputs(n=40)
