@@ -688,6 +688,24 @@ int swnerf_multires_loss(int n_levels, const int* patch_hw /*HOST*/, const float
                          int add_global, float* losses, float* reconstructed, float* const* d_rgb /*HOST*/,
                          float* const* d_rgb0 /*HOST, may be NULL*/, void* stream);
 
+/* ---- dataset images (the loaders under dataloader/: imageio.imread, cv2.resize INTER_AREA; csrc/image_kernels.hip) ---
+ * png_unfilter: filtered = DEVICE uint8 [n][H * (1 + W * bpp)], the inflated scanlines of n PNGs of equal size, every row led
+ *   by its filter-type byte; out = DEVICE uint8 [n, H, W, bpp], bpp 3 or 4 (else SWNERF_E_ARG).  The five filters of the PNG
+ *   specification: a, b, c = the unfiltered bytes to the left, above and above-left, 0 outside the image; Average adds
+ *   (a + b) >> 1 of the 9-bit sum, Paeth prefers a, then b, then c on ties; everything mod 256.  status = DEVICE int32 [n]:
+ *   0, or 1 + row of the first row of that image whose type byte is above 4 (the rest of that image is then unspecified; the
+ *   other images are not affected).  One workgroup per image, rows on a skewed wavefront.  H, W in 1..2^20.
+ * area_resize: src [n, H, W, c] uint8 (src_u8 != 0) or float32, c in 1..4 -> dst float32 [n, h, w, c], 1 <= h <= H and
+ *   1 <= w <= W (larger is SWNERF_E_ARG).  A byte converts as (float)((double)u / 255.).  dst(i, j) is the area mean that
+ *   INTER_AREA defines for down-scaling: source cell (y, x) weighs overlap([i H/h, (i+1) H/h), [y, y+1)) *
+ *   overlap([j W/w, (j+1) W/w), [x, x+1)) * h w / (H W); the overlaps are exact integers over h and w, the sum is fp64 and each
+ *   output is rounded once.  h | H and w | W: a plain fp64 sum of the block divided by its size (exact for power-of-two
+ *   factors); h == H and w == W is the plain conversion. */
+int swnerf_png_unfilter(const uint8_t* filtered, int64_t n, int64_t H, int64_t W, int bpp, uint8_t* out, int32_t* status,
+                        void* stream);
+int swnerf_area_resize(const void* src, int src_u8, int64_t n, int64_t H, int64_t W, int c, int64_t h, int64_t w, float* dst,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

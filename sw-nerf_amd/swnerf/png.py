@@ -2,7 +2,8 @@
 `imageio.imwrite(filename, to8b(rgb))` (nerf/run.py:210-213, d_nerf/run_dnerf.py:222-230); imageio is not a
 dependency of this package.  8-bit grey, grey+alpha, RGB or RGBA, no interlacing, filter type 0.  read_png is the input
 side of the D-NeRF metrics notebook (`imageio.imread` of estim/ and gt/ frames): 8-bit RGB or RGBA (alpha dropped), no
-interlacing, all five filter types, any number of IDAT chunks; anything else is refused."""
+interlacing, all five filter types, any number of IDAT chunks; anything else is refused.  read_png_filtered stops after the
+inflate: the dataset loaders (swnerf.images.load_pngs) undo the filters on the device."""
 import struct
 import zlib
 
@@ -67,8 +68,8 @@ def _unfilter(raw, h, w, bpp):
     return out
 
 
-def read_png(filename):
-    """-> uint8 [H,W,3].  8-bit RGB or RGBA (alpha dropped), non-interlaced; raises ValueError on anything else."""
+def _read_scanlines(filename):
+    """Signature, chunk and CRC checks, IHDR validation and the inflate -> (filtered scanlines, h, w, channels)"""
     with open(filename, "rb") as f:
         data = f.read()
     if data[:8] != b"\x89PNG\r\n\x1a\n":
@@ -96,6 +97,21 @@ def read_png(filename):
     if depth != 8 or color not in (2, 6) or comp != 0 or filt != 0 or interlace != 0 or w == 0 or h == 0:
         raise ValueError(f"read_png: {filename}: only 8-bit RGB / RGBA non-interlaced PNGs are supported "
                          f"(bit depth {depth}, colour type {color}, interlace {interlace})")
-    c = 3 if color == 2 else 4
-    img = _unfilter(zlib.decompress(b"".join(idat)), h, w, c).reshape(h, w, c)
+    return zlib.decompress(b"".join(idat)), h, w, 3 if color == 2 else 4
+
+
+def read_png_filtered(filename):
+    """-> (filtered, H, W, channels): the inflated scanlines as bytes, H rows of 1 + W * channels bytes, each led by its filter-type
+    byte - what swnerf.images.unfilter undoes on the device.  The file checks and refusals are read_png's, message for message;
+    nothing is unfiltered and the alpha channel stays."""
+    raw, h, w, c = _read_scanlines(filename)
+    if len(raw) != h * (w * c + 1):
+        raise ValueError(f"read_png: image data holds {len(raw)} bytes, expected {h * (w * c + 1)}")
+    return raw, h, w, c
+
+
+def read_png(filename):
+    """-> uint8 [H,W,3].  8-bit RGB or RGBA (alpha dropped), non-interlaced; raises ValueError on anything else."""
+    raw, h, w, c = _read_scanlines(filename)
+    img = _unfilter(raw, h, w, c).reshape(h, w, c)
     return np.ascontiguousarray(img[..., :3])
