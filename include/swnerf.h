@@ -706,6 +706,33 @@ int swnerf_png_unfilter(const uint8_t* filtered, int64_t n, int64_t H, int64_t W
 int swnerf_area_resize(const void* src, int src_u8, int64_t n, int64_t H, int64_t W, int c, int64_t h, int64_t w, float* dst,
                        void* stream);
 
+/* ---- LPIPS (nerf/run.py:49-61 lpips.LPIPS(net='alex'); d_nerf/metrics.ipynb lpips.LPIPS(net='vgg'); csrc/lpips_kernels.hip,
+ * DESIGN.md 6f "LPIPS") -----------------------------------------------------------------------------------------------
+ * Activations are [n, h, w, c] fp32 NHWC, contiguous; sides in 1..2^20, channels in 1..2^20; every element offset is 64-bit.
+ * n == 0 is a successful no-op.  No host synchronisation, no atomics: bit-identical from run to run.
+ * conv2d_pack: weight = torch's [cout, cin, ksz, ksz] -> packed [ksz * ksz * cin, cout], K in (ky, kx, ci) order: the stream
+ *   conv2d_nhwc reads.  Pack once per weight tensor.
+ * conv2d_nhwc: out[n, oy, ox, co] = act(bias[co] + sum_{ky,kx,ci} in[n, oy s - p + ky, ox s - p + kx, ci] packed[(ky, kx, ci), co]),
+ *   zero padding, out [n, ho, wo, cout] with ho = (h + 2 pad - ksz) / stride + 1 (floor), wo likewise.  An implicit GEMM on the
+ *   fp32 MFMA (fp32 operands and accumulation; the k-ordered sum is cut into segments of 128 k), no im2col buffer.  Square
+ *   kernels 1..11, stride 1..4, pad 0..5, any cin and cout >= 1, act = SWNERF_ACT_NONE or SWNERF_ACT_RELU (a NaN stays a NaN);
+ *   bias may be NULL.  Anything else, or an image with no window, is SWNERF_E_ARG.  16-byte loads along cin when cin % 4 == 0 and
+ *   `in` is 16-byte aligned, along cout when cout % 4 == 0 and `packed` is; 4-byte loads otherwise.  One launch.
+ * maxpool2d_nhwc: window 2 or 3, stride 2, floor mode, no padding (torchvision's MaxPool2d(2, 2) / (3, 2)):
+ *   out [n, (h - window) / 2 + 1, (w - window) / 2 + 1, c].  A NaN in the window gives a NaN, as torch.max_pool2d does.
+ * lpips_layer: one tap.  f0, f1 [n, h, w, c], lin [c]: per pixel d = sum_c lin_c (f0_c / (|f0|_2 + 1e-10) - f1_c / (|f1|_2 +
+ *   1e-10))^2 in fp32; out (DEVICE double [n]) = the mean of d over the h w pixels, summed in fp64 in a fixed order (block
+ *   partials, then one finishing pass); accumulate != 0 adds it to out instead.  map (may be NULL): [n, h, w] the per-pixel d.
+ *   workspace: DEVICE, swnerf_lpips_layer_workspace_bytes(n, h, w) bytes (0 for arguments the call refuses).  Two launches. */
+int swnerf_conv2d_pack(const float* weight, int cout, int cin, int ksz, float* packed, void* stream);
+int swnerf_conv2d_nhwc(const float* in, int64_t n, int64_t h, int64_t w, int cin, const float* packed,
+                       const float* bias /* may be NULL */, int cout, int ksz, int stride, int pad, int act, float* out,
+                       void* stream);
+int swnerf_maxpool2d_nhwc(const float* in, int64_t n, int64_t h, int64_t w, int c, int window, float* out, void* stream);
+size_t swnerf_lpips_layer_workspace_bytes(int64_t n, int64_t h, int64_t w);
+int swnerf_lpips_layer(const float* f0, const float* f1, const float* lin, int64_t n, int64_t h, int64_t w, int c,
+                       int accumulate, void* workspace, double* out, float* map /* may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

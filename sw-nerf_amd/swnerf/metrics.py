@@ -8,14 +8,16 @@ The reference scores a model two ways, and neither runs on this stack (skimage a
     (11x11 Gaussian window, population covariance, L from the prediction's range).
 Both run here through one batched HIP entry point, swnerf_image_metrics: `image_metrics` is the batch interface,
 `peak_signal_noise_ratio` / `structural_similarity` / `calculate_metrics` accept the reference's calls verbatim, and
-`MSE` / `PSNR` / `SSIM` / `estim_error` mirror the notebook.  LPIPS is not computed: it needs pretrained network weights
-this project does not have (`calculate_metrics` returns None in its place)."""
+`MSE` / `PSNR` / `SSIM` / `estim_error` mirror the notebook.  LPIPS (swnerf.lpips: the AlexNet / VGG16 trunks on HIP convolutions)
+is computed when the caller supplies the two weight files it needs; this project ships none, and without a model
+`calculate_metrics` returns None in its place and the dicts carry no 'lpips'."""
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from .lpips import LPIPS, LPIPS_notebook  # noqa: F401
 
 MODES = {"skimage": _lib.SSIM_SKIMAGE, "gauss11": _lib.SSIM_GAUSS11}
 WINDOW = {_lib.SSIM_SKIMAGE: 7, _lib.SSIM_GAUSS11: 11}
@@ -182,18 +184,34 @@ def structural_similarity(im1, im2, *, win_size=None, gradient=False, data_range
     return np.float64(r["ssim"][0].item())
 
 
-def calculate_metrics(gt, pred):
+def _lpips_gt_pred(lpips_model, gts, preds):
+    """the reference's call, nerf/run.py:59-60: lpips_model(gt, np.clip(pred, 0, 1)) on [0, 1] values with the package's default
+    normalize=False - the reference does NOT map them to the [-1, 1] the network was trained on; mirrored as it is"""
+    if isinstance(preds, torch.Tensor):
+        preds = preds.clamp(0.0, 1.0)
+    else:
+        preds = np.clip(np.asarray(preds), 0.0, 1.0)
+    return lpips_model(gts, preds, normalize=False, layout="nhwc")
+
+
+def calculate_metrics(gt, pred, lpips_model=None):
     """nerf/run.py:49-61: (psnr, ssim, lpips) of one [H,W,3] frame, pred clipped to [0, 1], data_range = gt.max() - gt.min().
-    LPIPS is not computed (no pretrained weights): the third value is None."""
+    lpips_model: a metrics.LPIPS (the reference builds net='alex'); the third value is then its [1,1,1,1] tensor for
+    (gt, clipped pred), passed as the reference passes them: [0, 1] values with normalize=False.  Without a model it is None."""
     _hwc_pair(gt, pred, "calculate_metrics")
     r = image_metrics(pred, gt, mode="skimage", data_range="gt", clip_pred=True)
-    return np.float64(r["psnr"][0].item()), np.float64(r["ssim"][0].item()), None
+    lp = None if lpips_model is None else _lpips_gt_pred(lpips_model, gt, pred)
+    return np.float64(r["psnr"][0].item()), np.float64(r["ssim"][0].item()), lp
 
 
-def batch_metrics(gts, preds):
-    """calculate_metrics over a batch of frames in one call: -> (psnr list, ssim list) of Python floats."""
+def batch_metrics(gts, preds, lpips_model=None):
+    """calculate_metrics over a batch of frames in one call: -> (psnr list, ssim list) of Python floats, and with a
+    lpips_model a third list, the LPIPS of every (gt, clipped pred) pair."""
     r = image_metrics(preds, gts, mode="skimage", data_range="gt", clip_pred=True)
-    return r["psnr"].cpu().tolist(), r["ssim"].cpu().tolist()
+    if lpips_model is None:
+        return r["psnr"].cpu().tolist(), r["ssim"].cpu().tolist()
+    lp = _lpips_gt_pred(lpips_model, gts, preds)
+    return r["psnr"].cpu().tolist(), r["ssim"].cpu().tolist(), lp.reshape(-1).cpu().tolist()
 
 
 # ---- d_nerf/metrics.ipynb: NCHW batches, (pred, gt) order -----------------------------------------------------------
@@ -223,8 +241,13 @@ class SSIM(object):
         return s.mean() if size_average else s
 
 
-def estim_error(estim, gt):
-    """the notebook's estim_error without LPIPS: {'mse', 'psnr', 'ssim'} of NCHW batches, one kernel pass"""
+def estim_error(estim, gt, lpips_model=None):
+    """the notebook's estim_error: {'mse', 'psnr', 'ssim'} of NCHW batches, one kernel pass; with a lpips_model (an
+    LPIPS_notebook, or a metrics.LPIPS, which is then called as the notebook's class calls it) also 'lpips'"""
     r = _nchw(estim, gt)
     mse = float(r["mse"].mean())
-    return {"mse": mse, "psnr": 10 * math.log10(1 / mse) if mse != 0 else math.inf, "ssim": float(r["ssim"].mean())}
+    errors = {"mse": mse, "psnr": 10 * math.log10(1 / mse) if mse != 0 else math.inf, "ssim": float(r["ssim"].mean())}
+    if lpips_model is not None:
+        lp = torch.mean(lpips_model(estim, gt, normalize=True)) if isinstance(lpips_model, LPIPS) else lpips_model(estim, gt)
+        errors["lpips"] = float(lp)
+    return errors

@@ -367,17 +367,27 @@ def render_path_multires(render_poses, render_times, hwf, chunk, render_kwargs_t
     return frames, per_level
 
 
-def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, render_factor=0):
+def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, render_factor=0, lpips_weights=None):
     """nerf/run.py:557-596 (`--render_only --render_test`): render.render_path, then calculate_metrics(gt, pred) of every
     frame (pred clipped to [0, 1], data_range = gt.max() - gt.min(), skimage's PSNR and 7x7 SSIM), all frames in one
-    batched GPU call.  Writes savedir/metrics.json = {"psnr": [...], "ssim": [...]} (indent 4; no "lpips": LPIPS is not
-    computed) and returns (rgbs, metrics).  The reference's video.mp4 is not written."""
+    batched GPU call.  Writes savedir/metrics.json = {"psnr": [...], "ssim": [...]} (indent 4) and returns (rgbs, metrics).
+    lpips_weights (or render_kwargs['lpips_weights']): what metrics.LPIPS takes as `weights`; the file then also holds
+    "lpips": [...], the AlexNet LPIPS of every frame as the reference calls it.  Without it there is no such key.  The
+    reference's video.mp4 is not written."""
     os.makedirs(savedir, exist_ok=True)
+    if lpips_weights is None and 'lpips_weights' in render_kwargs:
+        lpips_weights = render_kwargs['lpips_weights']
+    if 'lpips_weights' in render_kwargs:
+        render_kwargs = {k: v for k, v in render_kwargs.items() if k != 'lpips_weights'}
     rgbs, _ = render.render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=gt_imgs, savedir=savedir,
                                  render_factor=render_factor)
     gts = gt_imgs.cpu().numpy() if isinstance(gt_imgs, torch.Tensor) else np.asarray(gt_imgs)
-    psnr, ssim = metrics.batch_metrics(gts, rgbs)
-    out = {"psnr": psnr, "ssim": ssim}
+    if lpips_weights is None:
+        psnr, ssim = metrics.batch_metrics(gts, rgbs)
+        out = {"psnr": psnr, "ssim": ssim}
+    else:
+        psnr, ssim, lp = metrics.batch_metrics(gts, rgbs, lpips_model=metrics.LPIPS("alex", weights=lpips_weights))
+        out = {"psnr": psnr, "ssim": ssim, "lpips": lp}
     with open(os.path.join(savedir, "metrics.json"), "w") as f:
         json.dump(out, f, indent=4)
     return rgbs, out
@@ -394,13 +404,19 @@ def _read_images_in_dir(imgs_dir):
     return np.stack(imgs)
 
 
-def evaluate_dir(files_dir):
+def evaluate_dir(files_dir, lpips_weights=None, args=None):
     """The last cell of d_nerf/metrics.ipynb for a D-NeRF or T-NeRF render directory (render_path(..., save_also_gt=True)
     wrote files_dir/estim and files_dir/gt): estim_error of the two batches, written to files_dir/metrics.txt as str(dict).
-    -> {'mse', 'psnr', 'ssim'} (no 'lpips': LPIPS is not computed)."""
+    -> {'mse', 'psnr', 'ssim'}, and with lpips_weights (or args.lpips_weights; what metrics.LPIPS takes as `weights`) also
+    'lpips', the notebook's VGG LPIPS; without them there is no such key."""
     estim = _read_images_in_dir(os.path.join(files_dir, "estim"))
     gt = _read_images_in_dir(os.path.join(files_dir, "gt"))
-    errors = metrics.estim_error(estim, gt)
+    if lpips_weights is None:
+        lpips_weights = getattr(args, "lpips_weights", None)
+    if lpips_weights is None:
+        errors = metrics.estim_error(estim, gt)
+    else:
+        errors = metrics.estim_error(estim, gt, lpips_model=metrics.LPIPS_notebook(weights=lpips_weights))
     with open(os.path.join(files_dir, "metrics.txt"), "w") as f:
         f.write(str(errors))
     return errors

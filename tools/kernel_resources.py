@@ -20,6 +20,7 @@ DYN_LDS = {  # bytes per workgroup, from the swnerf_* launch code (csrc/*.hip)
     "render_pass_backward_kernel<false>": "142,336", "render_pass_backward_kernel<true>": "145,408",
     "mlp_forward_kernel": "107,776 (ring 8) / 140,544 (ring 16, training unit)", "query_points_kernel": "107,776",
     "gemm_tn_dma_kernel": "131,072 (+16,384 B2 rider)",
+    "cv_conv_kernel<2": "68,864", "cv_conv_kernel<1": "52,480",
     "deform_forward_train_kernel": "140,544", "deform_backward_dx_kernel": "140,544", "mlp_backward_dx_kernel": "140,544",
 }
 print("| kernel | registers per lane (VGPR + AGPR) | of which AGPR | scratch B/lane | static LDS B | dynamic LDS B per workgroup |")
