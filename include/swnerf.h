@@ -29,6 +29,7 @@ extern "C" {
 
 #define SWNERF_E_ARG      (-1)   /* bad size / NULL pointer / unsupported shape */
 #define SWNERF_E_UNSUPP   (-2)   /* valid in the reference, not built here (message says what) */
+#define SWNERF_E_DATA     (-3)   /* the bytes of a file are corrupt (message says where) */
 
 /* packed-network kinds (swnerf_packed_floats / swnerf_pack_*) */
 #define SWNERF_NET_CANON   0     /* vallina_NeRF == NeRFOriginal: 8x256, skip@4, view branch */
@@ -705,6 +706,42 @@ int swnerf_png_unfilter(const uint8_t* filtered, int64_t n, int64_t H, int64_t W
                         void* stream);
 int swnerf_area_resize(const void* src, int src_u8, int64_t n, int64_t H, int64_t W, int c, int64_t h, int64_t w, float* dst,
                        void* stream);
+
+/* ---- baseline JPEG frames (the LLFF scenes' .JPG camera files, the .jpg pictures of 2d_pos_encoding; imageio.imread ends in libjpeg's default
+ * decode, and these entries give its pixels byte for byte; csrc/jpeg_host.h, jpeg_math.h, jpeg_kernels.hip, DESIGN.md 6k "JPEG") ---
+ * The host reads markers and the Huffman stream, the device dequantises, inverts the DCT, up-samples chroma and converts colour.
+ * Decodable here: 8-bit, Huffman-coded, ONE interleaved scan, 1 component or 3 that libjpeg takes for YCbCr (a JFIF marker; or
+ *   an Adobe marker with transform 1; or neither and component ids other than 'R','G','B'), luma sampled 1x1, 2x1 or 2x2 with
+ *   chroma 1x1.  Anything else - progressive, arithmetic, 12-bit, 4 components, RGB-coded, other ratios, several scans, a header
+ *   that cannot be read - returns SWNERF_E_UNSUPP ("not decodable here", the message says why): the caller hands the file to
+ *   another decoder.  A single component is always SWNERF_JPEG_444.
+ * jpeg_header (HOST only, no GPU call): data = the file's bytes.  info [SWNERF_JPEG_INFO_LEN] = H, W, components (1 or 3),
+ *   sampling (SWNERF_JPEG_*), restart interval in MCUs (0: none), offset of the entropy-coded segment, 0, 0.  qt
+ *   [SWNERF_JPEG_QT_LEN] = one 64-entry table per component in natural (row-major, de-zigzagged) order, 8- and 16-bit tables alike.
+ * jpeg_coef_count: 64 * the blocks of all components, each plane padded to whole MCUs (MCU = 8 hs x 8 vs pixels); 0 for a
+ *   geometry jpeg_decode refuses.
+ * jpeg_entropy (HOST only, no GPU call, no global state: safe from several threads): coef [coef_count] int16 = one
+ *   [blocks_y][blocks_x][64] plane per component, natural order, every entry written.  Resets the DC predictors at restart
+ *   markers and checks their sequence.  SWNERF_E_DATA: the segment is truncated, holds an unassigned code, runs a coefficient
+ *   index past 63 or lacks the RSTn it should have (libjpeg's "pad with zeros and warn" is not copied).  Reads nothing past
+ *   data + len and writes nothing outside coef; coef_count must be jpeg_coef_count of the file's header (else SWNERF_E_ARG).
+ * jpeg_decode: n images of one geometry.  coef = DEVICE int16 [n][jpeg_coef_count] (16-byte aligned), qt = DEVICE uint16
+ *   [n][ncomp][64] (16-byte aligned; every image has its own tables), scratch_planes = DEVICE uint8 [n][jpeg_coef_count] (8-byte
+ *   aligned; the component planes, overwritten), out = DEVICE uint8 [n, H, W, channels_out], channels_out 3 or 4 (alpha = 255).
+ *   coef * q; libjpeg's "islow" inverse DCT (13-bit constants, columns descaled by 11 bits, rows by 18, + 128, clamped); its
+ *   "fancy" triangle up-sampling, plain replication when a chroma plane is at most 2 samples wide; its 16-bit fixed-point
+ *   YCbCr -> RGB; a single component gives R = G = B.  32-bit arithmetic with unsigned wrap-around: a crafted file gives defined
+ *   pixels.  Two launches, no atomics, no host synchronisation; n == 0 is a successful no-op; H, W in 1..65535. */
+#define SWNERF_JPEG_444 0
+#define SWNERF_JPEG_422 1
+#define SWNERF_JPEG_420 2
+#define SWNERF_JPEG_INFO_LEN 8
+#define SWNERF_JPEG_QT_LEN 192
+int     swnerf_jpeg_header(const uint8_t* data /*HOST*/, int64_t len, int32_t* info /*HOST*/, uint16_t* qt /*HOST*/);
+int64_t swnerf_jpeg_coef_count(int64_t H, int64_t W, int ncomp, int sampling);
+int     swnerf_jpeg_entropy(const uint8_t* data /*HOST*/, int64_t len, int16_t* coef /*HOST*/, int64_t coef_count);
+int     swnerf_jpeg_decode(const int16_t* coef, const uint16_t* qt, int64_t n, int64_t H, int64_t W, int ncomp, int sampling,
+                           int channels_out, uint8_t* scratch_planes, uint8_t* out, void* stream);
 
 /* ---- LPIPS (nerf/run.py:49-61 lpips.LPIPS(net='alex'); d_nerf/metrics.ipynb lpips.LPIPS(net='vgg'); csrc/lpips_kernels.hip,
  * DESIGN.md 6f "LPIPS") -----------------------------------------------------------------------------------------------

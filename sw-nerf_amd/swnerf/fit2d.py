@@ -206,8 +206,13 @@ def encode(pos, L):
 
 
 def load_picture(args):
-    """encoding.py:4-20: positions [(H*W), 2] (x fastest), colours [(H*W), 3] in [0, 1], width, height."""
-    from PIL import Image
+    """encoding.py:4-20: positions [(H*W), 2] (x fastest), colours [(H*W), 3] in [0, 1], width, height.  Without PIL the picture
+    (.png, or a baseline .jpg: libjpeg's pixels byte for byte) is decoded on the GPU by swnerf.images."""
+    try:
+        from PIL import Image
+    except ImportError:
+        from . import images
+        return picture_tensors(images.load_pngs([args.picture_dir])[0, ..., :3].cpu().numpy())
     return picture_tensors(np.asarray(Image.open(args.picture_dir).convert('RGB')))
 
 

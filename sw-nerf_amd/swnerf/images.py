@@ -1,9 +1,14 @@
 """The image stage of the dataset loaders (dataloader/*.py: `imageio.imread` of every frame, `cv2.resize(..., INTER_AREA)` for
 half_res): the host parses chunks and inflates (swnerf.png.read_png_filtered), the device undoes the PNG row filters and
 down-samples (csrc/image_kernels.hip).  The filtered bytes are exactly as large as the pixels and have to reach
-the device anyway, so loading costs about what zlib costs.  There is no CPU path: png.read_png is the host reader."""
+the device anyway, so loading costs about what zlib costs.  There is no CPU path: png.read_png is the host reader.
+Baseline JPEG frames go the same way: the host reads markers and the Huffman stream (csrc/jpeg_host.h), the device dequantises,
+inverts the DCT, up-samples chroma and converts colour with libjpeg's integer arithmetic (csrc/jpeg_kernels.hip), so the pixels
+are imageio.imread's byte for byte.  A JPEG that is not decodable natively (progressive, arithmetic-coded, ...) goes to PIL."""
+import ctypes
 import os
 import struct
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -89,9 +94,92 @@ def area_resize(images, h, w):
     return dst[0] if single else dst
 
 
+class _Jpeg:
+    """the header of a natively decodable JPEG file and its bytes; coefficients() is the Huffman decode"""
+
+    def __init__(self, data, info, qt, name):
+        self.data, self.name = data, name
+        self.H, self.W, self.ncomp, self.sampling = (int(v) for v in info[:4])
+        self.qt = qt[:self.ncomp * 64]
+        self.ncoef = int(_lib.lib().swnerf_jpeg_coef_count(self.H, self.W, self.ncomp, self.sampling))
+        self.kind = ("jpeg", self.ncomp, self.sampling)
+
+    def coefficients(self):
+        """int16 [ncoef]; ValueError names the file when its entropy-coded segment is corrupt"""
+        coef = np.empty((self.ncoef,), np.int16)
+        rc = _lib.lib().swnerf_jpeg_entropy(self.data, len(self.data), coef.ctypes.data, self.ncoef)     # ctypes drops the GIL
+        if rc == _lib.E_DATA:
+            raise ValueError(f"swnerf.images: {self.name}: {_lib.lib().swnerf_last_error().decode('utf-8', 'replace')}")
+        _lib.check(rc, "jpeg_entropy")
+        return coef
+
+
+def _jpeg_header(data, name="<bytes>"):
+    """-> _Jpeg, or None when the file is "not decodable here" (another decoder's turn).  No GPU call."""
+    info = (ctypes.c_int32 * _lib.JPEG_INFO_LEN)()
+    qt = np.zeros((_lib.JPEG_QT_LEN,), np.uint16)
+    rc = _lib.lib().swnerf_jpeg_header(data, len(data), info, qt.ctypes.data)
+    if rc == _lib.E_UNSUPP:
+        return None
+    _lib.check(rc, "jpeg_header")
+    return _Jpeg(data, list(info), qt, name)
+
+
+def _jpeg_decode_into(coef, qt, n, H, W, ncomp, sampling, out):
+    """coef: the int16 coefficients of n images, qt: their uint16 tables [n * ncomp * 64], on the device (any dtype of the right
+    byte count) -> out uint8 [n,H,W,3|4]; two launches, nothing waits"""
+    planes = torch.empty((coef.numel() * coef.element_size() // 2,), dtype=torch.uint8, device=out.device)
+    _lib.check(_lib.lib().swnerf_jpeg_decode(_lib.ptr(coef), _lib.ptr(qt), n, H, W, ncomp, sampling, int(out.shape[-1]),
+                                             _lib.ptr(planes), _lib.ptr(out), _lib.stream_of(out)), "jpeg_decode")
+
+
+_JPEG_WORKERS = 4                                                        # Huffman decoding ahead of the device; never more than 8
+
+
+def decode_jpegs(files, device=None, channels=3):
+    """files: the bytes of N baseline JPEG files of one size -> uint8 [N,H,W,channels] on the device, channels 3 (RGB) or 4 (alpha
+    255): libjpeg's default decode byte for byte.  The host decodes the Huffman streams (a few files side by side), the device does
+    the rest, one launch pair per run of files of one sampling.  ValueError: a file that is not decodable natively (progressive,
+    arithmetic-coded, 12-bit, CMYK, RGB-coded, unusual sampling, several scans - the message says which), a corrupt
+    entropy-coded segment, files of different sizes."""
+    dev = _device(device)
+    if channels not in (3, 4):
+        raise ValueError(f"swnerf.images.decode_jpegs: channels must be 3 or 4, got {channels!r}")
+    heads = []
+    for i, data in enumerate(files):
+        j = _jpeg_header(bytes(data), f"file {i}")
+        if j is None:
+            raise ValueError(f"swnerf.images.decode_jpegs: file {i}: {_lib.lib().swnerf_last_error().decode('utf-8', 'replace')}")
+        if heads and (j.H, j.W) != (heads[0].H, heads[0].W):
+            raise ValueError(f"swnerf.images.decode_jpegs: file {i} is {j.H} x {j.W}, file 0 is {heads[0].H} x {heads[0].W}: one call decodes one size")
+        heads.append(j)
+    if not heads:
+        raise ValueError("swnerf.images.decode_jpegs: no files")
+    out = torch.empty((len(heads), heads[0].H, heads[0].W, channels), dtype=torch.uint8, device=dev)
+    with ThreadPoolExecutor(max_workers=min(_JPEG_WORKERS, len(heads))) as pool:
+        coefs = list(pool.map(_Jpeg.coefficients, heads))
+    start = 0
+    while start < len(heads):
+        end = start + 1
+        while end < len(heads) and heads[end].kind == heads[start].kind:
+            end += 1
+        with torch.cuda.device(dev):
+            coef = torch.from_numpy(np.concatenate(coefs[start:end])).to(dev)
+            qt = torch.from_numpy(np.concatenate([j.qt for j in heads[start:end]]).view(np.int16)).to(dev)
+            j = heads[start]
+            _jpeg_decode_into(coef, qt, end - start, j.H, j.W, j.ncomp, j.sampling, out[start:end])
+        start = end
+    return out
+
+
 def image_size(path):
-    """(H, W, channels) from the file's header alone: the IHDR chunk of a PNG; PIL for .jpg / .jpeg"""
+    """(H, W, channels) from the file's header alone: the IHDR chunk of a PNG; the frame header of a .jpg / .jpeg (PIL when the
+    file is not decodable natively)"""
     if path.lower().endswith(_JPEG):
+        with open(path, "rb") as f:
+            j = _jpeg_header(f.read(), path)
+        if j is not None:
+            return j.H, j.W, 3
         with _pil().open(path) as im:
             return im.size[1], im.size[0], 3
     with open(path, "rb") as f:
@@ -106,35 +194,65 @@ def _pil():
     try:
         from PIL import Image
     except ImportError as e:
-        raise RuntimeError("swnerf.images.load_pngs: .jpg / .jpeg frames are decoded by PIL, which is not installed; "
-                           "convert them to 8-bit PNG (this package decodes only PNG itself)") from e
+        raise RuntimeError("swnerf.images.load_pngs: this .jpg / .jpeg frame is not a baseline JPEG this package decodes itself "
+                           "(8-bit, Huffman-coded, one scan, gray or YCbCr at 4:4:4 / 4:2:2 / 4:2:0); such files are decoded by PIL, "
+                           "which is not installed; convert them to baseline JPEG or 8-bit PNG") from e
     return Image
 
 
 def _read_host(path):
-    """-> (bytes-like, H, W, channels, filtered?)"""
+    """-> (bytes, H, W, channels, kind, tables): kind True = filtered PNG scanlines, False = plain pixels, ("jpeg", components,
+    sampling) = the int16 coefficients of a natively decodable JPEG, with its quantisation tables (None otherwise)"""
     if path.lower().endswith(_JPEG):
+        with open(path, "rb") as f:
+            j = _jpeg_header(f.read(), path)
+        if j is not None:
+            return j.coefficients().view(np.uint8), j.H, j.W, 3, j.kind, j.qt.view(np.uint8)
         with _pil().open(path) as im:
             a = np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
-        return a.reshape(-1), a.shape[0], a.shape[1], 3, False
+        return a.reshape(-1), a.shape[0], a.shape[1], 3, False, None
     raw, h, w, c = read_png_filtered(path)
-    return np.frombuffer(raw, np.uint8), h, w, c, True
+    return np.frombuffer(raw, np.uint8), h, w, c, True, None
 
 
 def load_pngs(paths, device=None, out_hw=None, chunk_bytes=256 << 20, alpha=None):
-    """Every file of `paths` (8-bit RGB / RGBA PNGs of one size; .jpg / .jpeg through PIL when it imports) as ONE device tensor in
-    `paths` order: uint8 [N,H,W,c], or with out_hw = (h, w) - or a callable (H, W) -> (h, w) - float32 [N,h,w,c] from area_resize.
-    The host inflates runs of files of one kind into pinned staging (two buffers of at most chunk_bytes) and copies without
-    blocking, so the inflate of the next run overlaps the copy, unfilter and resize of this one.
-    ValueError: files of different sizes; RGB and RGBA mixed - unless alpha="add", which appends an opaque alpha (255) to RGB
-    frames as load_custom_data does; a filter-type byte above 4 (names the file and row)."""
+    """Every file of `paths` (8-bit RGB / RGBA PNGs and .jpg / .jpeg files of one size) as ONE device tensor in `paths` order:
+    uint8 [N,H,W,c], or with out_hw = (h, w) - or a callable (H, W) -> (h, w) - float32 [N,h,w,c] from area_resize.
+    The host inflates (PNG) or Huffman-decodes (baseline JPEG) runs of files of one kind into pinned staging (two buffers of at
+    most chunk_bytes, sized from the first file) and copies without blocking, so the host work of the next run overlaps the copy,
+    unfilter / inverse DCT and resize of this one; when a .jpg / .jpeg is among them, the next few files are read ahead on a small
+    thread pool.  A JPEG that is not decodable natively is decoded by PIL when it imports (RuntimeError naming PIL otherwise).
+    ValueError: files of different sizes; 3 and 4 channels mixed - unless alpha="add", which appends an opaque alpha (255) to RGB
+    frames as load_custom_data does; a PNG filter-type byte above 4 (names the file and row); a corrupt entropy-coded segment of
+    a JPEG (names the file)."""
     dev = _device(device)
     paths = [os.fspath(p) for p in paths]
     if not paths:
         raise ValueError("swnerf.images.load_pngs: no files")
     if alpha not in (None, "add"):
         raise ValueError(f"swnerf.images.load_pngs: alpha must be None or 'add', got {alpha!r}")
-    first = _read_host(paths[0])
+    any_jpeg = any(p.lower().endswith(_JPEG) for p in paths)
+    pool = ThreadPoolExecutor(max_workers=min(_JPEG_WORKERS, len(paths))) if any_jpeg and len(paths) > 1 else None
+    try:
+        return _load(paths, dev, out_hw, chunk_bytes, alpha, any_jpeg, pool)
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True, cancel_futures=True)
+
+
+def _load(paths, dev, out_hw, chunk_bytes, alpha, any_jpeg, pool):
+    n = len(paths)
+    ahead = {}                                                           # index -> future of _read_host
+
+    def read(i):
+        if pool is None:
+            return _read_host(paths[i])
+        for j in range(i, min(n, i + 2 * _JPEG_WORKERS)):
+            if j not in ahead:
+                ahead[j] = pool.submit(_read_host, paths[j])
+        return ahead.pop(i).result()
+
+    first = read(0)
     H, W, c0 = first[1:4]
     c_out = 4 if alpha == "add" else c0
     if callable(out_hw):
@@ -143,30 +261,34 @@ def load_pngs(paths, device=None, out_hw=None, chunk_bytes=256 << 20, alpha=None
         out_hw = (int(out_hw[0]), int(out_hw[1]))
         if not (1 <= out_hw[0] <= H and 1 <= out_hw[1] <= W):
             raise ValueError(f"swnerf.images.load_pngs: {H} x {W} -> {out_hw[0]} x {out_hw[1]} is not a down-scale")
-    n = len(paths)
     result = torch.empty((n, H, W, c_out), dtype=torch.uint8, device=dev) if out_hw is None else \
         torch.empty((n,) + out_hw + (c_out,), dtype=torch.float32, device=dev)
     status = torch.zeros((n,), dtype=torch.int32, device=dev)
-    per_max = H * (1 + W * 4)
+    per_max = max(H * (1 + W * 4), int(first[0].shape[0]))               # a JPEG's coefficients are 2 bytes each, planes padded to MCUs
     per_run = max(1, min(n, int(chunk_bytes) // per_max))
     staging = [torch.empty((per_run * per_max,), dtype=torch.uint8).pin_memory() for _ in range(2 if n > per_run else 1)]
+    tables = [torch.empty((per_run * 2 * _lib.JPEG_QT_LEN,), dtype=torch.uint8).pin_memory() for _ in staging] if any_jpeg else None
     copied = [None] * len(staging)                                   # the event after the last copy out of each staging buffer
     stream = torch.cuda.current_stream(dev)
 
-    def flush(k, start, count, c, filtered):
-        """files start .. start + count - 1 lie in staging[k]: copy, unfilter, widen, resize - all enqueued, nothing waits"""
-        per = H * (1 + W * c) if filtered else H * W * c
+    def flush(k, start, count, nbytes, c, kind):
+        """files start .. start + count - 1 lie in staging[k]: copy, unfilter / inverse DCT, widen, resize - all enqueued, nothing waits"""
+        jpeg = isinstance(kind, tuple)
         with torch.cuda.device(dev):
-            d = staging[k][:count * per].to(dev, non_blocking=True)
+            d = staging[k][:nbytes].to(dev, non_blocking=True)
+            q = tables[k][:count * kind[1] * 128].to(dev, non_blocking=True) if jpeg else None
             copied[k] = torch.cuda.Event()
             copied[k].record(stream)
-            direct = out_hw is None and c == c_out
-            px = result[start:start + count] if direct else torch.empty((count, H, W, c), dtype=torch.uint8, device=dev)
-            if filtered:
+            c_px = c_out if jpeg else c                                  # the JPEG kernel writes the opaque alpha itself
+            direct = out_hw is None and c_px == c_out
+            px = result[start:start + count] if direct else torch.empty((count, H, W, c_px), dtype=torch.uint8, device=dev)
+            if jpeg:
+                _jpeg_decode_into(d, q, count, H, W, kind[1], kind[2], px)
+            elif kind:
                 _unfilter_into(d, count, H, W, c, px, status[start:start + count])
             else:
                 px.copy_(d.view(count, H, W, c))
-            if c != c_out:                                               # alpha="add": RGB frames get an opaque alpha
+            if c_px != c_out:                                            # alpha="add": RGB frames get an opaque alpha
                 px = torch.cat([px, torch.full((count, H, W, 1), 255, dtype=torch.uint8, device=dev)], -1)
             if out_hw is not None:
                 _resize_into(px, result[start:start + count])
@@ -175,22 +297,27 @@ def load_pngs(paths, device=None, out_hw=None, chunk_bytes=256 << 20, alpha=None
 
     k, start, count, run_kind, off = 0, 0, 0, None, 0
     for i, p in enumerate(paths):
-        raw, h, w, c, filtered = first if i == 0 else _read_host(p)
+        raw, h, w, c, kind, qt = first if i == 0 else read(i)
         if (h, w) != (H, W):
             raise ValueError(f"swnerf.images.load_pngs: {p} is {h} x {w}, {paths[0]} is {H} x {W}: one call loads one size")
         if c != c0 and alpha != "add":
             raise ValueError(f"swnerf.images.load_pngs: {p} has {c} channels, {paths[0]} has {c0}: pass alpha='add' to append "
                              "an opaque alpha to RGB frames")
-        if count and (run_kind != (c, filtered) or count == per_run):
-            flush(k, start, count, *run_kind)
+        need = int(raw.shape[0])
+        if count and (run_kind != (c, kind) or count == per_run or off + need > staging[k].numel()):
+            flush(k, start, count, off, *run_kind)
             k, start, count, off = (k + 1) % len(staging), i, 0, 0
         if count == 0:
-            run_kind = (c, filtered)
+            run_kind = (c, kind)
             if copied[k] is not None:
                 copied[k].synchronize()                                  # the copy out of this staging buffer has finished
-        staging[k].numpy()[off:off + raw.shape[0]] = raw
-        off += raw.shape[0]
+            if need > staging[k].numel():                                # a JPEG with more coefficients than the first file's
+                staging[k] = torch.empty((need,), dtype=torch.uint8).pin_memory()
+        staging[k].numpy()[off:off + need] = raw
+        if qt is not None:
+            tables[k].numpy()[count * qt.shape[0]:(count + 1) * qt.shape[0]] = qt
+        off += need
         count += 1
-    flush(k, start, count, *run_kind)
+    flush(k, start, count, off, *run_kind)
     _raise_bad_rows(status.cpu(), paths)                                 # the one wait: also ends every copy out of staging
     return result
