@@ -21,7 +21,7 @@ import torch
 
 
 def main(out_dir, H=400, n_poses=4, device="cuda:0"):
-    from swnerf import synth, runner, render, cameras, checkpoint, model
+    from swnerf import synth, runner, render, cameras, checkpoint, model, video
     dev = torch.device(device)
     W = H
     os.makedirs(out_dir, exist_ok=True)
@@ -53,6 +53,8 @@ def main(out_dir, H=400, n_poses=4, device="cuda:0"):
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     print(f"rendered {n_poses} frames of {H}x{W} (64+128 samples) in {dt:.2f} s = {n_poses * H * W / dt:,.0f} rays/s incl. PNG writing -> {frames}")
+    # nerf/run.py:574 writes video.mp4 into the frame directory; here a Motion-JPEG .avi beside it, so the directory holds frames only
+    print("video:", video.mimwrite(frames + "_video.mp4", rgbs, fps=30, quality=8))
     return rgbs, disps, frames
 
 

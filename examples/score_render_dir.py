@@ -8,7 +8,8 @@ point `lpips_weights` (or $SWNERF_LPIPS_DIR) at a directory with the real alexne
 vgg16-397923af.pth / vgg.pth to get those.
 
   1. nerf/run.py --render_only --render_test: runner.render_test(..., lpips_weights=dir) renders the test poses of a seeded
-     net and writes metrics.json with "psnr", "ssim" and "lpips" (AlexNet, called as the reference calls it);
+     net and writes metrics.json with "psnr", "ssim" and "lpips" (AlexNet, called as the reference calls it), and with video=True
+     the reference's video.mp4 as video.avi (Motion-JPEG);
   2. d_nerf/metrics.ipynb: the frames go to estim/ and gt/ as PNGs and runner.evaluate_dir(dir, lpips_weights=dir) writes
      metrics.txt with 'mse', 'psnr', 'ssim' and 'lpips' (VGG, inputs mapped to [-1, 1], the mean over the frames).
 
@@ -72,7 +73,7 @@ def main(out_dir, H=64, n_poses=3, device="cuda:0"):
     poses = torch.from_numpy(cameras.blender_render_poses(n_poses)).to(dev)
     scored = os.path.join(out_dir, "renderonly_test")
     with torch.no_grad():
-        rgbs, m1 = runner.render_test(poses, (Hh, W, focal), K, args.chunk, test_kw, gt, scored, lpips_weights=weights)
+        rgbs, m1 = runner.render_test(poses, (Hh, W, focal), K, args.chunk, test_kw, gt, scored, lpips_weights=weights, video=True)
     print("metrics.json:", json.dumps(m1))
     # the notebook's directory layout: estim/ and gt/ ('000.png' is the canonical frame the notebook skips)
     for sub, frames in (("estim", rgbs), ("gt", gt)):

@@ -3,6 +3,8 @@
 val / test.json and RGBA PNG frames, png.write_png) of a synthetic picture - no dataset is available offline - loads it with
 `data.load_dataset` (the host inflates, the device undoes the PNG filters and, with half_res, takes the area mean) and hands the
 dict to `runner.train` as it is.  The frames stay uint8 RGBA on the device; the batch kernel composites the drawn pixels on white.
+From the command line the run ends as the reference's does, with the spiral of the render poses as two Motion-JPEG .avi files
+(i_video = the last iteration; main(..., video=True)).
 
   python examples/train_from_dataset.py [out_dir] [H=32] [n_train=6] [steps=20] [half_res=0]
 """
@@ -42,7 +44,7 @@ def write_scene(base, H, W, n_train, n_val=2, n_test=2):
             json.dump({"camera_angle_x": synth.LEGO_CAMERA_ANGLE_X, "frames": frames}, fp)
 
 
-def main(out_dir, H=32, n_train=6, steps=20, half_res=False, device="cuda:0"):
+def main(out_dir, H=32, n_train=6, steps=20, half_res=False, device="cuda:0", video=False):
     from swnerf import data, runner
     dev = torch.device(device)
     scene = os.path.join(out_dir, "scene")
@@ -54,7 +56,7 @@ def main(out_dir, H=32, n_train=6, steps=20, half_res=False, device="cuda:0"):
                            use_viewdirs=True, i_embed=0, multires=10, multires_views=4, raw_noise_std=0., white_bkgd=True,
                            no_ndc=False, lindisp=False, chunk=1024 * 32, N_rand=min(512, side * side), no_batching=True,
                            precrop_iters=0, precrop_frac=.5, i_print=max(steps // 4, 1), i_weights=steps, i_testset=10 ** 9,
-                           N_iters=steps, seed=0)
+                           N_iters=steps, seed=0, i_video=steps if video else 10 ** 9)
     d = data.load_dataset(args, device=dev)
     print(f"loaded {tuple(d['images'].shape)} {d['images'].dtype} on {d['images'].device}; hwf {d['hwf']}, near {d['near']}, far {d['far']}, "
           f"split {[len(s) for s in d['i_split']]}")
@@ -62,10 +64,12 @@ def main(out_dir, H=32, n_train=6, steps=20, half_res=False, device="cuda:0"):
     np.random.seed(0)
     record = runner.train(args, d, device=dev)
     print(f"trained {len(record)} steps of {args.N_rand} rays: loss {record[0]['loss']:.4f} -> {record[-1]['loss']:.4f}")
+    if video:                                                                  # nerf/run.py:726-733: the spiral after the last iteration
+        print("video:", os.path.join(out_dir, args.expname, "{}_spiral_{:06d}_rgb.avi".format(args.expname, steps)), "and ..._disp.avi")
     return d, record
 
 
 if __name__ == "__main__":
     a = sys.argv
     main(a[1] if len(a) > 1 else "/tmp/swnerf_dataset_example", int(a[2]) if len(a) > 2 else 32, int(a[3]) if len(a) > 3 else 6,
-         int(a[4]) if len(a) > 4 else 20, bool(int(a[5])) if len(a) > 5 else False)
+         int(a[4]) if len(a) > 4 else 20, bool(int(a[5])) if len(a) > 5 else False, video=True)

@@ -743,6 +743,39 @@ int     swnerf_jpeg_entropy(const uint8_t* data /*HOST*/, int64_t len, int16_t* 
 int     swnerf_jpeg_decode(const int16_t* coef, const uint16_t* qt, int64_t n, int64_t H, int64_t W, int ncomp, int sampling,
                            int channels_out, uint8_t* scratch_planes, uint8_t* out, void* stream);
 
+/* ---- baseline JPEG frames of the render videos (the reference's imageio.mimwrite(..., to8b(rgbs), fps=30, quality=8); these entries
+ * write what libjpeg's default encoder writes for the same pixels, quality and sampling, byte for byte; csrc/jpeg_enc_math.h,
+ * jpeg_enc_host.h, jpeg_enc_kernels.hip, DESIGN.md 6k "JPEG encode") --------------------------------------------------------------
+ * The device converts, down-samples, transforms and quantises; the host writes the markers and the Huffman stream.
+ * jpeg_quant_tables (HOST only): qt [2][64] natural order = the Annex K.1 (luma) and K.2 (chroma) tables scaled as libjpeg's
+ *   jpeg_set_quality does: quality clipped to 1..100, scale = 5000 / quality below 50 and 200 - 2 quality otherwise, each entry
+ *   clamp((base * scale + 50) / 100, 1, 255).
+ * jpeg_file_bound: an upper bound on the bytes jpeg_write makes of this geometry (every coefficient at its longest code plus
+ *   value bits, every byte stuffed); 0 for a geometry jpeg_write refuses.
+ * jpeg_write (HOST only, no GPU call, no global state: safe from several threads): coef [coef_count] int16 in the layout of
+ *   jpeg_entropy (coef_count = jpeg_coef_count of the geometry, else SWNERF_E_ARG), qt [2][64] natural order with entries 1..255
+ *   (the chroma table is read only for 3 components).  Writes SOI, APP0 (JFIF 1.01, density 1 x 1), one DQT per table, SOF0
+ *   (components 1, 2, 3; luma hs x vs, chroma 1 x 1), the Annex K.3 Huffman tables as DC0, AC0, DC1, AC1 (one DHT each), SOS, the
+ *   interleaved scan (0xFF stuffed, the last byte padded with 1-bits) and EOI: no restart markers, no optimised tables.
+ *   Returns the bytes written; SWNERF_E_ARG when they do not fit into `cap` (nothing outside out[0..cap) is written);
+ *   SWNERF_E_DATA for a coefficient no baseline code expresses.
+ * jpeg_encode: n frames of one size.  frames = DEVICE uint8 (src_u8 != 0) or float32 [n, H, W, channels_in], channels_in 1 (R = G
+ *   = B), 3 or 4 (alpha ignored).  A float sample x becomes (uint8)(255.0f * min(max(x', 0), 1)), truncated, NaN -> 0, with
+ *   x' = x when divisor == 0 and the correctly rounded x / divisor otherwise (the reference's to8b(disps / np.max(disps))).
+ *   qt = DEVICE uint16 [ncomp][64] natural order (16-byte aligned), one set for all frames.  ncomp 3 (YCbCr) or 1 (needs
+ *   channels_in 1; SWNERF_JPEG_444).  scratch_planes = DEVICE uint8 [n][jpeg_coef_count] (8-byte aligned; the component planes,
+ *   overwritten), coef = DEVICE int16 [n][jpeg_coef_count] (16-byte aligned) in exactly the layout of jpeg_entropy, so
+ *   jpeg_decode(jpeg_encode(x)) composes.  libjpeg's RGB -> YCbCr, its 2:1 down-sampling without smoothing, edge replication
+ *   (columns before the averaging, rows after it), the "islow" forward DCT and sign(c) ((|c| + 4 q) / (8 q)); a block wholly outside
+ *   the component's real blocks has zero ACs and the DC of the block it continues.  Two launches, no atomics, no host
+ *   synchronisation; n == 0 is a successful no-op; H, W in 1..65535. */
+int     swnerf_jpeg_quant_tables(int quality, uint16_t* qt /*HOST*/);
+int64_t swnerf_jpeg_file_bound(int64_t H, int64_t W, int ncomp, int sampling);
+int64_t swnerf_jpeg_write(const int16_t* coef /*HOST*/, int64_t coef_count, const uint16_t* qt /*HOST*/, int64_t H, int64_t W, int ncomp,
+                          int sampling, uint8_t* out /*HOST*/, int64_t cap);
+int     swnerf_jpeg_encode(const void* frames, int src_u8, int64_t n, int64_t H, int64_t W, int channels_in, float divisor,
+                           const uint16_t* qt, int ncomp, int sampling, uint8_t* scratch_planes, int16_t* coef, void* stream);
+
 /* ---- LPIPS (nerf/run.py:49-61 lpips.LPIPS(net='alex'); d_nerf/metrics.ipynb lpips.LPIPS(net='vgg'); csrc/lpips_kernels.hip,
  * DESIGN.md 6f "LPIPS") -----------------------------------------------------------------------------------------------
  * Activations are [n, h, w, c] fp32 NHWC, contiguous; sides in 1..2^20, channels in 1..2^20; every element offset is 64-bit.

@@ -4,7 +4,10 @@ down-samples (csrc/image_kernels.hip).  The filtered bytes are exa
 the device anyway, so loading costs about what zlib costs.  There is no CPU path: png.read_png is the host reader.
 Baseline JPEG frames go the same way: the host reads markers and the Huffman stream (csrc/jpeg_host.h), the device dequantises,
 inverts the DCT, up-samples chroma and converts colour with libjpeg's integer arithmetic (csrc/jpeg_kernels.hip), so the pixels
-are imageio.imread's byte for byte.  A JPEG that is not decodable natively (progressive, arithmetic-coded, ...) goes to PIL."""
+are imageio.imread's byte for byte.  A JPEG that is not decodable natively (progressive, arithmetic-coded, ...) goes to PIL.
+The way back - encode_jpegs / write_jpeg, the frames of swnerf.video - is the same split run backwards: the device converts,
+down-samples, transforms and quantises (csrc/jpeg_enc_kernels.hip), the host writes the Huffman stream (csrc/jpeg_enc_host.h), and
+the file is what libjpeg writes for the same pixels, quality and sampling, byte for byte."""
 import ctypes
 import os
 import struct
@@ -321,3 +324,141 @@ def _load(paths, dev, out_hw, chunk_bytes, alpha, any_jpeg, pool):
     flush(k, start, count, off, *run_kind)
     _raise_bad_rows(status.cpu(), paths)                                 # the one wait: also ends every copy out of staging
     return result
+
+
+# ---- encode ---------------------------------------------------------------------------------------------------------------
+_SUBSAMPLING = {"4:4:4": "JPEG_444", "4:2:2": "JPEG_422", "4:2:0": "JPEG_420"}
+
+
+def _as_frames(frames):
+    """-> (tensor or ndarray [N,H,W,c], single): [N,H,W,1|3|4]; a 3-D input whose last side is 1, 3 or 4 is ONE frame [H,W,c],
+    any other 3-D input is [N,H,W]; 2-D is one [H,W] frame"""
+    if not isinstance(frames, (torch.Tensor, np.ndarray)):
+        frames = np.asarray(frames)
+    shape = tuple(frames.shape)
+    if len(shape) == 2:
+        return frames[None, :, :, None], True
+    if len(shape) == 3:
+        return (frames[None], True) if shape[-1] in (1, 3, 4) else (frames[..., None], False)
+    if len(shape) == 4 and shape[-1] in (1, 3, 4):
+        return frames, False
+    raise ValueError(f"swnerf.images.encode_jpegs: frames must be [N,H,W,1|3|4], [N,H,W], [H,W,1|3|4] or [H,W], got {shape}")
+
+
+def _jpeg_write_host(coef, qt, H, W, ncomp, sampling, bound):
+    """one frame's int16 coefficients (host) -> the bytes of its file; ctypes drops the GIL for the call"""
+    out = np.empty((bound,), np.uint8)
+    n = _lib.lib().swnerf_jpeg_write(coef.ctypes.data, coef.shape[0], qt.ctypes.data, H, W, ncomp, sampling, out.ctypes.data, bound)
+    if n < 0:
+        _lib.check(int(n), "jpeg_write")
+    return out[:n].tobytes()
+
+
+def encode_jpegs(frames, quality=90, subsampling="4:2:0", divisor=None, components=None, device=None, chunk_bytes=256 << 20):
+    """frames: a device tensor or a numpy array, uint8 or float32, [N,H,W,1|3|4] (alpha ignored), [N,H,W], or one frame without
+    the leading N (a 3-D input whose last side is 1, 3 or 4 is one frame) -> the bytes of N baseline JPEG files: what libjpeg
+    (PIL's Image.save(format="JPEG", quality=quality, subsampling=...)) writes for the same pixels, byte for byte.  A float sample
+    becomes a byte as the reference's to8b does, (uint8)(255 * clip(x, 0, 1)), of x / divisor when a divisor is given
+    (to8b(disps / np.max(disps))); NaN gives 0.  components: 3 (YCbCr; the default, also for 1-channel input, which players handle
+    most reliably) or 1 (a grey file; needs 1-channel input).  The device converts, down-samples, transforms and quantises in
+    chunks of at most chunk_bytes (host arrays go up through pinned staging); while it works on one chunk, the coefficients of the
+    chunk before are Huffman-coded on the small thread pool decode_jpegs uses."""
+    L = _lib.lib()
+    x, _ = _as_frames(frames)
+    on_host = not isinstance(x, torch.Tensor)
+    if on_host:
+        if x.dtype not in (np.uint8, np.float32):
+            raise TypeError(f"swnerf.images.encode_jpegs: frames must be uint8 or float32, got {x.dtype}")
+        x = np.ascontiguousarray(x)
+        dev = _device(device)
+    else:
+        x = _dev_tensor(x, "frames", (torch.uint8, torch.float32))
+        dev = x.device
+    n, H, W, cin = (int(v) for v in x.shape)
+    ncomp = 3 if components is None else int(components)
+    if ncomp not in (1, 3) or (ncomp == 1 and cin != 1):
+        raise ValueError(f"swnerf.images.encode_jpegs: components must be 3, or 1 for 1-channel input; got {components!r} for {cin} channel(s)")
+    if subsampling not in _SUBSAMPLING:
+        raise ValueError(f"swnerf.images.encode_jpegs: subsampling must be one of {', '.join(_SUBSAMPLING)}, got {subsampling!r}")
+    sampling = _lib.JPEG_444 if ncomp == 1 else getattr(_lib, _SUBSAMPLING[subsampling])
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"swnerf.images.encode_jpegs: frame size {H} x {W} outside 1..65535")
+    if n == 0:
+        return []
+    is_u8 = x.dtype in (np.uint8, torch.uint8)
+    qt = np.empty((2, 64), np.uint16)
+    _lib.check(L.swnerf_jpeg_quant_tables(int(quality), qt.ctypes.data), "jpeg_quant_tables")
+    ncoef = int(L.swnerf_jpeg_coef_count(H, W, ncomp, sampling))
+    bound = int(L.swnerf_jpeg_file_bound(H, W, ncomp, sampling))
+    per_in = H * W * cin * (1 if is_u8 else 4)
+    per_run = max(1, min(n, int(chunk_bytes) // max(per_in, 2 * ncoef)))
+    runs = [(s, min(n, s + per_run)) for s in range(0, n, per_run)]
+    two = 2 if len(runs) > 1 else 1
+    host_coef = [torch.empty((per_run, ncoef), dtype=torch.int16).pin_memory() for _ in range(two)]
+    staging = [torch.empty((per_run * per_in,), dtype=torch.uint8).pin_memory() for _ in range(two)] if on_host else None
+    done = [None] * two                                                  # the event after the copy into host_coef[k]
+    futures = [[] for _ in runs]
+    with torch.cuda.device(dev), ThreadPoolExecutor(max_workers=min(_JPEG_WORKERS, n)) as pool:
+        stream = torch.cuda.current_stream(dev)
+        qt_dev = torch.from_numpy(np.ascontiguousarray(qt[[0, 1, 1][:ncomp]]).view(np.int16)).to(dev)
+
+        def huffman(r):
+            """run r has been enqueued: wait for its coefficients and hand its frames to the pool"""
+            k = r % two
+            done[k].synchronize()
+            rows = host_coef[k].numpy()
+            futures[r] = [pool.submit(_jpeg_write_host, rows[i], qt, H, W, ncomp, sampling, bound) for i in range(runs[r][1] - runs[r][0])]
+
+        for r, (a, b) in enumerate(runs):
+            k = r % two
+            if r >= two:
+                for f in futures[r - two]:                               # host_coef[k] (and staging[k]) are free again
+                    f.result()
+            if on_host:
+                src = x[a:b].reshape(-1).view(np.uint8)
+                staging[k].numpy()[:src.shape[0]] = src
+                d = staging[k][:src.shape[0]].to(dev, non_blocking=True)
+            else:
+                d = x[a:b]
+            coef = torch.empty((b - a, ncoef), dtype=torch.int16, device=dev)
+            planes = torch.empty((b - a, ncoef), dtype=torch.uint8, device=dev)
+            _lib.check(L.swnerf_jpeg_encode(_lib.ptr(d), int(is_u8), b - a, H, W, cin, float(divisor) if divisor else 0.0, _lib.ptr(qt_dev),
+                                            ncomp, sampling, _lib.ptr(planes), _lib.ptr(coef), _lib.stream_of(coef)), "jpeg_encode")
+            host_coef[k][:b - a].copy_(coef, non_blocking=True)
+            done[k] = torch.cuda.Event()
+            done[k].record(stream)
+            if r:
+                huffman(r - 1)                                           # overlaps the device's work on run r
+        huffman(len(runs) - 1)
+        return [f.result() for fs in futures for f in fs]
+
+
+def encode_coefficients(frames, qt, subsampling="4:2:0", divisor=None, components=None):
+    """the device half of encode_jpegs alone: frames as encode_jpegs takes them, but on the device; qt: uint16 [2][64] natural
+    order (luma, chroma) -> int16 [N, coef_count] on the device, in the layout swnerf_jpeg_entropy produces"""
+    L = _lib.lib()
+    x, _ = _as_frames(frames)
+    x = _dev_tensor(x, "frames", (torch.uint8, torch.float32))
+    n, H, W, cin = (int(v) for v in x.shape)
+    ncomp = 3 if components is None else int(components)
+    sampling = _lib.JPEG_444 if ncomp == 1 else getattr(_lib, _SUBSAMPLING[subsampling])
+    ncoef = int(L.swnerf_jpeg_coef_count(H, W, ncomp, sampling))
+    qt = np.ascontiguousarray(np.asarray(qt, np.uint16).reshape(2, 64)[[0, 1, 1][:ncomp]])
+    with torch.cuda.device(x.device):
+        qt_dev = torch.from_numpy(qt.view(np.int16)).to(x.device)
+        coef = torch.empty((n, ncoef), dtype=torch.int16, device=x.device)
+        planes = torch.empty((n, ncoef), dtype=torch.uint8, device=x.device)
+        _lib.check(L.swnerf_jpeg_encode(_lib.ptr(x), int(x.dtype == torch.uint8), n, H, W, cin, float(divisor) if divisor else 0.0,
+                                        _lib.ptr(qt_dev), ncomp, sampling, _lib.ptr(planes), _lib.ptr(coef), _lib.stream_of(coef)), "jpeg_encode")
+    return coef
+
+
+def write_jpeg(path, img, quality=90, subsampling="4:2:0", divisor=None, components=None, device=None):
+    """one frame ([H,W,1|3|4] or [H,W]; a device tensor or a numpy array, uint8 or float32) as a baseline JPEG file - the lossy
+    sibling of png.write_png; the arguments are encode_jpegs'"""
+    x, single = _as_frames(img)
+    if not single:
+        raise ValueError(f"swnerf.images.write_jpeg: one frame [H,W,1|3|4] or [H,W], got {tuple(img.shape)}")
+    data = encode_jpegs(x, quality, subsampling, divisor, components, device)[0]
+    with open(path, "wb") as f:
+        f.write(data)

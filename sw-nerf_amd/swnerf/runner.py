@@ -18,7 +18,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import metrics, pyramid, render, render_dnerf, render_tnerf
+from . import metrics, pyramid, render, render_dnerf, render_tnerf, video
+from .video import mimwrite
 from .png import read_png, write_png
 from .checkpoint import reload_latest, find_checkpoints, load_multires, save_multires, to8b
 from .ray import get_rays
@@ -367,13 +368,14 @@ def render_path_multires(render_poses, render_times, hwf, chunk, render_kwargs_t
     return frames, per_level
 
 
-def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, render_factor=0, lpips_weights=None):
+def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, render_factor=0, lpips_weights=None, video=False):
     """nerf/run.py:557-596 (`--render_only --render_test`): render.render_path, then calculate_metrics(gt, pred) of every
     frame (pred clipped to [0, 1], data_range = gt.max() - gt.min(), skimage's PSNR and 7x7 SSIM), all frames in one
     batched GPU call.  Writes savedir/metrics.json = {"psnr": [...], "ssim": [...]} (indent 4) and returns (rgbs, metrics).
     lpips_weights (or render_kwargs['lpips_weights']): what metrics.LPIPS takes as `weights`; the file then also holds
-    "lpips": [...], the AlexNet LPIPS of every frame as the reference calls it.  Without it there is no such key.  The
-    reference's video.mp4 is not written."""
+    "lpips": [...], the AlexNet LPIPS of every frame as the reference calls it.  Without it there is no such key.  video=True
+    also writes the reference's video.mp4, as savedir/video.avi (swnerf.video.mimwrite: Motion-JPEG, quality 90, 30 fps); the
+    default leaves savedir with the frames and metrics.json alone."""
     os.makedirs(savedir, exist_ok=True)
     if lpips_weights is None and 'lpips_weights' in render_kwargs:
         lpips_weights = render_kwargs['lpips_weights']
@@ -381,6 +383,8 @@ def render_test(render_poses, hwf, K, chunk, render_kwargs, gt_imgs, savedir, re
         render_kwargs = {k: v for k, v in render_kwargs.items() if k != 'lpips_weights'}
     rgbs, _ = render.render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=gt_imgs, savedir=savedir,
                                  render_factor=render_factor)
+    if video:
+        mimwrite(os.path.join(savedir, 'video.mp4'), rgbs, fps=30, quality=8)
     gts = gt_imgs.cpu().numpy() if isinstance(gt_imgs, torch.Tensor) else np.asarray(gt_imgs)
     if lpips_weights is None:
         psnr, ssim = metrics.batch_metrics(gts, rgbs)
@@ -453,6 +457,30 @@ def _gt_rgb(images, idx, white_bkgd):
     if im.shape[-1] == 4:
         im = im[..., :3] * im[..., -1:] + (1. - im[..., -1:]) if white_bkgd else im[..., :3]
     return im
+
+
+def _render_poses_and_times(d, device, timed):
+    """what the video branch renders: data['render_poses'] on the device and, for the runners with frame times, data['render_times']
+    - linspace(0, 1, len(render_poses)) when the data carries none (the tuple form)"""
+    poses = torch.as_tensor(np.asarray(torch.as_tensor(d['render_poses']).cpu(), dtype=np.float32)).to(device)
+    if not timed:
+        return poses, None
+    times = d.get('render_times')
+    if times is None:
+        times = np.linspace(0., 1., poses.shape[0], dtype=np.float32)
+    return poses, np.asarray(torch.as_tensor(times).cpu(), dtype=np.float32)
+
+
+def _write_spiral(args, i, rgbs, disps, hooks):
+    """{expname}_spiral_{i:06d}_rgb.avi and ..._disp.avi (nerf/run.py:726-733; the reference's .mp4): to8b(rgbs) and
+    to8b(disps / np.max(disps)), both conversions on the device"""
+    moviebase = os.path.join(args.basedir, args.expname, '{}_spiral_{:06d}_'.format(args.expname, i))
+    os.makedirs(os.path.dirname(moviebase), exist_ok=True)
+    if hooks and 'on_video' in hooks:
+        hooks['on_video'](i, rgbs, disps)
+    video.write_video(moviebase + 'rgb.avi', np.asarray(rgbs, dtype=np.float32), fps=30, quality=90)
+    video.write_video(moviebase + 'disp.avi', np.asarray(disps, dtype=np.float32)[..., None], fps=30, quality=90, divisor=float(np.max(disps)))
+    print('Done, saving', rgbs.shape, disps.shape)
 
 
 class _Record:
@@ -558,13 +586,14 @@ def _curriculum_draw(args, s):
 
 
 def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset, extra_loss=None, first_iter=None, step_tail=None,
-                advance=True):
+                advance=True, render_video=None, i_video=50000):
     """Iterations s.start + 1 .. last_iter of the three runners (first_iter .. last_iter when given; step_tail: what follows
     optimizer.step() instead of _step_tail; advance=False: global_step stays at s.start; render_testset None: no test-set render -
     the private phase of train_multires).  What differs between the runners comes as callables:
     draw(i) -> (img_i, ray_batch, target, ids); render_batch(i, img_i, ray_batch) -> (rgb, rgb0 for loss_fn, state);
     extra_loss(state) -> a term added to loss_fn's loss before backward, or None for none; render_testset(i_test, poses_test, gt_imgs,
-    savedir) under no_grad every i_testset iterations.  -> the per-step record."""
+    savedir) under no_grad every i_testset iterations; render_video(i) -> (rgbs, disps) of the render poses under no_grad every
+    args.i_video (default i_video) iterations, written as two .avi files (_write_spiral); None: no video.  -> the per-step record."""
     hooks = hooks or {}
     i_test = np.asarray(d['i_split'][2]).reshape(-1) if len(d['i_split']) > 2 else np.zeros(0, np.int64)
     global_step = s.start
@@ -582,6 +611,10 @@ def _train_loop(args, d, s, last_iter, hooks, draw, render_batch, render_testset
         loss.backward()
         s.optimizer.step()
         step_tail(args, i, global_step, s.optimizer, record, loss, img_loss, s.train_kw, hooks)
+        if render_video is not None and i % _opt(args, 'i_video', i_video) == 0 and i > 0:
+            with torch.no_grad():
+                rgbs, disps = render_video(i)
+            _write_spiral(args, i, rgbs, disps, hooks)
         if render_testset is not None and i % _opt(args, 'i_testset', 50000) == 0 and i > 0 and i_test.size:
             testsavedir = os.path.join(args.basedir, args.expname, 'testset_{:06d}'.format(i))
             poses_test = torch.as_tensor(np.asarray(d['poses'], dtype=np.float32)[i_test]).to(s.device)
@@ -596,7 +629,9 @@ def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
     """The training loop of nerf/run.py:598-796 from `create_nerf` on: a batch from swnerf.batching.RayBatcher (use_batching
     over all training rays, or no_batching from one image with the precrop window), the render of the PACKED batch
     (render.batchify_rays + image_outputs, retraw=True), loss, backward, Adam, the lr decay, a checkpoint every i_weights, a
-    print every i_print, render_test every i_testset.  Video, TensorBoard and the config file are not written.
+    print every i_print, render_test every i_testset, the spiral of data['render_poses'] every i_video (default 50000) as
+    {expname}_spiral_{i:06d}_rgb.avi / _disp.avi (swnerf.video: Motion-JPEG where the reference writes .mp4).  TensorBoard and the
+    config file are not written.
 
     args: the reference's option names (N_rand, no_batching, precrop_iters, precrop_frac, chunk, lrate, lrate_decay, i_print,
     i_weights, i_testset, ...; N_iters - extra, default 200000 - is the last iteration; seed - extra, default 0 - keys the
@@ -604,7 +639,8 @@ def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
     sampler: "device" draws the pixels on the GPU with the keyed permutation; "numpy" draws np.random.choice(..., replace=False)
     on the host as the reference does and hands the indices to the same kernel - the reference's random stream and rays.
     loss_fn(rgb, target, rgb0) -> (loss, img_loss, img_loss0): default batching.photometric_loss.
-    hooks: {'on_batch': f(i, img_i, ray_batch, target, ids), 'on_step': f(i, optimizer)}.
+    hooks: {'on_batch': f(i, img_i, ray_batch, target, ids), 'on_step': f(i, optimizer), 'on_video': f(i, rgbs, disps) with the
+    float frames before they are encoded}.
     -> the per-step record: a list of {'step', 'loss', 'psnr', 'lr'}."""
     d = _train_data(data, False)
     s = _train_common(args, d, device, sampler, loss_fn, create_nerf, False)
@@ -622,7 +658,10 @@ def train(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
 
     def render_testset(i_test, poses_test, gt_imgs, savedir):
         render_test(poses_test, d['hwf'], d['K'], s.chunk, s.test_kw, gt_imgs, savedir)
-    return _train_loop(args, d, s, _opt(args, 'N_iters', 200000), hooks, draw, render_batch, render_testset)
+
+    def render_video(i):
+        return render.render_path(_render_poses_and_times(d, s.device, False)[0], d['hwf'], d['K'], s.chunk, s.test_kw)
+    return _train_loop(args, d, s, _opt(args, 'N_iters', 200000), hooks, draw, render_batch, render_testset, render_video=render_video)
 
 
 def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
@@ -630,6 +669,8 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     precrop_iters_time (:650-655), the frame time of the drawn image in column 8 of the batch (read from the device table by the
     batch kernel) and, with add_tv_loss, the TV loss of :690-725: a second render of the SAME rays on extras['z_vals'].detach()
     at a random time between the frame and its previous / next one.  use_batching raises NotImplementedError, as the reference.
+    Every i_video iterations (default 40000) the render poses at data['render_times'] (a dict's entry; linspace(0, 1, N) without
+    one) go to frames_{expname}_spiral_{i:06d}_time/ and to {expname}_spiral_{i:06d}_rgb.avi / _disp.avi (run_dnerf.py:820-829).
     data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  args.N_iter is the last iteration.
     hooks: those of `train`, and 'on_tv': f(i, which, ray_batch_other, z_vals) before each prev / next render."""
     d = _train_data(data, True)
@@ -639,9 +680,13 @@ def train_dnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
     return _dnerf_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks)
 
 
+def _spiral_frames_dir(args, i):
+    return os.path.join(args.basedir, args.expname, 'frames_{}_spiral_{:06d}_time/'.format(args.expname, i))
+
+
 def _dnerf_loop(args, d, s, last_iter, hooks, testset=True, **loop_kw):
     """The D-NeRF iterations on what _train_common prepared: train_dnerf, and each level of train_multires' private phase
-    (testset=False: no test-set render; loop_kw: _train_loop's first_iter, step_tail, advance)."""
+    (testset=False: no test-set render and no video; loop_kw: _train_loop's first_iter, step_tail, advance)."""
     times = s.batcher.times_host
     add_tv = bool(_opt(args, 'add_tv_loss', False))
 
@@ -684,15 +729,21 @@ def _dnerf_loop(args, d, s, last_iter, hooks, testset=True, **loop_kw):
     def render_testset(i_test, poses_test, gt_imgs, savedir):
         render_dnerf.render_path(poses_test, torch.as_tensor(times[i_test]).to(s.device), d['hwf'], s.chunk, s.test_kw,
                                  gt_imgs=gt_imgs, savedir=savedir)
+
+    def render_video(i):
+        poses, render_times = _render_poses_and_times(d, s.device, True)
+        return render_dnerf.render_path(poses, torch.as_tensor(render_times).to(s.device), d['hwf'], s.chunk, s.test_kw,
+                                        savedir=_spiral_frames_dir(args, i))
     return _train_loop(args, d, s, last_iter, hooks, _curriculum_draw(args, s), render_batch, render_testset if testset else None,
-                       tv_loss if add_tv else None, **loop_kw)
+                       tv_loss if add_tv else None, render_video=render_video if testset else None, i_video=40000, **loop_kw)
 
 
 def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=None):
     """The training loop of t_nerf/run_tnerf.py:596-800 from `create_nerf` on; as `train_dnerf` without the TV loss: the time
     curriculum precrop_iters_time (:646-651), a 12-column batch with the drawn image's frame time in column 8 (from the batcher's
     device table), render_tnerf.batchify_rays(..., retraw=True, fused_train=...), the single-net loss (rgb0 is None), Adam and
-    the lr decay, a checkpoint every i_weights (network_fine None), render_tnerf.render_path every i_testset.
+    the lr decay, a checkpoint every i_weights (network_fine None), render_tnerf.render_path every i_testset, the spiral frames and
+    the two .avi files of `train_dnerf` every i_video (default 40000; run_tnerf.py:775-784).
     args.N_iter is the last iteration; args.fused_train (extra, default True) = False keeps loss.backward() on the op path.
     use_batching raises NotImplementedError: the reference's branch (:631-642) builds rays without a frame time and cannot run.
     data: (images, poses, render_poses, hwf, i_split, times, near, far) or a dict.  hooks: those of `train`."""
@@ -710,8 +761,12 @@ def train_tnerf(args, data, device=None, sampler="device", loss_fn=None, hooks=N
 
     def render_testset(i_test, poses_test, gt_imgs, savedir):
         render_tnerf.render_path(poses_test, [float(t) for t in times[i_test]], d['hwf'], s.chunk, s.test_kw, gt_imgs=gt_imgs, savedir=savedir)
+
+    def render_video(i):
+        poses, render_times = _render_poses_and_times(d, s.device, True)
+        return render_tnerf.render_path(poses, [float(t) for t in render_times], d['hwf'], s.chunk, s.test_kw, savedir=_spiral_frames_dir(args, i))
     return _train_loop(args, d, s, _opt(args, 'N_iter', _opt(args, 'N_iters', 200000)), hooks, _curriculum_draw(args, s), render_batch,
-                       render_testset)
+                       render_testset, render_video=render_video, i_video=40000)
 
 
 # ---- train() of the MultiRes runner (multires_dnerf/multires_dnerf.py:612-1068) -----------------------------------------------
@@ -753,8 +808,10 @@ def train_multires(args, data, device=None, sampler="device", hooks=None, privat
     level's patch rendered by its nets, the fused loss (`multires_train_loss` with a PatchBatcher: two launches for data, loss and
     gradients), one backward(), every optimizer's step() and zero_grad(), each level's learning rate from its own step counter,
     `save_multires` every i_weights, `render_path_multires` of the test poses (every level at hwf, as the reference; no gt) every
-    i_testset, lines in log.txt every i_print.
-    Not written: video, TensorBoard, the i_img panels, args.txt / config.txt; do_half_precision is refused.
+    i_testset, lines in log.txt every i_print; every i_video iterations (default 40000) 120 frames of the first render pose at
+    times linspace(0, 1, 120), every level at hwf, reconstructed and written as {expname}_reconstructed_{i:06d}_rgb.avi
+    (multires_dnerf.py:1027-1045; the levels' frames go to frames_layer_{l}_{i:06d}_time/).
+    Not written: TensorBoard, the i_img panels, args.txt / config.txt; do_half_precision is refused.
 
     args: the reference's option names (layer_num, global_optimization_epoch, N_iter, N_rand, precrop_*, add_tv_loss, lrate,
     lrate_decay, i_print, i_weights, i_testset, ...; seed - extra, default 0; optimizer - extra, "torch" or "fused").
@@ -862,4 +919,16 @@ def train_multires(args, data, device=None, sampler="device", hooks=None, privat
                 render_path_multires(poses_dev[i_test], batcher.times[i_test], d['hwf'], _opt(args, 'chunk', 1024 * 32), tests,
                                      level_hwf="reference", savedir=testsavedir)
             print('Saved test set')
+        if i % _opt(args, 'i_video', 40000) == 0:
+            n = 120
+            pose0 = _render_poses_and_times(d, device, False)[0][:1].expand(n, -1, -1)
+            per_level = []
+            with torch.no_grad():
+                for layer, kw in enumerate(tests):
+                    rgbs, _ = render_dnerf.render_path(pose0, torch.linspace(0, 1, n).to(device), d['hwf'], _opt(args, 'chunk', 1024 * 32), kw,
+                                                       savedir=os.path.join(args.basedir, args.expname, f'frames_layer_{layer}_{i:06d}_time/'))
+                    per_level.append(torch.from_numpy(np.ascontiguousarray(rgbs, dtype=np.float32)).to(device))
+                frames = pyramid.reconstruct_image_from_pyramid_batch(per_level)
+            video.write_video(os.path.join(args.basedir, args.expname, f'{args.expname}_reconstructed_{i:06d}_rgb.avi'), frames, fps=30, quality=90)
+            print('Done, saving reconstructed video')
     return {'private': private, 'joint': joint}
