@@ -6,6 +6,8 @@ import subprocess
 import numpy as np
 import torch
 
+import wgrad_units_ref as WR
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 SRC = r'''
 #include "swnerf_common.h"
@@ -45,6 +47,8 @@ int main() {
     printf("%.6e ", w);
   }
   printf("\n%d %d\n", same, SW_SINCOS_F32_BANDS);
+  // the slot -> column table of the fused training pass's encodings for every band pair the kernels accept
+  for (int Lp = 0; Lp <= 10; ++Lp) for (int Ld = 0; Ld <= 4; ++Ld) { for (int f = 0; f < SW_XS_LD; ++f) printf("%d ", sw_xs_col(f, Lp, Ld)); printf("\n"); }
   return 0;
 }
 '''
@@ -97,6 +101,25 @@ def test_common_header_on_host(tmp_path):
         assert e < 1.2e-7, f"band {kb}: max |err| {e:.3e} (all bands: {band})"
     same, nf32 = (int(x) for x in lines[k + 7].split())
     assert same == 1 and nf32 == 10                                   # L_pos, L_time <= 10 in the fused kernels: their bits
+    # the plain-Python restatement of the slot maps (wgrad_units_ref: the yardstick of the unslot kernels' GPU tests) is the header's,
+    # entry for entry: sw_pos_col / sw_dir_col / sw_time_col for every L, and sw_xs_col for every (L_pos, L_dir) in 0..10 x 0..4
+    ints = lambda ln: [int(c) for c in ln.split()]
+    for L in range(11):
+        assert ints(lines[7 + L]) == [WR.pos_col(a, h, L) for a in range(32) for h in range(2)], L
+        assert ints(lines[23 + L]) == [WR.time_col(a, h, L) for a in range(16) for h in range(2)], L
+    for L in range(5):
+        assert ints(lines[18 + L]) == [WR.dir_col(a, h, L) for a in range(16) for h in range(2)], L
+    table = lines[k + 8:]
+    assert len(table) == 55
+    for ln, (Lp, Ld) in zip(table, ((Lp, Ld) for Lp in range(11) for Ld in range(5))):
+        cols = ints(ln)
+        assert cols == [WR.xs_col(f, Lp, Ld) for f in range(WR.XS_LD)], (Lp, Ld)
+        assert sorted(c for c in cols[:64] if c >= 0) == list(range(3 * (1 + 2 * Lp)))
+        assert sorted(c for c in cols[64:] if c >= 0) == list(range(3 * (1 + 2 * Ld)))
+    # the gamma(t) k-tile shares the slot decoding (g, h, e) of sw_xs_col: unslot_time_kernel's map, every L_time
+    for Lt in range(11):
+        cols = [WR.time_slot_col(f, Lt) for f in range(32)]
+        assert sorted(c for c in cols if c >= 0) == list(range(1 + 2 * Lt))
 
 
 def test_embed_kernel_multiply_shift_divisions_are_exact():
