@@ -347,8 +347,7 @@ extern "C" int swnerf_pack_net(int kind, const float* const* params, int L_pos, 
         return pack_tnerf(params, L_pos, L_dir, L_time, packed, (hipStream_t)stream);
     }
     if (kind != SWNERF_NET_CANON && kind != SWNERF_NET_DNERF) return sw_fail(SWNERF_E_ARG, "pack_net: unknown kind %d", kind);
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4 || L_time < 0 || L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "pack_net: embedder bands (%d,%d,%d) exceed (10,4,10)", L_pos, L_dir, L_time);
+    if (int rc = sw_check_bands("pack_net", 3, L_pos, L_dir, L_time)) return rc;
     const int np = kind == SWNERF_NET_CANON ? 24 : 42;
     for (int i = 0; i < np; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net: params[%d] is NULL", i);
     const int Cpos = 3 * (1 + 2 * L_pos), Cdir = 3 * (1 + 2 * L_dir), Ctime = 1 + 2 * L_time;
@@ -416,7 +415,7 @@ int sw_pack_canon_bias_x3(const float* const* params, const float* fold, float* 
 // use_viewdirs=False (model.py:59-60): the trunk alone; output_linear's rows ride as bias-style tiles like the other heads.
 extern "C" int swnerf_pack_net_noview(const float* const* params, int L_pos, int out_ch, float* packed, void* stream) {
     if (!params || !packed) return sw_fail(SWNERF_E_ARG, "pack_net_noview: NULL pointer");
-    if (L_pos < 0 || L_pos > 10) return sw_fail(SWNERF_E_UNSUPP, "pack_net_noview: %d position bands exceed 10", L_pos);
+    if (int rc = sw_check_bands("pack_net_noview", 1, L_pos)) return rc;
     if (out_ch < 4 || out_ch > SW_NOVIEW_MAX_OUT)
         return sw_fail(SWNERF_E_UNSUPP, "pack_net_noview: output_ch %d (the reference builds 4 or 5, nerf/run.py:231)", out_ch);
     for (int i = 0; i < 18; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net_noview: params[%d] is NULL", i);
@@ -445,7 +444,7 @@ extern "C" int swnerf_pack_net_bwd_kind(int bwd_kind, const float* const* params
     if (!params || !packed_bwd) return sw_fail(SWNERF_E_ARG, "pack_net_bwd: NULL pointer");
     if (bwd_kind != SWNERF_BWD_CANON && bwd_kind != SWNERF_BWD_CANON_INPUT_GRAD && bwd_kind != SWNERF_BWD_DEFORM && bwd_kind != SWNERF_BWD_DNERF_FUSED)
         return sw_fail(SWNERF_E_ARG, "pack_net_bwd: unknown stream kind %d", bwd_kind);
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4) return sw_fail(SWNERF_E_UNSUPP, "pack_net_bwd: embedder bands (%d,%d) exceed (10,4)", L_pos, L_dir);
+    if (int rc = sw_check_bands("pack_net_bwd", 2, L_pos, L_dir)) return rc;
     const int np = bwd_kind == SWNERF_BWD_DEFORM ? 18 : (bwd_kind == SWNERF_BWD_DNERF_FUSED ? 42 : 24);
     for (int i = 0; i < np; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net_bwd: params[%d] is NULL", i);
     const int Cpos = 3 * (1 + 2 * L_pos), Cdir = 3 * (1 + 2 * L_dir);
@@ -495,7 +494,7 @@ extern "C" int swnerf_pack_net_bwd_kind(int bwd_kind, const float* const* params
 extern "C" size_t swnerf_packed_bwd_noview_floats(void) { return (size_t)SW_NVBWD_FLOATS; }
 extern "C" int swnerf_pack_net_bwd_noview(const float* const* params, int L_pos, int out_ch, float* packed_bwd, void* stream) {
     if (!params || !packed_bwd) return sw_fail(SWNERF_E_ARG, "pack_net_bwd_noview: NULL pointer");
-    if (L_pos < 0 || L_pos > 10) return sw_fail(SWNERF_E_UNSUPP, "pack_net_bwd_noview: %d position bands exceed 10", L_pos);
+    if (int rc = sw_check_bands("pack_net_bwd_noview", 1, L_pos)) return rc;
     if (out_ch < 4 || out_ch > SW_NOVIEW_MAX_OUT) return sw_fail(SWNERF_E_UNSUPP, "pack_net_bwd_noview: output_ch %d (4 or 5)", out_ch);
     for (int i = 0; i < 18; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net_bwd_noview: params[%d] is NULL", i);
     const int Cpos = 3 * (1 + 2 * L_pos);

@@ -26,57 +26,34 @@ struct QueryTimeDev {
 
 __global__ void __launch_bounds__(256, 1) query_points_dnerf_kernel(QueryTimeDev P) {
     extern __shared__ __attribute__((aligned(16))) float lds_bias[];
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* lds_ring = lds_bias + SW_LDS_BIAS_FLOATS + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    float* lds_tb = lds_bias + P.tb_off + wv * SW_TB_LDS_FLOATS;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_bias, P.b0, P.nbias);
-    if (tile * 32 >= P.M) return;
-    const int64_t row = tile * 32 + j;
-    const bool live = row < P.M;
-    const int64_t rr = live ? row : P.M - 1;
-    const float x0 = P.pts[rr * 3], x1 = P.pts[rr * 3 + 1], x2 = P.pts[rr * 3 + 2];
+    RowTile rt;
+    if (!row_tile(rt, lds_bias, P.b0, P.nbias, P.M)) return;
+    const int h = rt.h;
+    float* lds_tb = lds_bias + P.tb_off + rt.wv * SW_TB_LDS_FLOATS;
+    const float x0 = P.pts[rt.rr * 3], x1 = P.pts[rt.rr * 3 + 1], x2 = P.pts[rt.rr * 3 + 2];
     f32x16 emb[2], in[8], out[8];
     float head[3];
     pe_pos(x0, x1, x2, h, emb);
     WStream ws;
     // directions vary per loop turn: skip the stream's per-ray DIR prefix (and its b_vf tiles), as mlp_forward_kernel does
-    ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, lds_ring, lane);
+    ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, rt.lds_ring, rt.lane);
     // the stream's TIME segment, once per wave: _time.0.bias + its gamma(t) columns (mlp_core.h)
-    if (P.two_pass) time_bias_tile(P.ft, h, lds_tb, lane, ws);
+    if (P.two_pass) time_bias_tile(P.ft, h, lds_tb, rt.lane, ws);
     float ex = 0.f, ey = 0.f, ez = 0.f;                       // run_deform == 0: dx = 0 (model.py:143-145)
 #pragma nounroll
     for (int pass = P.two_pass ? 0 : 1; pass < 2; ++pass) {
-        trunk_pass<true, false, false, false, true>(emb, lds_emb, P.ft, pass == 0, h, in, out, head, ws, nullptr, nullptr, false, nullptr, nullptr, lds_tb);
+        trunk_pass<true, false, false, false, true>(emb, rt.lds_emb, P.ft, pass == 0, h, in, out, head, ws, nullptr, nullptr, false, nullptr, nullptr, lds_tb);
         if (pass == 0) {
             ex = head[0]; ey = head[1]; ez = head[2];
             pe_pos(x0 + ex, x1 + ey, x2 + ez, h, emb);        // embed_fn(input_pts_orig + dx) (model.py:148-149)
         }
     }
-    const float* hb_rgb = ws.bias - SW_BIAS_TILE_FLOATS;      // [b_alpha, b_r, b_g, b_b]
-    const float* rgb_tiles = ws.bias;                         // rgb_linear.weight as bias-style tiles: re-read on every turn
-    ws_restart(ws, P.wvl);
-    float sr = 0.f, sg = 0.f, sb = 0.f;
-    const int64_t nv = P.shared ? P.V : 1;
-#pragma nounroll
-    for (int64_t v = 0; v < nv; ++v) {
-        const float* dp = P.dirs + (P.shared ? v : rr) * 3;
-        f32x16 demb, hv[4];
-        pe_dir(dp[0], dp[1], dp[2], h, demb);
-        ws.bias = rgb_tiles;
-        ws.base = reinterpret_cast<const char*>(P.wvl);
-        canon_tail_rows(in, demb, hv, lds_bias + h * 16, ws);
-        float c3[3];
-        head_valu<3, 4>(hv, ws, c3);
-        sr += c3[0] + hb_rgb[1]; sg += c3[1] + hb_rgb[2]; sb += c3[2] + hb_rgb[3];
-    }
-    if (live && h == 0) {
-        const float inv = 1.f / (float)nv;
-        f32x4 r4 = {sr * inv, sg * inv, sb * inv, head[0]};
-        *reinterpret_cast<f32x4*>(P.out + row * 4) = r4;
-        if (P.dx) { P.dx[row * 3 + 0] = ex; P.dx[row * 3 + 1] = ey; P.dx[row * 3 + 2] = ez; }
+    float rgb[3];
+    views_mean(in, ws, P.wvl, P.dirs, P.V, P.shared, rt.rr, h, lds_bias, rgb);
+    if (rt.live && h == 0) {
+        f32x4 r4 = {rgb[0], rgb[1], rgb[2], head[0]};
+        *reinterpret_cast<f32x4*>(P.out + rt.row * 4) = r4;
+        if (P.dx) { P.dx[rt.row * 3 + 0] = ex; P.dx[rt.row * 3 + 1] = ey; P.dx[rt.row * 3 + 2] = ez; }
     }
 }
 
@@ -90,8 +67,7 @@ extern "C" int swnerf_query_points_time(int kind, const float* packed, const flo
         return sw_fail(SWNERF_E_ARG, "query_points_time: net kind %d has no frame time (SWNERF_NET_DNERF or SWNERF_NET_TNERF)", kind);
     if (M == 0 && packed) return 0;
     if (!packed || !pts || !dirs || !out || M < 0) return sw_fail(SWNERF_E_ARG, "query_points_time: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4 || L_time < 0 || L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "query_points_time: embedder bands (%d,%d,%d) exceed (10,4,10)", L_pos, L_dir, L_time);
+    if (int rc = sw_check_bands("query_points_time", 3, L_pos, L_dir, L_time)) return rc;
     if (shared_dirs ? n_dirs < 1 : n_dirs != M)
         return sw_fail(SWNERF_E_ARG, "query_points_time: need %s directions, got %lld for %lld points", shared_dirs ? ">= 1 shared" : "one per point", (long long)n_dirs, (long long)M);
     hipStream_t st = (hipStream_t)stream;
@@ -110,7 +86,5 @@ extern "C" int swnerf_query_points_time(int kind, const float* packed, const flo
     size_t lds = SW_LDS_FIXED_FLOATS * sizeof(float);
     P.tb_off = (int)(lds / sizeof(float));
     if (P.two_pass) lds += 4 * SW_TB_LDS_FLOATS * sizeof(float);             // the four waves' TIME tiles, behind everything else
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(query_points_dnerf_kernel, grid, block, lds, st, P);
-    return sw_check(hipGetLastError(), "query_points_time launch");
+    return sw_launch_rows(query_points_dnerf_kernel, P, M, lds, st, "query_points_time launch");
 }

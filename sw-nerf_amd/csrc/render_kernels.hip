@@ -27,46 +27,20 @@ struct QueryDev {
 
 __global__ void __launch_bounds__(256, 1) query_points_kernel(QueryDev P) {
     extern __shared__ __attribute__((aligned(16))) float lds_bias[];
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* lds_ring = lds_bias + SW_LDS_BIAS_FLOATS + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_bias, P.b0, P.nbias);
-    if (tile * 32 >= P.M) return;
-    const int64_t row = tile * 32 + j;
-    const bool live = row < P.M;
-    const int64_t rr = live ? row : P.M - 1;
+    RowTile rt;
+    if (!row_tile(rt, lds_bias, P.b0, P.nbias, P.M)) return;
     f32x16 emb[2], in[8], out[8];
     float head[3];
-    pe_pos(P.pts[rr * 3], P.pts[rr * 3 + 1], P.pts[rr * 3 + 2], h, emb);
+    pe_pos(P.pts[rt.rr * 3], P.pts[rt.rr * 3 + 1], P.pts[rt.rr * 3 + 2], rt.h, emb);
     WStream ws;
     // directions vary per point / per loop turn: skip the stream's per-ray DIR prefix (and its b_vf tiles)
-    ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, lds_ring, lane);
-    trunk_pass<false>(emb, lds_emb, 0.f, false, h, in, out, head, ws);
-    const float* hb_rgb = ws.bias - SW_BIAS_TILE_FLOATS;      // [b_alpha, b_r, b_g, b_b]
-    const float* rgb_tiles = ws.bias;                         // rgb_linear.weight as bias-style tiles: re-read on every turn
-    // feature_linear is folded into the view layer (swnerf_common.h SW_CANON_STEPS): the loop below runs the 4 x 9 segment on
-    // [gamma(d) | h7] from the views-loop stream, whose tail is its own head.
-    ws_restart(ws, P.wvl);
-    float sr = 0.f, sg = 0.f, sb = 0.f;
-    const int64_t nv = P.shared ? P.V : 1;
-#pragma nounroll
-    for (int64_t v = 0; v < nv; ++v) {
-        const float* dp = P.dirs + (P.shared ? v : rr) * 3;
-        f32x16 demb, hv[4];
-        pe_dir(dp[0], dp[1], dp[2], h, demb);
-        ws.bias = rgb_tiles;
-        ws.base = reinterpret_cast<const char*>(P.wvl);
-        canon_tail_rows(in, demb, hv, lds_bias + h * 16, ws);
-        float c3[3];
-        head_valu<3, 4>(hv, ws, c3);
-        sr += c3[0] + hb_rgb[1]; sg += c3[1] + hb_rgb[2]; sb += c3[2] + hb_rgb[3];
-    }
-    if (live && h == 0) {
-        const float inv = 1.f / (float)nv;
-        f32x4 r4 = {sr * inv, sg * inv, sb * inv, head[0]};
-        *reinterpret_cast<f32x4*>(P.out + row * 4) = r4;
+    ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, rt.lds_ring, rt.lane);
+    trunk_pass<false>(emb, rt.lds_emb, 0.f, false, rt.h, in, out, head, ws);
+    float rgb[3];
+    views_mean(in, ws, P.wvl, P.dirs, P.V, P.shared, rt.rr, rt.h, lds_bias, rgb);
+    if (rt.live && rt.h == 0) {
+        f32x4 r4 = {rgb[0], rgb[1], rgb[2], head[0]};
+        *reinterpret_cast<f32x4*>(P.out + rt.row * 4) = r4;
     }
 }
 
@@ -148,24 +122,21 @@ extern "C" int swnerf_query_points(const float* packed, const float* pts, int64_
                                    int shared_dirs, int L_pos, int L_dir, float* out, void* stream) {
     if (M == 0 && packed) return 0;
     if (!packed || !pts || !dirs || !out || M < 0) return sw_fail(SWNERF_E_ARG, "query_points: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4) return sw_fail(SWNERF_E_UNSUPP, "query_points: embedder bands (%d,%d) exceed (10,4)", L_pos, L_dir);
+    if (int rc = sw_check_bands("query_points", 2, L_pos, L_dir)) return rc;
     if (shared_dirs ? n_dirs < 1 : n_dirs != M)
         return sw_fail(SWNERF_E_ARG, "query_points: need %s directions, got %lld for %lld points", shared_dirs ? ">= 1 shared" : "one per point", (long long)n_dirs, (long long)M);
     QueryDev P;
     P.pts = pts; P.M = M; P.dirs = dirs; P.V = n_dirs; P.shared = shared_dirs ? 1 : 0; P.out = out;
     P.w0 = packed; P.b0 = packed + SW_CANON_W_FLOATS; P.nbias = SW_CANON_BIAS_TILES * SW_BIAS_TILE_FLOATS;
     P.wvl = packed + SW_CANON_VL_OFFSET;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(query_points_kernel, grid, block, SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "query_points launch");
+    return sw_launch_rows(query_points_kernel, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "query_points launch");
 }
 
 extern "C" int swnerf_mlp_forward(int kind, const float* packed, const float* x, int64_t M, int L_pos, int L_dir,
                                   const float* t_emb, int L_time, int run_deform, float* out, float* dx_out, void* stream) {
     if (M == 0 && packed) return 0;
     if (!packed || !x || !out || M < 0) return sw_fail(SWNERF_E_ARG, "mlp_forward: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4 || L_time < 0 || L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "mlp_forward: embedder bands (%d,%d,%d) exceed (10,4,10)", L_pos, L_dir, L_time);
+    if (int rc = sw_check_bands("mlp_forward", 3, L_pos, L_dir, L_time)) return rc;
     if (kind == SWNERF_NET_DNERF && run_deform && !t_emb) return sw_fail(SWNERF_E_ARG, "mlp_forward: D-NeRF deformation needs t_emb");
     MlpDev P;
     P.x = x; P.M = M; P.Lp = L_pos; P.Ld = L_dir; P.Lt = L_time;
@@ -175,12 +146,8 @@ extern "C" int swnerf_mlp_forward(int kind, const float* packed, const float* x,
     int rc = stream_ptrs(kind, packed, run_deform, &P.w0, &P.b0, &P.nbias, &P.two_pass);
     if (rc) return rc;
     P.wvl = views_loop_ptr(kind, packed);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    const size_t lds = SW_LDS_FIXED_FLOATS * sizeof(float);
-    if (kind == SWNERF_NET_DNERF) hipLaunchKernelGGL(mlp_forward_kernel<true>, grid, block, lds, st, P);
-    else hipLaunchKernelGGL(mlp_forward_kernel<false>, grid, block, lds, st, P);
-    return sw_check(hipGetLastError(), "mlp_forward launch");
+    return sw_launch_rows(kind == SWNERF_NET_DNERF ? mlp_forward_kernel<true> : mlp_forward_kernel<false>, P, M,
+                          SW_LDS_FIXED_FLOATS * sizeof(float), stream, "mlp_forward launch");
 }
 
 // model.forward(x) for the net WITHOUT view directions (SWNERF_NET_NOVIEW; model.py:39-47, 59-60): x [M, C_pos] (any
@@ -188,31 +155,19 @@ extern "C" int swnerf_mlp_forward(int kind, const float* packed, const float* x,
 struct MlpNoviewDev { const float* x; int64_t M; int C; int Lp; const float* w0; const float* b0; int nbias; int out_ch; float* out; };
 
 __global__ void __launch_bounds__(256, 1) mlp_forward_noview_kernel(MlpNoviewDev P) {
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     extern __shared__ __attribute__((aligned(16))) float lds_bias[];
-    float* lds_ring = lds_bias + SW_LDS_BIAS_FLOATS + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_bias, P.b0, P.nbias);
-    if (tile * 32 >= P.M) return;
-    const int64_t row = tile * 32 + j;
-    const bool live = row < P.M;
-    const float* xr = P.x + (live ? row : P.M - 1) * P.C;
+    RowTile rt;
+    if (!row_tile(rt, lds_bias, P.b0, P.nbias, P.M)) return;
     f32x16 emb[2], in[8], out[8];
     float head[3];
-#pragma unroll
-    for (int a = 0; a < 32; ++a) {
-        const int col = sw_pos_col(a, h, P.Lp);
-        emb[a >> 4][a & 15] = (col >= 0) ? xr[col] : 0.f;
-    }
+    gather_pos(P.x + rt.rr * P.C, rt.h, P.Lp, emb);
     WStream ws;
-    ws_start(ws, P.w0, lds_bias, lds_ring, lane);
-    trunk_pass<false, false, false, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws);
+    ws_start(ws, P.w0, lds_bias, rt.lds_ring, rt.lane);
+    trunk_pass<false, false, false, true>(emb, rt.lds_emb, 0.f, false, rt.h, in, out, head, ws);
     float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     head_valu_rt<8>(in, ws, P.out_ch, o5);
-    if (live && h == 0) {
-        float* o = P.out + row * P.out_ch;
+    if (rt.live && rt.h == 0) {
+        float* o = P.out + rt.row * P.out_ch;
         o[0] = o5[0] + ws.bias[0]; o[1] = o5[1] + ws.bias[1]; o[2] = o5[2] + ws.bias[2]; o[3] = o5[3] + ws.bias[3];
         if (P.out_ch == 5) o[4] = o5[4] + ws.bias[4];
     }
@@ -222,13 +177,12 @@ __global__ void __launch_bounds__(256, 1) mlp_forward_noview_kernel(MlpNoviewDev
 extern "C" int swnerf_mlp_forward_noview(const float* packed, const float* x, int64_t M, int ldx, int L_pos, int out_ch, float* out, void* stream) {
     if (M == 0 && packed) return 0;
     if (!packed || !x || !out || M < 0) return sw_fail(SWNERF_E_ARG, "mlp_forward_noview: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10) return sw_fail(SWNERF_E_UNSUPP, "mlp_forward_noview: %d position bands exceed 10", L_pos);
+    if (int rc = sw_check_bands("mlp_forward_noview", 1, L_pos)) return rc;
     if (ldx < 3 * (1 + 2 * L_pos)) return sw_fail(SWNERF_E_ARG, "mlp_forward_noview: rows of %d floats cannot hold %d embedded columns", ldx, 3 * (1 + 2 * L_pos));
     MlpNoviewDev P;
     P.x = x; P.M = M; P.C = ldx; P.Lp = L_pos; P.out_ch = out_ch; P.out = out;
     int two = 0;
     int rc = stream_ptrs_noview(packed, out_ch, &P.w0, &P.b0, &P.nbias, &two);
     if (rc) return rc;
-    hipLaunchKernelGGL(mlp_forward_noview_kernel, dim3((unsigned)((M + 127) / 128)), dim3(256), SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "mlp_forward_noview launch");
+    return sw_launch_rows(mlp_forward_noview_kernel, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "mlp_forward_noview launch");
 }

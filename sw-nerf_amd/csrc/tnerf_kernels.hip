@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_query_kernel(
     float* lds_t0 = lds_emb + 2 * 16 * 64;
     float* lds_t5 = lds_t0 + 4 * SW_BIAS_TILE_FLOATS;
     float* lds_vb = lds_t5 + 4 * SW_BIAS_TILE_FLOATS;
-    bias_to_lds(lds_all, P.b0, P.nbias);         // the only block barrier
+    bias_to_lds(lds_all, P.b0, P.nbias);         // the only block barrier (its own SW_TN_* LDS layout: not mlp_kernels.h row_tile)
     if (tile * 32 >= P.M) return;                // wave-uniform
     const int64_t row = tile * 32 + j;
     const bool live = row < P.M;
@@ -137,7 +137,5 @@ int sw_tnerf_query_launch(const float* packed, const float* pts, int64_t M, cons
     TnQueryDev P;
     P.pts = pts; P.M = M; P.dirs = dirs; P.V = n_dirs; P.ft = ft; P.out = out;
     P.w0 = packed; P.b0 = packed + SW_TN_W_FLOATS; P.nbias = SW_TN_BIAS_TILES * SW_BIAS_TILE_FLOATS;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(tnerf_query_kernel, grid, block, SW_TN_LDS_FLOATS * sizeof(float), st, P);
-    return sw_check(hipGetLastError(), "query_points_time (T-NeRF) launch");
+    return sw_launch_rows(tnerf_query_kernel, P, M, SW_TN_LDS_FLOATS * sizeof(float), st, "query_points_time (T-NeRF) launch");
 }

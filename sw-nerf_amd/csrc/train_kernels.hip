@@ -37,6 +37,27 @@ __device__ __forceinline__ f32x4 mask_take(const MaskRing& mr) {
     return v;
 }
 
+// out = sum_c w_c . d_c (ACC: added to out): NC weight rows of 256 riding as bias-style tiles, tile n of channel c at
+// wt + (c * 8 + n) tiles, as [h][r]; wt already points at the lane half's 16 floats.  Summed left to right.
+template <int NC, bool ACC = false>
+__device__ __forceinline__ void wrows_valu(const float* wt, const float (&d)[NC], f32x16 (&out)[8]) {
+#pragma unroll
+    for (int n = 0; n < 8; ++n)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 w[NC];
+#pragma unroll
+            for (int c = 0; c < NC; ++c) w[c] = *reinterpret_cast<const f32x4*>(wt + (c * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float s = ACC ? out[n][4 * g + e] + w[0][e] * d[0] : w[0][e] * d[0];
+#pragma unroll
+                for (int c = 1; c < NC; ++c) s += w[c][e] * d[c];
+                out[n][4 * g + e] = s;
+            }
+        }
+}
+
 struct DxDev {
     const float* w0; const float* b0;      // backward stream; its 8 "bias" tiles = alpha_linear.weight
     const float* bits; const float* d_out; // [ceil(M/32), SW_MASK_TILE_FLOATS], [M,4]
@@ -49,24 +70,18 @@ struct DxDev {
 template <bool INGRAD>
 __global__ void __launch_bounds__(256, 1) mlp_backward_dx_kernel(DxDev P) {
     extern __shared__ __attribute__((aligned(16))) float lds_bias[];
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* lds_ring = lds_bias + SW_LDS_BIAS_FLOATS + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_bias, P.b0, SW_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS);
-    if (tile * 32 >= P.M) return;
-    const int64_t row = tile * 32 + j;
-    const bool live = row < P.M;
-    const int64_t rr = live ? row : P.M - 1;
+    RowTile rt;
+    if (!row_tile(rt, lds_bias, P.b0, SW_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS, P.M)) return;
+    const int lane = rt.lane, h = rt.h;
+    const int64_t rr = rt.rr;
     const f32x4 dr = *reinterpret_cast<const f32x4*>(P.d_out + rr * 4);     // d rgb(3), d sigma
     float* grad_row = P.grad + rr * SW_ACT_LD + 4 * h;
     const f32x4 nomask = {0.f, 0.f, 0.f, 0.f};
     MaskRing mr;
-    mask_start(mr, P.bits, tile, lds_emb + 2 * 16 * 64, lane);
+    mask_start(mr, P.bits, rt.tile, rt.lds_emb + 2 * 16 * 64, lane);
     mask_fetch(mr, 8);                                                   // views hidden; older than every weight step
     WStream ws;
-    ws_start(ws, P.w0, lds_bias, lds_ring, lane);
+    ws_start(ws, P.w0, lds_bias, rt.lds_ring, lane);
     // d hv = rgb_linear.weight^T . d rgb, masked by hv > 0           (4 tiles <- 1 k-tile holding 3 channels)
     f32x16 k1[1];
 #pragma unroll
@@ -90,7 +105,7 @@ __global__ void __launch_bounds__(256, 1) mlp_backward_dx_kernel(DxDev P) {
         if (INGRAD && l == 5) {                                          // the skip input cat[gamma(x), h4]: its gamma(x) part
             f32x16 ge[2];
             seg_mfma<2, 8, SEG_ZERO>(ge, in, ws);
-            emb_park(lds_emb, lane, ge);
+            emb_park(rt.lds_emb, lane, ge);
         }
         seg_mfma<8, 8, SEG_ZERO, 8>(out, in, ws, 1.f, SideStore{grad_row + 256 * l, nullptr, nomask});
     }
@@ -101,9 +116,10 @@ __global__ void __launch_bounds__(256, 1) mlp_backward_dx_kernel(DxDev P) {
         tiles_store<8>(grad_row, in);
     } else {
         f32x16 ge[2];
-        emb_fetch(lds_emb, lane, ge);
+        emb_fetch(rt.lds_emb, lane, ge);
         seg_mfma<2, 8, SEG_ACC, 8>(ge, in, ws, 1.f, SideStore{grad_row, nullptr, nomask});
         // slot a of lane half h holds sin (h=0) / cos (h=1) of 2^k x_c, a = 3k + c < 30; slots 30, 31 hold x itself
+        // (in line here and in render_pass_backward_kernel<1> ON PURPOSE: as one __forceinline__ function this kernel came out +27 instructions / -1 s_waitcnt, the fused one +96 / +44 or, with reference results, 312 -> 316 registers)
         const float x0 = P.pts[rr * 3], x1 = P.pts[rr * 3 + 1], x2 = P.pts[rr * 3 + 2];
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
 #pragma unroll
@@ -118,7 +134,7 @@ __global__ void __launch_bounds__(256, 1) mlp_backward_dx_kernel(DxDev P) {
         }
         if (h == 0) { g0 += ge[1][14]; g1 += ge[1][15]; } else { g2 += ge[1][14]; }
         g0 += __shfl_xor(g0, 32, 64); g1 += __shfl_xor(g1, 32, 64); g2 += __shfl_xor(g2, 32, 64);
-        if (live && h == 0) { P.d_pts[row * 3] = g0; P.d_pts[row * 3 + 1] = g1; P.d_pts[row * 3 + 2] = g2; }
+        if (rt.live && h == 0) { P.d_pts[rt.row * 3] = g0; P.d_pts[rt.row * 3 + 1] = g1; P.d_pts[rt.row * 3 + 2] = g2; }
     }
 }
 
@@ -131,31 +147,18 @@ struct DeformDev {
 };
 
 __global__ void __launch_bounds__(256, 1) deform_forward_train_kernel(DeformDev P) {
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     extern __shared__ __attribute__((aligned(16))) float lds_bias[];
-    float* lds_ring = lds_bias + SW_LDS_BIAS_FLOATS + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_bias, P.b0, P.nbias);
-    if (tile * 32 >= P.M) return;
-    const int64_t row = tile * 32 + j;
-    const bool live = row < P.M;
-    const int64_t rr = live ? row : P.M - 1;
-    const float* xr = P.x + rr * P.C;
+    RowTile rt;
+    if (!row_tile(rt, lds_bias, P.b0, P.nbias, P.M)) return;
     f32x16 emb[2], in[8], out[8];
     float head[3];
-#pragma unroll
-    for (int a = 0; a < 32; ++a) {
-        const int col = sw_pos_col(a, h, P.Lp);
-        emb[a >> 4][a & 15] = (col >= 0) ? xr[col] : 0.f;
-    }
-    const float ft = P.t_emb[rr * P.Ct];                                  // column 0 of gamma(t) is t
+    gather_pos(P.x + rt.rr * P.C, rt.h, P.Lp, emb);
+    const float ft = P.t_emb[rt.rr * P.Ct];                                // column 0 of gamma(t) is t
     WStream ws;
-    ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, lds_ring, lane);   // (behind the per-ray DIR prefix)
-    trunk_pass<true, true>(emb, lds_emb, ft, true, h, in, out, head, ws, P.act + rr * SW_ACT_LD + 4 * h,
-                           P.bits + tile * SW_MASK_TILE_FLOATS + lane * 4, true, nullptr);
-    if (live && h == 0) { P.dx[row * 3] = head[0]; P.dx[row * 3 + 1] = head[1]; P.dx[row * 3 + 2] = head[2]; }
+    ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, rt.lds_ring, rt.lane);   // (behind the per-ray DIR prefix)
+    trunk_pass<true, true>(emb, rt.lds_emb, ft, true, rt.h, in, out, head, ws, P.act + rt.rr * SW_ACT_LD + 4 * rt.h,
+                           P.bits + rt.tile * SW_MASK_TILE_FLOATS + rt.lane * 4, true, nullptr);
+    if (rt.live && rt.h == 0) { P.dx[rt.row * 3] = head[0]; P.dx[rt.row * 3 + 1] = head[1]; P.dx[rt.row * 3 + 2] = head[2]; }
 }
 
 // dX chain of the deformation net: d h7 = _time_out.weight^T . d dx, then _time.7 .. _time.1 (model.py:128-136 reversed)
@@ -167,35 +170,20 @@ struct DeformBwdDev {
 
 __global__ void __launch_bounds__(256, 1) deform_backward_dx_kernel(DeformBwdDev P) {
     extern __shared__ __attribute__((aligned(16))) float lds_bias[];
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* lds_ring = lds_bias + SW_LDS_BIAS_FLOATS + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_bias, P.b0, SW_DBWD_BIAS_TILES * SW_BIAS_TILE_FLOATS);
-    if (tile * 32 >= P.M) return;
-    const int64_t row = tile * 32 + j;
-    const bool live = row < P.M;
-    const int64_t rr = live ? row : P.M - 1;
-    const float d0 = P.d_dx[rr * 3], d1 = P.d_dx[rr * 3 + 1], d2 = P.d_dx[rr * 3 + 2];
+    RowTile rt;
+    if (!row_tile(rt, lds_bias, P.b0, SW_DBWD_BIAS_TILES * SW_BIAS_TILE_FLOATS, P.M)) return;
+    const int lane = rt.lane, h = rt.h;
+    const int64_t rr = rt.rr;
+    const float d3[3] = {P.d_dx[rr * 3], P.d_dx[rr * 3 + 1], P.d_dx[rr * 3 + 2]};
     float* grad_row = P.grad + rr * SW_ACT_LD + 4 * h;
     const f32x4 nomask = {0.f, 0.f, 0.f, 0.f};
     MaskRing mr;
-    mask_start(mr, P.bits, tile, lds_emb + 2 * 16 * 64, lane);
+    mask_start(mr, P.bits, rt.tile, rt.lds_emb + 2 * 16 * 64, lane);
     mask_fetch(mr, 7);
     WStream ws;
-    ws_start(ws, P.w0, lds_bias, lds_ring, lane);
+    ws_start(ws, P.w0, lds_bias, rt.lds_ring, lane);
     f32x16 in[8], out[8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 w0 = *reinterpret_cast<const f32x4*>(ws.bias + (0 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-            const f32x4 w1 = *reinterpret_cast<const f32x4*>(ws.bias + (1 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-            const f32x4 w2 = *reinterpret_cast<const f32x4*>(ws.bias + (2 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[n][4 * g + e] = w0[e] * d0 + w1[e] * d1 + w2[e] * d2;
-        }
+    wrows_valu<3>(ws.bias, d3, out);                                     // d h7 = _time_out.weight^T . d dx
 #pragma nounroll
     for (int l = 7; l >= 1; --l) {
 #pragma unroll
@@ -306,27 +294,9 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
             mask_fetch(mr, 7);
             // d h7 = output_linear.weight^T . d raw: out_ch weight rows as bias-style tiles (tile n of channel c: [h][r])
             const float* wt = lds_all + h * 16;
-#pragma unroll
-            for (int n = 0; n < 8; ++n)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 w0 = *reinterpret_cast<const f32x4*>(wt + (0 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-                    const f32x4 w1 = *reinterpret_cast<const f32x4*>(wt + (1 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-                    const f32x4 w2 = *reinterpret_cast<const f32x4*>(wt + (2 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-                    const f32x4 w3 = *reinterpret_cast<const f32x4*>(wt + (3 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) out[n][4 * g + e] = w0[e] * dr[0] + w1[e] * dr[1] + w2[e] * dr[2] + w3[e] * dr[3];
-                }
-            if (oc == 5) {                                                   // wave-uniform
-#pragma unroll
-                for (int n = 0; n < 8; ++n)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 w4 = *reinterpret_cast<const f32x4*>(wt + (4 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) out[n][4 * g + e] += w4[e] * dr5;
-                    }
-            }
+            const float d4[4] = {dr[0], dr[1], dr[2], dr[3]}, d5[1] = {dr5};
+            wrows_valu<4>(wt, d4, out);
+            if (oc == 5) wrows_valu<1, true>(wt + 4 * 8 * SW_BIAS_TILE_FLOATS, d5, out);      // wave-uniform
             ws_wait<0>();            // h7's mask has landed (no segment lies between its fetch and its use here: once per tile, ~1 us)
         } else {
         mask_fetch(mr, 8);
@@ -370,7 +340,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
             const float z = zv[sc];
             const float* dxs = P.dx + (ray * S + sc) * 3;
             const float x0 = rox + ddx * z + dxs[0], x1 = roy + ddy * z + dxs[1], x2 = roz + ddz * z + dxs[2];   // x + dx, as the forward formed it
-            float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+            float g0 = 0.f, g1 = 0.f, g2 = 0.f;                               // the Jacobian of mlp_backward_dx_kernel<true>, in line (see there)
 #pragma unroll
             for (int a = 0; a < 30; ++a) {
                 const int k = a / 3, c = a % 3;
@@ -388,16 +358,8 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
             if (h == 0) { f32x4 g4 = {g0, g1, g2, 0.f}; *reinterpret_cast<f32x4*>(P.g_dx + prow * 4) = g4; }
             // d h7 = _time_out.weight^T . d dx  (24 bias-style tiles right behind alpha_linear's 8), then _time.7 .. _time.1
             float* gd_row = P.grad_d + prow * SW_ACT_LD + 4 * h;
-#pragma unroll
-            for (int n = 0; n < 8; ++n)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 w0 = *reinterpret_cast<const f32x4*>(ws.bias + (0 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-                    const f32x4 w1 = *reinterpret_cast<const f32x4*>(ws.bias + (1 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-                    const f32x4 w2 = *reinterpret_cast<const f32x4*>(ws.bias + (2 * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) out[n][4 * g + e] = w0[e] * g0 + w1[e] * g1 + w2[e] * g2;
-                }
+            const float g3[3] = {g0, g1, g2};
+            wrows_valu<3>(ws.bias, g3, out);
 #pragma nounroll
             for (int l = 7; l >= 1; --l) {
 #pragma unroll
@@ -426,9 +388,7 @@ extern "C" int swnerf_mlp_backward_dx(const float* packed_bwd, const float* bits
     DxDev P;
     P.w0 = packed_bwd; P.b0 = packed_bwd + SW_BWD_W_FLOATS; P.bits = bits; P.d_out = d_out; P.M = M; P.grad = grad;
     P.pts = nullptr; P.d_pts = nullptr; P.Lp = 0;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(mlp_backward_dx_kernel<false>, grid, block, SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "mlp_backward_dx launch");
+    return sw_launch_rows(mlp_backward_dx_kernel<false>, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "mlp_backward_dx launch");
 }
 
 extern "C" int swnerf_mlp_backward_dx_pts(const float* packed_bwd, const float* bits, const float* d_out, const float* pts,
@@ -436,13 +396,11 @@ extern "C" int swnerf_mlp_backward_dx_pts(const float* packed_bwd, const float* 
     if (M == 0 && packed_bwd) return 0;
     if (!packed_bwd || !bits || !d_out || !pts || !grad || !d_pts || M < 0)
         return sw_fail(SWNERF_E_ARG, "mlp_backward_dx_pts: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10) return sw_fail(SWNERF_E_UNSUPP, "mlp_backward_dx_pts: %d position bands exceed 10", L_pos);
+    if (int rc = sw_check_bands("mlp_backward_dx_pts", 1, L_pos)) return rc;
     DxDev P;
     P.w0 = packed_bwd; P.b0 = packed_bwd + SW_BWD_IG_W_FLOATS; P.bits = bits; P.d_out = d_out; P.M = M; P.grad = grad;
     P.pts = pts; P.d_pts = d_pts; P.Lp = L_pos;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(mlp_backward_dx_kernel<true>, grid, block, SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "mlp_backward_dx_pts launch");
+    return sw_launch_rows(mlp_backward_dx_kernel<true>, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "mlp_backward_dx_pts launch");
 }
 
 extern "C" int swnerf_deform_backward_dx(const float* packed_bwd, const float* bits_d, const float* d_dx, int64_t M,
@@ -451,16 +409,14 @@ extern "C" int swnerf_deform_backward_dx(const float* packed_bwd, const float* b
     if (!packed_bwd || !bits_d || !d_dx || !grad_d || M < 0) return sw_fail(SWNERF_E_ARG, "deform_backward_dx: NULL pointer or negative M");
     DeformBwdDev P;
     P.w0 = packed_bwd; P.b0 = packed_bwd + SW_DBWD_W_FLOATS; P.bits = bits_d; P.d_dx = d_dx; P.M = M; P.grad = grad_d;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(deform_backward_dx_kernel, grid, block, SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "deform_backward_dx launch");
+    return sw_launch_rows(deform_backward_dx_kernel, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "deform_backward_dx launch");
 }
 
 extern "C" int swnerf_mlp_forward_train(const float* packed, const float* x, int64_t M, int L_pos, int L_dir,
                                         float* out, float* act, float* bits, void* stream) {
     if (M == 0 && packed) return 0;
     if (!packed || !x || !out || !act || !bits || M < 0) return sw_fail(SWNERF_E_ARG, "mlp_forward_train: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4) return sw_fail(SWNERF_E_UNSUPP, "mlp_forward_train: embedder bands (%d,%d) exceed (10,4)", L_pos, L_dir);
+    if (int rc = sw_check_bands("mlp_forward_train", 2, L_pos, L_dir)) return rc;
     MlpDev P;
     P.x = x; P.M = M; P.Lp = L_pos; P.Ld = L_dir; P.Lt = 0;
     P.Cpos = 3 * (1 + 2 * L_pos); P.C = P.Cpos + 3 * (1 + 2 * L_dir);
@@ -468,26 +424,21 @@ extern "C" int swnerf_mlp_forward_train(const float* packed, const float* x, int
     int rc = stream_ptrs(SWNERF_NET_CANON, packed, 0, &P.w0, &P.b0, &P.nbias, &P.two_pass);
     if (rc) return rc;
     P.wvl = views_loop_ptr(SWNERF_NET_CANON, packed);
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL((mlp_forward_kernel<false, true>), grid, block, SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "mlp_forward_train launch");
+    return sw_launch_rows(mlp_forward_kernel<false, true>, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "mlp_forward_train launch");
 }
 
 extern "C" int swnerf_deform_forward_train(const float* packed, const float* x, const float* t_emb, int64_t M,
                                            int L_pos, int L_dir, int L_time, float* dx, float* act_d, float* bits_d, void* stream) {
     if (M == 0 && packed) return 0;
     if (!packed || !x || !t_emb || !dx || !act_d || !bits_d || M < 0) return sw_fail(SWNERF_E_ARG, "deform_forward_train: NULL pointer or negative M");
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4 || L_time < 0 || L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "deform_forward_train: embedder bands (%d,%d,%d) exceed (10,4,10)", L_pos, L_dir, L_time);
+    if (int rc = sw_check_bands("deform_forward_train", 3, L_pos, L_dir, L_time)) return rc;
     DeformDev P;
     P.x = x; P.t_emb = t_emb; P.M = M; P.Lp = L_pos; P.C = 3 * (1 + 2 * L_pos) + 3 * (1 + 2 * L_dir); P.Ct = 1 + 2 * L_time;
     P.dx = dx; P.act = act_d; P.bits = bits_d;
     int two = 0;
     int rc = stream_ptrs(SWNERF_NET_DNERF, packed, 1, &P.w0, &P.b0, &P.nbias, &two);
     if (rc) return rc;
-    const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-    hipLaunchKernelGGL(deform_forward_train_kernel, grid, block, SW_LDS_FIXED_FLOATS * sizeof(float), (hipStream_t)stream, P);
-    return sw_check(hipGetLastError(), "deform_forward_train launch");
+    return sw_launch_rows(deform_forward_train_kernel, P, M, SW_LDS_FIXED_FLOATS * sizeof(float), stream, "deform_forward_train launch");
 }
 
 // ---- the fused training pass ("backward for the fused path") ---------------------

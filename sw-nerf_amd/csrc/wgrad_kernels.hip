@@ -646,7 +646,7 @@ extern "C" int swnerf_unslot_grad(const float* Cs, int ld_s, int rows, int slot0
                                   float* W, int ldw, int col0, void* stream) {
     if (!Cs || !W || rows < 1 || nslots < 1 || slot0 < 0 || slot0 + nslots > SW_XS_LD || ld_s < nslots)
         return sw_fail(SWNERF_E_ARG, "unslot_grad: bad arguments (rows=%d slot0=%d nslots=%d ld_s=%d)", rows, slot0, nslots, ld_s);
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4) return sw_fail(SWNERF_E_UNSUPP, "unslot_grad: embedder bands (%d,%d) exceed (10,4)", L_pos, L_dir);
+    if (int rc = sw_check_bands("unslot_grad", 2, L_pos, L_dir)) return rc;
     const int total = rows * nslots;
     hipLaunchKernelGGL(unslot_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Cs, ld_s, rows, slot0,
                        nslots, L_pos, L_dir, W, ldw, col0);

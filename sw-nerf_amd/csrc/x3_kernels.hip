@@ -106,8 +106,7 @@ extern "C" int swnerf_pack_net_x3_kind(int kind, const float* const* params, int
                                        const float* packed_fp32, float* packed_x3, void* stream) {
     if (!params || !packed_fp32 || !packed_x3) return sw_fail(SWNERF_E_ARG, "pack_net_x3: NULL pointer");
     if (kind != SWNERF_NET_CANON && kind != SWNERF_NET_DNERF) return sw_fail(SWNERF_E_ARG, "pack_net_x3: unknown kind %d", kind);
-    if (L_pos < 0 || L_pos > 10 || L_dir < 0 || L_dir > 4 || L_time < 0 || L_time > 10)
-        return sw_fail(SWNERF_E_UNSUPP, "pack_net_x3: embedder bands (%d,%d,%d) exceed (10,4,10)", L_pos, L_dir, L_time);
+    if (int rc = sw_check_bands("pack_net_x3", 3, L_pos, L_dir, L_time)) return rc;
     const int np = kind == SWNERF_NET_CANON ? 24 : 42;
     for (int i = 0; i < np; ++i) if (!params[i]) return sw_fail(SWNERF_E_ARG, "pack_net_x3: params[%d] is NULL", i);
     hipStream_t st = (hipStream_t)stream;
