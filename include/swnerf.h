@@ -390,7 +390,9 @@ int swnerf_render_pass_backward_noview(const float* packed_bwd, const float* bit
  * (act_d uses the first 2048 columns; xs_d = gamma(x) 64 slots + gamma(t) 32 slots).
  * backward: packed_bwd_fused = swnerf_pack_net_bwd_kind(SWNERF_BWD_DNERF_FUSED); dx = the forward's position_delta;
  * g_position_delta [N,S,3] its upstream gradient or NULL; outputs grad / grad_d [rows, act floats], d_raw [rows,4],
- * g_dx [rows,4] = d dx (4th column 0) - the A operand of the `_time_out` weight-gradient GEMM. */
+ * g_dx [rows,4] = d dx (4th column 0) - the A operand of the `_time_out` weight-gradient GEMM.
+ * The backward takes L_pos alone and checks it with cols: L_pos outside 0..10 is SWNERF_E_ARG there ("cols %d / L_pos %d"),
+ * not SWNERF_E_UNSUPP as at the entry points that take the bands of a net. */
 int swnerf_render_pass_train_dnerf(const swnerf_pass_args* args /*HOST*/, float* act, float* bits, float* xs,
                                    float* act_d, float* bits_d, float* xs_d, void* stream);
 int swnerf_render_pass_backward_dnerf(const float* packed_bwd_fused, const float* bits, const float* bits_d, const float* raw,
@@ -427,7 +429,8 @@ int swnerf_canon_narrow_grads(const float* grad, int ldg, const float* act, int 
  * All operands 16-byte aligned, leading dimensions multiples of 4; outputs accumulate (atomics). */
 int swnerf_deform_narrow_grads(const float* grad_d, int ldg, const float* act_d, int lda, const float* xs_d, const float* g_dx, int64_t M,
                                float* c0s, float* cts, float* w4, float* b_l0, float* b4, void* stream);
-/* ... for xs_d: slots 64..95 hold gamma(t) (L_time bands) instead of gamma(d) */
+/* ... for xs_d: slots 64..95 hold gamma(t) (L_time bands) instead of gamma(d); L_time outside 0..10 is one of its bad
+ * arguments (SWNERF_E_ARG, the message gives L_time), not SWNERF_E_UNSUPP */
 int swnerf_unslot_grad_time(const float* Cs, int ld_s, int rows_w, int nslots, int L_time, float* W, int ldw, int col0, void* stream);
 
 /* ---- the fused T-NeRF pass under autograd (TNeRF, model.py:152-210; the step of t_nerf/run_tnerf.py:646-720) ----------------

@@ -36,7 +36,8 @@ def _relu(i, pre, flips, pres):
 
 
 def deform64(sd, ex, et, flips=None, pres=None):
-    """query_time (model.py:128-136) in float64 on the encodings gamma(x) [M,63], gamma(t) [M,21] -> dx [M,3]"""
+    """query_time (model.py:128-136) in float64 on the encodings gamma(x) [M,63], gamma(t) [M,21] (the widths of the default
+    bands; any others are taken from the operands) -> dx [M,3]"""
     lin = lambda name, x: x @ sd[name + ".weight"].T + sd[name + ".bias"]
     h = torch.cat([ex, et], -1)
     for i in range(8):
@@ -46,26 +47,26 @@ def deform64(sd, ex, et, flips=None, pres=None):
     return lin("_time_out", h)
 
 
-def mlp64(sd, ex, et, ed, x32, dx_value, flips=None, pres=None, run_deform=True, detach_bands=()):
+def mlp64(sd, ex, et, ed, x32, dx_value, flips=None, pres=None, run_deform=True, detach_bands=(), L_pos=10):
     """DirectTemporalNeRF.forward (model.py:128-151) in float64 with the ReLUs written as masks.  sd: float64 parameters
     (state_dict names); ex / et / ed: the fp32 encodings gamma(x) [M,63], gamma(t) [M,21], gamma(d) [M,27] the reference
     forms, cast to float64; x32 [M,3] fp32, dx_value [M,3] fp32: x' takes its value from x32 + dx_value in fp32 (and its
     encoding's value from the fp32 encoding of that), its gradient from the float64 dx.  flips / pres: {layer: bool
     [M, units]} / dict that receives {layer: pre-activation}.  run_deform=False (t == 0 with zero_canonical, model.py:143-145):
     dx = 0 and only `_occ` is evaluated.  detach_bands (tests of the checker only): frequency bands k of gamma(x') whose
-    sin / cos columns carry no gradient to x'.  Returns (raw [M,4], dx [M,3])."""
+    sin / cos columns carry no gradient to x'.  L_pos: the bands of gamma(x') (ex is 3(1+2 L_pos) wide).  Returns (raw [M,4], dx [M,3])."""
     lin = lambda name, x: x @ sd[name + ".weight"].T + sd[name + ".bias"]
     if run_deform:
         dx = deform64(sd, ex, et, flips, pres)
         xp32 = x32 + dx_value                                        # model.py:147 as the evaluation under test rounds it
         xp = xp32.double() + (dx - dx.detach())
-        g = embed64(xp)
+        g = embed64(xp, L_pos)
         if detach_bands:
             keep = torch.ones(g.shape[1], dtype=torch.bool)
             for k in detach_bands:
                 keep[3 + 6 * k:9 + 6 * k] = False
             g = torch.where(keep, g, g.detach())
-        pts = O.embed(xp32, 10).double() + (g - g.detach())
+        pts = O.embed(xp32, L_pos).double() + (g - g.detach())
     else:
         dx = torch.zeros((ex.shape[0], 3), dtype=torch.float64)
         pts = ex
@@ -85,13 +86,14 @@ class Truth:
     the loss sees raw and position_delta only); second: (gamma(x2), gamma(t2)), fp32 [n*S, .], the inputs of a second evaluation of
     the deformation net alone whose dx the loss sees as position_delta_2 (the TV operand of run_dnerf.py:690-725), or None."""
 
-    def __init__(self, sd_np, names, n, S, enc, dx_value, run_deform, compose, ray_loss, second=None, detach_bands=()):
+    def __init__(self, sd_np, names, n, S, enc, dx_value, run_deform, compose, ray_loss, second=None, detach_bands=(), L_pos=10):
         self.sd = {k: v.double().requires_grad_(True) for k, v in O.to_torch_sd(sd_np).items()}
         self.names, self.n, self.S = list(names), n, S
         ex, et, ed, x32 = enc
         self.ex, self.et, self.ed = (a.double().reshape(n, S, -1) for a in (ex, et, ed))
         self.x32, self.dxv = x32.float().reshape(n, S, 3), dx_value.float().reshape(n, S, 3)
         self.run_deform, self.compose, self.ray_loss, self.detach_bands = run_deform, compose, ray_loss, detach_bands
+        self.L_pos = L_pos
         self.second = None if second is None else tuple(a.double().reshape(n, S, -1) for a in second)     # (ex2, et2)
 
     def grads(self, idx, flips=None, pres=None, flips2=None, pres2=None):
@@ -102,7 +104,7 @@ class Truth:
             v.grad = None
         flat = lambda a: a[idx].reshape(m * S, -1)
         raw, dx = mlp64(sd, flat(self.ex), flat(self.et), flat(self.ed), flat(self.x32), flat(self.dxv), flips, pres,
-                        self.run_deform, self.detach_bands)
+                        self.run_deform, self.detach_bands, self.L_pos)
         raw, dx = raw.reshape(m, S, 4), dx.reshape(m, S, 3)
         ret = {"raw": raw, "position_delta": dx}
         if self.compose is not None:
@@ -170,18 +172,20 @@ def _check(T, gpu_grads, what, thr, rtol):
     return flips, len(risky), worst
 
 
-def ray_encodings(rb, z, t=None):
+def ray_encodings(rb, z, t=None, bands=(10, 4, 10)):
     """The fp32 encodings the reference forms for the samples of rays rb [n,12] at depths z [n,S] (run_dnerf.py:46-83):
-    (gamma(x) [n*S,63], gamma(t) [n*S,21], gamma(d) [n*S,27], x [n*S,3]); t: another frame time than column 8."""
+    (gamma(x) [n*S,63], gamma(t) [n*S,21], gamma(d) [n*S,27], x [n*S,3]) at the default bands = (L_pos, L_dir, L_time);
+    t: another frame time than column 8."""
     n, S = z.shape
     pts = (rb[:, None, 0:3] + rb[:, None, 3:6] * z[..., None]).reshape(-1, 3)
     ft = rb[:, 8:9] if t is None else torch.full((n, 1), t, dtype=torch.float32)
-    et = O.embed(ft[:, None].expand(n, S, 1).reshape(-1, 1), 10)
-    ed = O.embed(rb[:, None, -3:].expand(n, S, 3).reshape(-1, 3), 4)
-    return O.embed(pts, 10), et, ed, pts
+    et = O.embed(ft[:, None].expand(n, S, 1).reshape(-1, 1), bands[2])
+    ed = O.embed(rb[:, None, -3:].expand(n, S, 3).reshape(-1, 3), bands[1])
+    return O.embed(pts, bands[0]), et, ed, pts
 
 
-def ray_truth(sd_np, names, rb, z, white_bkgd, ray_loss, dx_value, second=None, noise=None, zero_canonical=True, detach_bands=()):
+def ray_truth(sd_np, names, rb, z, white_bkgd, ray_loss, dx_value, second=None, noise=None, zero_canonical=True, detach_bands=(),
+              bands=(10, 4, 10)):
     """The Truth of a render pass of rays rb [n,12] (frame time = column 8) at depths z [n,S]"""
     n, S = z.shape
     t = float(rb[0, 8])
@@ -190,13 +194,13 @@ def ray_truth(sd_np, names, rb, z, white_bkgd, ray_loss, dx_value, second=None, 
     if second is not None:
         t2, z2 = second
         assert z2.shape == z.shape
-        sec = ray_encodings(rb, z2, float(np.float32(t2)))[:2]
-    return Truth(sd_np, names, n, S, ray_encodings(rb, z), dx_value, not (t == 0. and zero_canonical),
-                 dict(z=z, rays_d=rb[:, 3:6], white_bkgd=white_bkgd, noise=noise), ray_loss, sec, detach_bands)
+        sec = ray_encodings(rb, z2, float(np.float32(t2)), bands)[:2]
+    return Truth(sd_np, names, n, S, ray_encodings(rb, z, bands=bands), dx_value, not (t == 0. and zero_canonical),
+                 dict(z=z, rays_d=rb[:, 3:6], white_bkgd=white_bkgd, noise=noise), ray_loss, sec, detach_bands, bands[0])
 
 
 def flip_aware_check(sd_np, rb, z, white_bkgd, ray_loss, gpu_grads, what, dx_value, second=None, noise=None, thr=5e-6, rtol=2e-5,
-                     stats=None):
+                     stats=None, bands=(10, 4, 10)):
     """sd_np: the DirectTemporalNeRF's fp32 weights (numpy, state_dict names); rb [n,12] (frame time = column 8), z [n,S]
     fp32 CPU tensors; dx_value [n,S,3]: position_delta of the evaluation under test (ignored at t == 0);
     ray_loss(ret, idx) -> scalar: the loss restricted to rays idx (ret: rgb_map disp_map acc_map raw position_delta, and
@@ -204,7 +208,7 @@ def flip_aware_check(sd_np, rb, z, white_bkgd, ray_loss, gpu_grads, what, dx_val
     loss must be the sum of it over a partition of the rays; gpu_grads {name: tensor | None}: a parameter reported as None
     is compared, as zeros, with the truth like any other.  Returns (#flips, #risky); stats (a dict) receives `worst`,
     the largest residual of a tensor over its max."""
-    T = ray_truth(sd_np, list(gpu_grads), rb, z, white_bkgd, ray_loss, dx_value, second, noise)
+    T = ray_truth(sd_np, list(gpu_grads), rb, z, white_bkgd, ray_loss, dx_value, second, noise, bands=bands)
     flips, risky, worst = _check(T, gpu_grads, what, thr, rtol)
     if stats is not None:
         stats["worst"] = worst

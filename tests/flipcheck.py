@@ -18,10 +18,10 @@ import torch
 from oracle import nerf_oracle as O
 
 
-def _mlp64(sd, e, flips=None, pres=None):
+def _mlp64(sd, e, flips=None, pres=None, Cpos=63):
     """vallina_NeRF.forward (model.py:39-62) in float64 with the ReLU written as a mask; flips: {layer: bool [rows, units]}
     (layers 0..7 = pts_linears, 8 = views_linears.0).  use_viewdirs=False (model.py:59-60) when sd has output_linear and e is
-    63 wide; else e = [gamma(x) 63 | gamma(d) 27]."""
+    Cpos wide; else e = [gamma(x) Cpos | gamma(d)] (Cpos = 63, gamma(d) 27 wide at the default bands)."""
     lin = lambda name, x: x @ sd[name + ".weight"].T + sd[name + ".bias"]
 
     def relu(i, pre):
@@ -31,36 +31,38 @@ def _mlp64(sd, e, flips=None, pres=None):
         if flips is not None and i in flips:
             m = m ^ flips[i]
         return pre * m
-    pts = e[:, :63]
+    pts = e[:, :Cpos]
     h = pts
     for i in range(8):
         h = relu(i, lin(f"pts_linears.{i}", h))
         if i == 4:
             h = torch.cat([pts, h], -1)
-    if e.shape[1] == 63:
+    if e.shape[1] == Cpos:
         return lin("output_linear", h)
     sigma = lin("alpha_linear", h)
-    hv = relu(8, lin("views_linears.0", torch.cat([lin("feature_linear", h), e[:, 63:]], -1)))
+    hv = relu(8, lin("views_linears.0", torch.cat([lin("feature_linear", h), e[:, Cpos:]], -1)))
     return torch.cat([lin("rgb_linear", hv), sigma], -1)
 
 
-def flip_aware_check(sd_np, rb, z, white_bkgd, ray_loss, gpu_grads, what, thr=5e-6, rtol=2e-5, noise=None):
+def flip_aware_check(sd_np, rb, z, white_bkgd, ray_loss, gpu_grads, what, thr=5e-6, rtol=2e-5, noise=None, bands=(10, 4), stats=None):
     """sd_np: the net's fp32 weights (numpy; vallina_NeRF names, with or without view directions); rb [n,8|11], z [n,S] fp32 CPU tensors;
+    bands = (L_pos, L_dir) of the embedders the net was built for; stats (a dict) receives `worst`, the largest residual of a tensor over its max;
     ray_loss(ret, idx) -> scalar: the loss restricted to rays idx (ret: rgb_map disp_map acc_map raw of those rays) - the
     total loss must be the sum of it over a partition of the rays; gpu_grads: {name: tensor}.  Returns (#flips, #risky)."""
     n, S = z.shape
     names = [k for k in gpu_grads if gpu_grads[k] is not None]
     sd = {k: v.double().requires_grad_(True) for k, v in O.to_torch_sd(sd_np).items()}
     pts = rb[:, None, 0:3] + rb[:, None, 3:6] * z[..., None]
-    e_all = O.embed(pts.reshape(-1, 3), 10)
+    e_all = O.embed(pts.reshape(-1, 3), bands[0])
+    Cpos = e_all.shape[1]
     if rb.shape[1] > 8:                                   # nerf/run.py:80-82: the view directions, expanded per sample
-        e_all = torch.cat([e_all, O.embed(rb[:, None, -3:].expand(pts.shape).reshape(-1, 3), 4)], -1)
+        e_all = torch.cat([e_all, O.embed(rb[:, None, -3:].expand(pts.shape).reshape(-1, 3), bands[1])], -1)
     e_all = e_all.double().reshape(n, S, -1)
 
     def grads(idx, flips=None, pres=None):
         for v in sd.values():
             v.grad = None
-        raw = _mlp64(sd, e_all[idx].reshape(len(idx) * S, -1), flips, pres).reshape(len(idx), S, -1)
+        raw = _mlp64(sd, e_all[idx].reshape(len(idx) * S, -1), flips, pres, Cpos).reshape(len(idx), S, -1)
         raw_c = raw[..., :4] if noise is None else torch.cat([raw[..., :3], raw[..., 3:4] + noise[idx].double()[..., None]], -1)
         rgb, disp, acc, _, _ = O.raw2outputs(raw_c, z[idx].double(), rb[idx, 3:6].double(), 0., white_bkgd)
         ray_loss({"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "raw": raw}, idx).backward()
@@ -95,12 +97,15 @@ def flip_aware_check(sd_np, rb, z, white_bkgd, ray_loss, gpu_grads, what, thr=5e
             assert not bool(bad.any()), f"{what}: flip coefficients {c[bad].tolist()} are not 0 / 1 (units {[units[i] for i in torch.nonzero(bad)[:, 0].tolist()]})"
             diff = diff - Dm @ cr
             flips = int(cr.sum())
-    o = 0
+    o, worst = 0, 0.0
     for k in names:
         m = gpu_grads[k].numel()
         d, scale = float(diff[o:o + m].abs().max()), max(float(truth[o:o + m].abs().max()), 1e-12)
         assert d <= rtol * scale, f"{what} {k}: {d:.3e} of {scale:.3e} ({d / scale:.2e}) after accounting for {flips} ReLU flips of {len(risky)} risky units"
+        worst = max(worst, d / scale)
         o += m
+    if stats is not None:
+        stats["worst"] = worst
     return flips, len(risky)
 
 

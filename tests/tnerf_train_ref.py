@@ -49,15 +49,15 @@ def render64(sd, rb, z, white_bkgd, flips=None, pres=None, noise=None, Lp=10, Ld
     return {"rgb_map": rgb, "acc_map": acc, "disp_map": disp, "raw": torch.cat([rgb_raw, sigma.reshape(n, S, 1)], -1)}
 
 
-def risky_units(sd32, rb, z, noise=None, thr=5e-6):
+def risky_units(sd32, rb, z, noise=None, thr=5e-6, bands=(10, 4, 10)):
     """How many ReLU units (colour head, sigma) lie within thr of the kink in float64: a CPU quantity (flip_aware_check caps it at 400)."""
     pres = []
     with torch.no_grad():
-        render64({k: v.double() for k, v in sd32.items()}, rb, z, True, pres=pres, noise=noise)
+        render64({k: v.double() for k, v in sd32.items()}, rb, z, True, pres=pres, noise=noise, Lp=bands[0], Ld=bands[1], Lt=bands[2])
     return sum(int((p.abs() < thr).sum()) for p in pres)
 
 
-def flip_aware_check(sd32, rb, z, white_bkgd, ray_loss, gpu_grads, what, noise=None, thr=5e-6, rtol=2e-5):
+def flip_aware_check(sd32, rb, z, white_bkgd, ray_loss, gpu_grads, what, noise=None, thr=5e-6, rtol=2e-5, bands=(10, 4, 10), stats=None):
     """tnerf_ref.flip_aware_check over render64 (same method, same gate): ray_loss(ret, idx) sees disp_map and raw as well, and
     `noise` [n,S] is the sigma noise of the pass.  Returns (#flips, #risky)."""
     n, S = z.shape
@@ -67,7 +67,7 @@ def flip_aware_check(sd32, rb, z, white_bkgd, ray_loss, gpu_grads, what, noise=N
     def grads(idx, flips=None, pres=None):
         for v in sd.values():
             v.grad = None
-        ray_loss(render64(sd, rb[idx], z[idx], white_bkgd, flips, pres, None if noise is None else noise[idx]), idx).backward()
+        ray_loss(render64(sd, rb[idx], z[idx], white_bkgd, flips, pres, None if noise is None else noise[idx], *bands), idx).backward()
         return torch.cat([(sd[k].grad if sd[k].grad is not None else torch.zeros_like(sd[k])).reshape(-1) for k in names])
 
     pres = []
@@ -95,13 +95,16 @@ def flip_aware_check(sd32, rb, z, white_bkgd, ray_loss, gpu_grads, what, noise=N
             assert not bool(bad.any()), f"{what}: flip coefficients {c[bad].tolist()} are not 0 / 1"
             diff = diff - Dm @ cr
             flips = int(cr.sum())
-    o = 0
+    o, worst = 0, 0.0
     for k in names:
         m = gpu_grads[k].numel()
         dd, scale = float(diff[o:o + m].abs().max()), max(float(truth[o:o + m].abs().max()), 1e-12)
         print(f"{what} {k}: {dd:.3e} of {scale:.3e} ({dd / scale:.2e})")
         assert dd <= rtol * scale, f"{what} {k}: {dd:.3e} of {scale:.3e} ({dd / scale:.2e}) after {flips} flips of {len(risky)} risky units"
+        worst = max(worst, dd / scale)
         o += m
+    if stats is not None:
+        stats["worst"] = worst
     return flips, len(risky)
 
 
