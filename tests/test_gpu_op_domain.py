@@ -19,11 +19,11 @@ import pytest
 import torch
 
 from oracle import nerf_oracle as O
+from density_regimes import (T, _np, close, bits, Guarded, REGIMES, UPSTREAM, NAMES,             # the five regimes the ops were always held to
+                             comp_inputs, comp_loss, comp_reference)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-T = lambda a: torch.from_numpy(np.ascontiguousarray(a))
-SENTINEL = 0x5EED5EED                  # a finite float pattern no kernel here produces by accident
 
 
 @pytest.fixture(scope="module")
@@ -43,49 +43,6 @@ def sw():
 def L_():
     from swnerf import _lib
     return _lib
-
-
-def _np(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-
-def close(a, b, atol, rtol=0.0, what=""):
-    """every element: |a - b| <= atol + rtol |b|, equal NaN pattern; b is the float64 truth"""
-    a, b = _np(a).astype(np.float64), _np(b).astype(np.float64)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert np.array_equal(np.isnan(a), np.isnan(b)), f"{what}: NaN pattern differs"
-    if a.size == 0:
-        return 0.0
-    err = np.abs(np.nan_to_num(a) - np.nan_to_num(b))
-    lim = atol + rtol * np.abs(np.nan_to_num(b))
-    worst = float((err - lim).max())
-    assert worst <= 0.0, f"{what}: max err {err.max():.3e} (|ref| up to {np.abs(np.nan_to_num(b)).max():.3e}), worst excess {worst:.3e}"
-    return float(err.max())
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-class Guarded:
-    """n floats in the middle of a larger buffer filled with a sentinel bit pattern: `out` is what a kernel writes, check()
-    holds the floats in front of and behind it to their bits.  `off` floats in front (1024: 16-byte aligned; 1027: not)."""
-    PAD = 1024
-
-    def __init__(self, shape, dev, off=1024):
-        self.n = int(np.prod(shape))
-        self.off = off
-        self.buf = torch.full((off + self.n + self.PAD,), SENTINEL, dtype=torch.int32, device=dev)
-        self.out = self.buf[off:off + self.n].view(torch.float32).view(*shape) if self.n else torch.empty(shape, device=dev)
-
-    def check(self, what):
-        torch.cuda.synchronize()
-        assert bool((self.buf[:self.off] == SENTINEL).all()), f"{what}: wrote in front of the output"
-        assert bool((self.buf[self.off + self.n:] == SENTINEL).all()), f"{what}: wrote behind the output"
-
-    def untouched(self):
-        torch.cuda.synchronize()
-        return bool((self.buf == SENTINEL).all())
 
 
 # ------------------------------------------------------------------------------------------------------------ a. embed
@@ -208,68 +165,9 @@ def test_device_sincos_equals_host_build(sw, dev, tmp_path):
 
 
 # ----------------------------------------------------------------------------------------------------- c. compositing
-REGIMES = ("mild", "wall", "soft_then_wall", "all_opaque", "all_empty")
 COMP_S_BWD = (2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024)
 COMP_S_FWD = COMP_S_BWD + (1025, 2049)
 COMP_N = (1, 2, 3, 4, 5, 41)
-UPSTREAM = ("rgb", "disp", "acc", "weights", "depth", "all")
-
-
-def comp_inputs(regime, S, seed, N=41):
-    """densities a trained scene produces (random nets do not); everything float32"""
-    rng = np.random.default_rng(seed)
-    raw = (rng.standard_normal((N, S, 4)) * 1.5).astype(np.float32)
-    idx = np.arange(S)[None, :]
-    if regime == "mild":
-        sg = rng.standard_normal((N, S)) * 3.0 - 0.5
-    elif regime == "wall":                                   # empty space, then a surface from a random sample on
-        j = rng.integers(0, S, (N, 1))
-        sg = np.where(idx >= j, 10.0 ** rng.uniform(2, 4, (N, S)), -0.1 - np.abs(rng.standard_normal((N, S))))
-    elif regime == "soft_then_wall":
-        j = rng.integers((S + 1) // 2, S, (N, 1)) if S > 2 else np.ones((N, 1), np.int64)
-        sg = np.where(idx >= j, 10.0 ** rng.uniform(1, 3, (N, S)), np.abs(rng.standard_normal((N, S)) * 3.0))
-    elif regime == "all_opaque":
-        sg = 10.0 ** rng.uniform(3, 6, (N, S))
-    else:
-        sg = np.full((N, S), -2.0)
-    raw[..., 3] = sg.astype(np.float32)
-    z = np.sort(rng.uniform(2, 6, (N, S)).astype(np.float32), -1)
-    d = rng.standard_normal((N, 3)).astype(np.float32)
-    noise = (rng.standard_normal((N, S)) * 0.5).astype(np.float32)
-    if regime == "all_empty":
-        noise = -np.abs(noise)                               # stays empty under noise: disp NaN, acc 0, every sigma gradient exactly 0
-    ups = {"rgb": rng.standard_normal((N, 3)).astype(np.float32), "disp": rng.standard_normal(N).astype(np.float32),
-           "acc": rng.standard_normal(N).astype(np.float32), "weights": rng.standard_normal((N, S)).astype(np.float32),
-           "depth": rng.standard_normal(N).astype(np.float32)}
-    return raw, z, d, noise, ups
-
-
-NAMES = ("rgb", "disp", "acc", "weights", "depth")
-
-
-def comp_loss(outs, ups, which, conv):
-    """sum of <output, upstream gradient> over the outputs named by `which`: the others get no gradient (None at the autograd
-    function, NULL at the ABI).  A NaN disparity (acc == 0) carries no gradient in the reference either: masked out."""
-    tot = None
-    for name, o in zip(NAMES, outs):
-        if which != "all" and which != name:
-            continue
-        if name == "disp":
-            o = torch.where(torch.isnan(o), torch.zeros_like(o), o)
-        t = (o * conv(ups[name])[:o.shape[0]]).sum()
-        tot = t if tot is None else tot + t
-    return tot
-
-
-def comp_reference(raw, z, d, noise, white, ups, with_grad):
-    """the oracle in float64 on the float32 inputs -> (outputs, {which: d raw})"""
-    r = T(raw).double().requires_grad_(with_grad)
-    outs = O.raw2outputs(r, T(z).double(), T(d).double(), 0., white, noise=None if noise is None else T(noise).double())
-    grads = {}
-    if with_grad:
-        for which in UPSTREAM:
-            grads[which], = torch.autograd.grad(comp_loss(outs, ups, which, lambda a: T(a).double()), r, retain_graph=True)
-    return [o.detach() for o in outs], grads
 
 
 def check_compositing(impl, regime, S, put, stats=None):
