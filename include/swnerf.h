@@ -806,6 +806,46 @@ size_t swnerf_lpips_layer_workspace_bytes(int64_t n, int64_t h, int64_t w);
 int swnerf_lpips_layer(const float* f0, const float* f1, const float* lin, int64_t n, int64_t h, int64_t w, int c,
                        int accumulate, void* workspace, double* out, float* map /* may be NULL */, void* stream);
 
+/* ---- square markers (nerf/transform_mesh.py: cv2.aruco's detectMarkers on images_ori/; csrc/marker_math.h, marker_kernels.hip,
+ * DESIGN.md 6k "Markers") ---------------------------------------------------------------------------------------------
+ * A marker is a 6 x 6 grid of cells: a one-cell black border round a 4 x 4 payload, on a lighter surround (ArUco's 4X4 family).
+ * Pixel coordinates: pixel (i, j) covers [j, j + 1) x [i, i + 1), its centre is (j + 0.5, i + 0.5) - cv2's coordinates plus 0.5.
+ * frames = DEVICE uint8 [n, H, W, c], c = 1, 3 (RGB) or 4 (alpha ignored); H, W in 1..16384, n in 0..65535 (0: a successful no-op).
+ * workspace = DEVICE, 256-byte aligned, swnerf_marker_workspace_bytes(n, H, W) bytes (0 for sizes the calls refuse; about 30 bytes
+ *   per pixel).  Nothing is allocated, the host is never synchronised, the launches depend on n, H, W only.  Every stage up to the
+ *   coarse corners is integer arithmetic with order-independent integer atomics: the same bits on every run.
+ * marker_mask: grey [n, H, W] = (4899 R + 9617 G + 1868 B + 8192) >> 14 (c == 1: a copy); mask [n, H, W] = 1 where
+ *   g cnt < s - C cnt, s and cnt the exact sum and pixel count of the (2 radius + 1)^2 window clipped to the image; radius 1..64,
+ *   C -255..255.
+ * marker_label: mask [n, H, W] (non-zero = dark) -> labels int32 [n, H, W]: -1 on light pixels, else the smallest frame-local linear
+ *   index i W + j of the pixel's 8-connected component.  Needs no workspace.
+ * marker_candidates: labels exactly as marker_label wrote them -> count [n] = the components of at least min_area (>= 16) pixels,
+ *   rows int32 [n, capacity, 11] = the first `capacity` of them in ascending label order: label, area, flags, x0 y0 .. x3 y3.  The
+ *   corners are pixel indices, clockwise with y down: P1 (farthest from the centroid rounded to half pixels), the pixel farthest on
+ *   the negative side of P1P2, P2 (farthest from P1), the pixel farthest on the positive side; the smallest linear index wins a tie.
+ *   Flags: SWNERF_MARKER_BORDER touches the image border, SWNERF_MARKER_ONE_SIDED no pixel on one side of P1P2 (that corner is 0 0),
+ *   SWNERF_MARKER_SMALL_QUAD integer quad area below min_area.
+ * marker_detect: all stages for each of the nradii (1..4, ascending) radii (HOST array): candidates without flags are refined (24
+ *   points per side at t in [0.15, 0.85], mid-level crossing of a bilinear profile along the normal at -4 .. 4 px, contrast >= 40, a
+ *   total-least-squares line through >= 8 crossings, corners where adjacent lines meet) and decoded (the 36 cell centres through the
+ *   homography, threshold (min + max) / 2, contrast >= 40, all 20 border cells dark).  A survivor whose centre lies within 4 px of
+ *   a survivor of a smaller radius is dropped.  count [n] = the markers found, also when that exceeds K; the first K in (radius,
+ *   label) order are stored: quads float32 [n, K, 4, 2] (x, y; clockwise with y down) and payload int32 [n, K] = the 16 payload
+ *   cells row-major from corner 0 with corner 1 to the right, the first cell in bit 15, white = 1.  Entries past count are not
+ *   written. */
+#define SWNERF_MARKER_BORDER 1
+#define SWNERF_MARKER_ONE_SIDED 2
+#define SWNERF_MARKER_SMALL_QUAD 4
+#define SWNERF_MARKER_CAND_INTS 11
+int64_t swnerf_marker_workspace_bytes(int64_t n, int64_t H, int64_t W);
+int     swnerf_marker_mask(const uint8_t* frames, int64_t n, int64_t H, int64_t W, int c, int radius, int C, void* workspace,
+                           uint8_t* grey, uint8_t* mask, void* stream);
+int     swnerf_marker_label(const uint8_t* mask, int64_t n, int64_t H, int64_t W, int32_t* labels, void* stream);
+int     swnerf_marker_candidates(const int32_t* labels, int64_t n, int64_t H, int64_t W, int min_area, void* workspace,
+                                 int64_t capacity, int32_t* rows, int32_t* count, void* stream);
+int     swnerf_marker_detect(const uint8_t* frames, int64_t n, int64_t H, int64_t W, int c, const int* radii /*HOST*/, int nradii, int C,
+                             int min_area, int K, void* workspace, float* quads, int32_t* payload, int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
