@@ -196,6 +196,11 @@ typedef struct swnerf_gemm_item {
     const float* A2; int lda2; int No2; float* C3; int ldc3; float* bias3;
 } swnerf_gemm_item;
 int swnerf_gemm_tn_group(const swnerf_gemm_item* items /*HOST*/, int n_items, int64_t M, void* stream);
+/* swnerf_gemm_tn_group in "bf16x3" arithmetic (opt-in): the main 256 x 256 product of every item that qualifies for
+ * the LDS-DMA kernel (16-byte aligned rows, M >= 4096; the first 16 such items) is evaluated as A_hi.B_hi + A_hi.B_lo + A_lo.B_hi on
+ * split-bf16 operands with fp32 accumulation, all of them as ONE launch; per entry |error| <= (2^-14 + n u) |A|^T |B| + n u |C0|, n = 3 M + 514.
+ * Bias column sums, both riders, and every item that does not qualify are fp32, as in swnerf_gemm_tn_group.  Same argument checks. */
+int swnerf_gemm_tn_group_x3(const swnerf_gemm_item* items /*HOST*/, int n_items, int64_t M, void* stream);
 
 /* ---- training path of DirectTemporalNeRF (autograd of model.py:128-151; the loss of
  * d_nerf/run_dnerf.py:690-725 needs d/d(position_delta) too).  The forward is the composition the

@@ -23,6 +23,7 @@
 #include "swnerf_common.h"
 #include "lds_dma.h"
 #include "mlp_core.h"
+#include "bf16x3_split.h"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -125,12 +126,6 @@ __device__ __forceinline__ void x3_advance(XStream& xs) {
 __device__ __forceinline__ void x3_rewind(XStream& xs, int net_chunks, const float* lds_bias, int lane) {
     xs.gnext -= (size_t)net_chunks * X3_CHUNK_BYTES;
     xs.bias = lds_bias + (lane >> 5) * 16;
-}
-
-__device__ __forceinline__ unsigned x3_cvt_pk(float a, float b) {       // [bf16(a) | bf16(b) << 16], round to nearest even
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
 }
 
 // `floor`: 0 for a ReLU layer, -inf for none (one v_max_f32 either way; see relu1 for why it is spelled in asm)

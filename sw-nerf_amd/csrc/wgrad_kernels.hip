@@ -502,10 +502,7 @@ static int gemm_dma_launch(GemmFused F, void* stream) {
 // ---- a "fused item": one 256 x 256 GEMM with its optional riders - swnerf_gemm_tn_fused's arguments, or an element of
 // swnerf_gemm_tn_group's list (index < 0: the former).  Both entry points check, place and launch it through the functions below.
 static int check_fused_item(const swnerf_gemm_item& q, int index) {
-    const char* bad = nullptr;
-    if (!q.A || !q.B || !q.C || q.lda < 256 || q.ldb < 256 || q.ldc < 256) bad = "main operands";
-    else if (q.B2 && (!q.C2 || q.Ni2 < 1 || q.Ni2 > 64 || q.ldb2 < q.Ni2 || q.ldc2 < q.Ni2)) bad = "B2 rider";
-    else if (q.A2 && (!q.C3 || q.No2 < 1 || q.No2 > 32 || q.lda2 < q.No2 || q.ldc3 < 256)) bad = "A2 rider";
+    const char* bad = fused_item_bad(&q);
     if (!bad) return 0;
     char who[48];
     if (index < 0) snprintf(who, sizeof who, "gemm_tn_fused");
@@ -513,8 +510,6 @@ static int check_fused_item(const swnerf_gemm_item& q, int index) {
     return sw_fail(SWNERF_E_ARG, "%s: bad %s (lda=%d ldb=%d ldc=%d Ni2=%d No2=%d)", who, bad, q.lda, q.ldb, q.ldc, q.Ni2, q.No2);
 }
 
-// the DMA kernel takes the item's main GEMM (and its B2 rider); otherwise it is separate swnerf_gemm_tn calls
-static bool fused_item_takes_dma(const swnerf_gemm_item& q, int64_t M) { return dma_aligned(q.A, q.lda) && dma_aligned(q.B, q.ldb) && M >= 4096; }
 static GemmFused make_fused(const swnerf_gemm_item& q, int64_t M) {
     GemmFused F;
     F.g.A = q.A; F.g.lda = q.lda; F.g.No = 256; F.g.B = q.B; F.g.ldb = q.ldb; F.g.Ni = 256; F.g.C = q.C; F.g.ldc = q.ldc; F.g.bias = q.bias;
@@ -529,7 +524,7 @@ static int fused_item_a2(const swnerf_gemm_item& q, int64_t M, void* stream) {
 }
 static int fused_item_alone(const swnerf_gemm_item& q, int64_t M, void* stream) {          // a checked item, its own launch(es)
     int rc;
-    if (fused_item_takes_dma(q, M)) rc = gemm_dma_launch(make_fused(q, M), stream);
+    if (fused_item_takes_dma(&q, M)) rc = gemm_dma_launch(make_fused(q, M), stream);
     else {
         rc = swnerf_gemm_tn(q.A, q.lda, 256, q.B, q.ldb, 256, M, q.C, q.ldc, q.bias, stream);
         if (!rc && q.B2) rc = swnerf_gemm_tn(q.A, q.lda, 256, q.B2, q.ldb2, q.Ni2, M, q.C2, q.ldc2, nullptr, stream);
@@ -563,7 +558,7 @@ extern "C" int swnerf_gemm_tn_group(const swnerf_gemm_item* items, int n_items, 
     bool any_b2 = false;
     for (int k = 0; k < n_items; ++k) {
         const swnerf_gemm_item& q = items[k];
-        if (!fused_item_takes_dma(q, M) || G.n == GG_MAX) {
+        if (!fused_item_takes_dma(&q, M) || G.n == GG_MAX) {
             if (int rc = fused_item_alone(q, M, stream)) return rc;
             continue;
         }

@@ -82,6 +82,14 @@ def _device(device):
     return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
 
 
+def _set_wgrad_precision(args):
+    """args.wgrad_precision (extra, "fp32" or "bf16x3"; absent: the process default, fp32 unless SWNERF_WGRAD_PRECISION says
+    otherwise) selects the arithmetic of the grouped weight-gradient GEMMs for this runner's training (swnerf.wgrad.set_precision;
+    DESIGN.md 6c).  This is not `do_half_precision`: parameters, activations, the optimizer and every other kernel stay fp32."""
+    from . import wgrad
+    wgrad.set_precision(_opt(args, 'wgrad_precision', wgrad.DEFAULT_PRECISION))
+
+
 def _make_optimizer(args, creator, params, adamw=False, **kw):
     """Adam (AdamW with adamw) over `params`: torch.optim's, or with args.optimizer == "fused" (extra, default "torch") the
     multi-tensor HIP step of swnerf.optim - the same arithmetic, state and checkpoints."""
@@ -115,6 +123,7 @@ def create_nerf(args, device=None):
     netchunk = args.netchunk
     network_query_fn = lambda inputs, viewdirs, network_fn: render.run_network(
         inputs, viewdirs, network_fn, embed_fn=embed_fn, embeddirs_fn=embeddirs_fn, netchunk=netchunk)
+    _set_wgrad_precision(args)
     optimizer = _make_optimizer(args, "create_nerf", grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start, _ = reload_latest(args.basedir, args.expname, model, model_fine, optimizer, ft_path=args.ft_path,
                              no_reload=args.no_reload, map_location=device)
@@ -143,6 +152,7 @@ def _create_dnerf(args, device, encoders, load, reproducible_wgrad=None, creator
         for net in (model, model_fine):
             if net is not None:
                 net.reproducible_wgrad = reproducible_wgrad
+    _set_wgrad_precision(args)
     optimizer = _make_optimizer(args, creator, grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start = load(model, model_fine, optimizer)
     train, test = _render_kwargs(args, network_query_fn, _coarse_fine(args, model, model_fine),
@@ -177,6 +187,7 @@ def create_tnerf(args, device=None):
     grad_vars = list(model.parameters())
     network_query_fn = _timed_query_fn(render_tnerf.run_network, embed_fn, embeddirs_fn, embedtime_fn, args.netchunk,
                                        args.nerf_type != "temporal")
+    _set_wgrad_precision(args)
     optimizer = _make_optimizer(args, "create_tnerf", grad_vars, lr=args.lrate, betas=(0.9, 0.999))
     start = _reload(args, device)(model, None, optimizer)
     train, test = _render_kwargs(args, network_query_fn, {'N_importance': 0, 'network_fn': model, 'N_samples': args.N_samples})
@@ -190,6 +201,7 @@ def create_fit2d(args, device=None):
     from . import fit2d
     device = _device(device)
     model = fit2d.Model(input_dimension=2 + 4 * args.L, layer_num=args.layer_num).to(device)
+    _set_wgrad_precision(args)
     optimizer = _make_optimizer(args, "create_fit2d", model.parameters(), adamw=True, lr=0.001)
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.95)
     start, metrics = 0, {"MSE": [], "PSNR": []}

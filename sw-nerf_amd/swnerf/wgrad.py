@@ -13,6 +13,7 @@ feature_linear: it has no activation (model.py:49-53) and every kernel runs it f
   d views_linears.0.weight[:, :256] = G W_f^T + db_hv (x) b_f,   d feature_linear.weight = Wv_f^T G,   d feature_linear.bias = Wv_f^T db_hv
 (swnerf_feature_finish; Wv_f = views_linears.0.weight[:, :256])."""
 import ctypes
+import os
 
 import torch
 
@@ -20,6 +21,27 @@ from . import _lib
 
 SW_ACT_HV = 2304          # csrc/swnerf_common.h: column of the view hidden layer in the act / grad rows
 SW_ACT_H7 = 1792          # ... of h7
+
+# Arithmetic of the grouped 256 x 256 weight-gradient GEMMs of a fused training step (_Group below): "fp32" (the default:
+# v_mfma_f32_32x32x2_f32) or "bf16x3" (split-bf16 operands, three v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation;
+# include/swnerf.h swnerf_gemm_tn_group_x3).  Opt-in: set_precision(), SWNERF_WGRAD_PRECISION, or a creator's
+# args.wgrad_precision.  Everything outside a _Group - the narrow products, T-NeRF's 128-wide GEMMs, the op path - is fp32.
+_PRECISIONS = ("fp32", "bf16x3")
+DEFAULT_PRECISION = os.environ.get("SWNERF_WGRAD_PRECISION", "fp32")
+if DEFAULT_PRECISION not in _PRECISIONS:
+    raise ValueError(f"swnerf: SWNERF_WGRAD_PRECISION={DEFAULT_PRECISION!r} is not one of {sorted(_PRECISIONS)}")
+PRECISION = DEFAULT_PRECISION
+X3_LAUNCHES = 0           # grouped bf16x3 launches so far (swnerf_gemm_tn_group_x3 calls)
+
+
+def set_precision(name):
+    """Select the arithmetic of the grouped weight-gradient GEMMs; returns the previous setting."""
+    global PRECISION
+    if name not in _PRECISIONS:
+        raise ValueError(f"swnerf.wgrad.set_precision: unknown precision {name!r} (one of {sorted(_PRECISIONS)})")
+    prev, PRECISION = PRECISION, name
+    return prev
+
 
 GEMM_STREAMS = 2          # side streams the weight-gradient GEMMs of a chunk fan out over
 _SIDE_STREAMS = {}
@@ -64,16 +86,22 @@ def _st(st):
 
 
 class _Group:
-    """Collects the 256 x 256 weight-gradient GEMMs of one row chunk and launches them as ONE kernel (swnerf_gemm_tn_group:
-    one ramp and one atomic epilogue per chunk instead of one per layer); `st` is where that launch goes."""
+    """Collects the 256 x 256 weight-gradient GEMMs of one row chunk and launches them as ONE kernel (swnerf_gemm_tn_group,
+    or swnerf_gemm_tn_group_x3 with set_precision("bf16x3"): one ramp and one atomic epilogue per chunk instead of one per layer);
+    `st` is where that launch goes."""
 
     def __init__(self, st):
         self.st, self.items = st, []
 
     def launch(self, L, M):
         if self.items:
+            global X3_LAUNCHES
             arr = (_lib.GemmItem * len(self.items))(*self.items)
-            _lib.check(L.swnerf_gemm_tn_group(arr, len(self.items), M, _st(self.st)), "gemm_tn_group")
+            if PRECISION == "bf16x3":
+                _lib.check(L.swnerf_gemm_tn_group_x3(arr, len(self.items), M, _st(self.st)), "gemm_tn_group_x3")
+                X3_LAUNCHES += 1
+            else:
+                _lib.check(L.swnerf_gemm_tn_group(arr, len(self.items), M, _st(self.st)), "gemm_tn_group")
             self.items = []
 
 

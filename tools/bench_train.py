@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One training step of the reference (nerf/run.py:635-708) on the differentiable op path, C2 shape:
 4096 rays, 64 coarse + 128 fine samples, coarse + fine nets, loss = mse(rgb) + mse(rgb0), backward, Adam.
-Secondary metric (the headline bench.py is the forward render); prints a markdown table + per-kernel times."""
+Secondary metric (the headline bench.py is the forward render); prints a markdown table + per-kernel times.
+    bench_train.py [N] [--wgrad-precision fp32|bf16x3]      (the grouped weight-gradient GEMMs' arithmetic: swnerf.wgrad.set_precision)"""
 import os
 import sys
 import time
@@ -11,10 +12,12 @@ for p in (os.path.join(ROOT, "sw-nerf_amd"), ROOT):
     sys.path.insert(0, p)
 import numpy as np
 import torch
-from swnerf import synth, model, embedder, render
+from swnerf import synth, model, embedder, render, wgrad
 
 dev = torch.device("cuda:0")
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+N = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 4096
+WGRAD = sys.argv[sys.argv.index("--wgrad-precision") + 1] if "--wgrad-precision" in sys.argv else "fp32"
+wgrad.set_precision(WGRAD)
 embed_fn, c10 = embedder.get_embedder(10, 3, 0)
 embeddirs_fn, c4 = embedder.get_embedder(4, 3, 0)
 nets = []
@@ -64,5 +67,5 @@ torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / reps
 t = np.mean(np.array(timers), 0)
 flop = N * 256 * 2 * (527872 + 495616 + 527872)   # EXECUTED: forward + dX chain + dW, feature_linear folded (bench.py FLOP_EXEC_TRAIN_PER_ROW)
-print(f"| training step, {N} rays x (64+128), two nets, fp32 | {dt*1e3:.1f} ms/step | {N/dt:,.0f} rays/s | forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, Adam {t[2]:.1f} ms | ~{flop/dt/1e12:.0f} TFLOP/s |")
+print(f"| training step, {N} rays x (64+128), two nets, fp32{'' if WGRAD == 'fp32' else ', weight-gradient GEMMs ' + WGRAD} | {dt*1e3:.1f} ms/step | {N/dt:,.0f} rays/s | forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, Adam {t[2]:.1f} ms | ~{flop/dt/1e12:.0f} TFLOP/s |")
 print(f"peak memory {torch.cuda.max_memory_allocated()/2**30:.1f} GiB")
