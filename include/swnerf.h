@@ -851,6 +851,57 @@ int     swnerf_marker_candidates(const int32_t* labels, int64_t n, int64_t H, in
 int     swnerf_marker_detect(const uint8_t* frames, int64_t n, int64_t H, int64_t W, int c, const int* radii /*HOST*/, int nradii, int C,
                              int min_area, int K, void* workspace, float* quads, int32_t* payload, int32_t* count, void* stream);
 
+/* ---- mesh clean-up and measurement (what a trimesh user does after nerf/extract_mesh.py and nerf/transform_mesh.py: split, smooth,
+ * area / volume; csrc/meshops_math.h, meshops_kernels.hip, DESIGN.md 6b "Clean-up and measurement") ------------------------------
+ * verts = DEVICE float32 [V,3], faces = DEVICE int32 [F,3] (0-based), contiguous: what swnerf_mc_emit writes.  V = 0 or F = 0 is a
+ * successful no-op with empty / zero results.  V >= 2^31 or 3 F >= 2^31 is SWNERF_E_ARG (corner ids 3 f + k are int32).
+ * workspace = DEVICE, 256-byte aligned, swnerf_mesh_workspace_bytes of (V, F) bytes (0 for refused sizes; about 12 bytes a vertex
+ *   and 4 a face); every call may use the same one.  Nothing is allocated and the host is never synchronised; each phase is its
+ *   own launch (no grid-wide barrier, no spin-wait), and all counts come from order-independent integer atomics.
+ * A face index outside 0..V-1 is never dereferenced: the first kernel that reads `faces` counts such indices into a status word,
+ *   the later kernels of the call see it and write nothing further; the caller reads the word and refuses the mesh.
+ * mesh_components: lock-free union-find over the vertices joining (a, b) and (b, c) of every face.  vlabel int32 [V] = the smallest
+ *   vertex index of the vertex's component.  table int32 [V,3] (capacity; the first C rows are written) = (label, faces, vertices)
+ *   in ascending label order; a face belongs to the label of its first vertex, an unreferenced vertex is a component of 0 faces.
+ *   counts int32 [2] = {C, bad indices}.  With bad indices vlabel and table hold nothing meaningful and C = 0.
+ * mesh_compact: keep the vertices whose label is in kept (DEVICE int32 [n_kept], ascending) and the faces whose first vertex is;
+ *   verts_out [V_out,3] = verts[mask], faces_out [F_out,3] = remap[faces[fmask]], normals / colors (either pair may be NULL) like
+ *   verts; the original relative order is kept.  V_out and F_out are the table's sums over the kept rows: rows past them are
+ *   never written.
+ * mesh_incidence: CSR of the corners at each vertex.  offsets int32 [V+1], items int32 [3F]: vertex v's slice
+ *   items[offsets[v] .. offsets[v+1]) holds the corner ids 3 f + k with faces[f][k] == v in ascending order, for any valence
+ *   (short slices by insertion, long ones by an in-place heap sort).  A face may repeat an index.  status int32 [1] = bad indices.
+ * mesh_smooth_step: one umbrella step, out [V,3] != verts.  For vertex v at p with slice c_1 < .. < c_n, in fp64 without
+ *   contraction: S = sum over the slice, in that order, of P[faces[f][(k+1)%3]] then P[faces[f][(k+2)%3]] (f = c / 3, k = c % 3);
+ *   out = (float)(p + (double)s * (S / (double)(2 n) - p)); n = 0: out = p.  On a closed manifold every neighbour counts twice
+ *   (the uniform umbrella); at a boundary the interior neighbours weigh double.  A pure function of its inputs: the same bits on
+ *   every run.  Taubin smoothing alternates s = lambda and s = mu.
+ * mesh_vertex_normals: normals [V,3] = the sum over the slice, in order, of the fp64 cross(p1 - p0, p2 - p0) of each incident
+ *   face (area weighting), divided by its fp64 length and rounded to float32; a zero or non-finite sum gives (0,0,0).
+ * mesh_measure: values double [16] = area (sum of sqrt((cx cx + cy cy) + cz cz) / 2, c = cross(p1 - p0, p2 - p0) in fp64), signed
+ *   volume (sum of p0 . cross(p1, p2) / 6), the three first moments (sum of the volume term times (p0 + p1 + p2) / 4), bbox min
+ *   [5..7] and max [8..10] over the referenced vertices (exact; +inf / -inf when there is none), the rest 0.  The fp64 sums are
+ *   per-workgroup partials over contiguous face ranges added in index order by one workgroup: no float atomics, the same bits on
+ *   every run.  counts int64 [8] = referenced vertices, undirected edges E, boundary edges (in exactly one face), non-manifold
+ *   edges (in more than two faces, or twice in one direction), components with at least one face, Euler characteristic
+ *   V_ref - E + F, closed (no boundary and no non-manifold edge), bad indices.  An edge is counted at the smallest corner id that
+ *   carries it, found by scanning the incidence slice of its end point of lower valence. */
+int64_t swnerf_mesh_workspace_bytes(int64_t V, int64_t F);
+int     swnerf_mesh_components(const int32_t* faces, int64_t V, int64_t F, void* workspace, int32_t* vlabel, int32_t* table,
+                               int32_t* counts, void* stream);
+int     swnerf_mesh_compact(const float* verts, const int32_t* faces, const float* normals /* may be NULL */,
+                            const float* colors /* may be NULL */, const int32_t* vlabel, int64_t V, int64_t F, const int32_t* kept,
+                            int64_t n_kept, void* workspace, int64_t V_out, int64_t F_out, float* verts_out, int32_t* faces_out,
+                            float* normals_out, float* colors_out, void* stream);
+int     swnerf_mesh_incidence(const int32_t* faces, int64_t V, int64_t F, void* workspace, int32_t* offsets, int32_t* items,
+                              int32_t* status, void* stream);
+int     swnerf_mesh_smooth_step(const float* verts, const int32_t* faces, const int32_t* offsets, const int32_t* items, int64_t V,
+                                int64_t F, float s, float* out, void* stream);
+int     swnerf_mesh_vertex_normals(const float* verts, const int32_t* faces, const int32_t* offsets, const int32_t* items, int64_t V,
+                                   int64_t F, float* normals, void* stream);
+int     swnerf_mesh_measure(const float* verts, const int32_t* faces, const int32_t* offsets, const int32_t* items, int64_t V,
+                            int64_t F, void* workspace, double* values, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

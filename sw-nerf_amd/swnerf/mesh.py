@@ -10,7 +10,11 @@ directions shared by every grid point - the 8-layer trunk and the density ONCE p
 only the view branch V times: 8832 + 640 V MFMAs per 32 points instead of 9472 V.
 `swnerf_query_points_time` does the same for the two time-conditioned nets at one frame time (`frame_time=`):
 DirectTemporalNeRF (deformation net, gamma(x + dx), canonical trunk once per point; d_nerf/run_dnerf.py:46-83) and TNeRF
-(t_nerf/run_tnerf.py:48-87); `mesh_sequence` meshes a list of times."""
+(t_nerf/run_tnerf.py:48-87); `mesh_sequence` meshes a list of times.
+
+Clean-up and measurement of the extracted mesh (connected components, Taubin smoothing, normals, area / volume / extents) are in
+swnerf.meshops and re-exported here: `components`, `keep_components`, `vertex_faces`, `smooth`, `vertex_normals`, `measure`,
+`clean`, and the `clean=` keyword of `generate_mesh` / `nerf_to_mesh`."""
 import ctypes
 
 import numpy as np
@@ -220,6 +224,11 @@ class Mesh:
             fh.write(_rows("f", np.repeat(f, 2, axis=1), "%d//%d", per=2))
         return path
 
+    def measure(self):
+        """area, volume, centroid, extents, edge statistics of this mesh, computed on the GPU (swnerf.meshops.measure)"""
+        from . import meshops
+        return meshops.measure(self)
+
 
 def _rows(tag, a, fmt, per=1):
     """`tag` + one line per row of a 2-D array, `per` values per field (a//a)"""
@@ -258,23 +267,36 @@ def _grid_geometry(xyz_coords):
     return tuple(float(x) for x in spacing), tuple(float(x) for x in origin)
 
 
-def _to_mesh(out):
+def _check_clean(clean):
+    """refuse a bad `clean=` before any GPU work"""
+    from . import meshops
+    meshops.clean_options(clean)
+
+
+def _to_mesh(out, clean=None):
+    """device arrays -> Mesh; `clean` (None, True or a dict of meshops.clean's keywords) is applied on the device first"""
+    from . import meshops
+    opts = meshops.clean_options(clean)
+    if opts is not None:
+        out = meshops.clean_arrays(*out, **opts)
     verts, faces, normals, vcol = out
     return Mesh(verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), None if vcol is None else vcol.cpu().numpy())
 
 
-def generate_mesh(density_field, color_field, xyz_coords, density_threshold=0.5, device=None):
+def generate_mesh(density_field, color_field, xyz_coords, density_threshold=0.5, device=None, clean=None):
     """extract_mesh.py:92-131 on the GPU: marching cubes of density_field at density_threshold with the reference's spacing /
-    origin derivation, each vertex coloured by its nearest sample -> Mesh.  The fields are the float64 numpy arrays of
-    sample_grid (computed in float32 here) or CUDA tensors; color_field may be None.  Differences from skimage + trimesh:
-    DESIGN.md 6b."""
+    origin derivation, each vertex coloured by its nearest sample -> Mesh.  clean: None (the surface as extracted), True or a dict
+    of `clean`'s keywords (floaters removed, optionally smoothed, on the device before the host copy).  The fields are the float64
+    numpy arrays of sample_grid (computed in float32 here) or CUDA tensors; color_field may be None.  Differences from skimage +
+    trimesh: DESIGN.md 6b."""
+    _check_clean(clean)
     spacing, origin = _grid_geometry(xyz_coords)
     if device is None:
         device = density_field.device if isinstance(density_field, torch.Tensor) and density_field.is_cuda else torch.device("cuda")
     as_dev = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, np.float32))).to(device, torch.float32)
     d = as_dev(density_field)
     c = as_dev(color_field) if color_field is not None else None
-    return _to_mesh(marching_cubes(d, density_threshold, spacing, origin, c))
+    return _to_mesh(marching_cubes(d, density_threshold, spacing, origin, c), clean)
 
 
 def _grid_spacing_origin(bounds, resolution):
@@ -282,20 +304,22 @@ def _grid_spacing_origin(bounds, resolution):
     return tuple(float(a[1] - a[0]) for a in axes), tuple(float(a[0]) for a in axes)
 
 
-def nerf_to_mesh(net, bounds, resolution=64, density_threshold=8, num_views=100, batch_size=1 << 20, frame_time=None):
+def nerf_to_mesh(net, bounds, resolution=64, density_threshold=8, num_views=100, batch_size=1 << 20, frame_time=None, clean=None):
     """extract_mesh.py:133-145 with the network in place of `nerf_function`: grid query and marching cubes on the net's
     device, no host round trip of the field (the [R,R,R,4] query output is read in place) -> Mesh.  frame_time: the time a
-    time-conditioned net is meshed at (sample_grid)."""
+    time-conditioned net is meshed at (sample_grid).  clean: as in generate_mesh."""
+    _check_clean(clean)
     q = sample_grid(bounds, resolution, net, num_views=num_views, batch_size=batch_size, on_device=True, sharded=False,
                     frame_time=frame_time)
     spacing, origin = _grid_spacing_origin(bounds, resolution)
-    return _to_mesh(marching_cubes(q[..., 3], density_threshold, spacing, origin, q[..., :3]))
+    return _to_mesh(marching_cubes(q[..., 3], density_threshold, spacing, origin, q[..., :3]), clean)
 
 
 def mesh_sequence(net, bounds, times, resolution=64, density_threshold=8, num_views=100, out_dir=None, basename="mesh_{:03d}.obj"):
     """The surface of a time-conditioned net (DirectTemporalNeRF, TNeRF) at every time of `times` -> [Mesh, ...]: one grid
     query and one marching-cubes pass per time on the net's device, the R^3 grid points uploaded once.  With `out_dir` mesh i is
-    also written to out_dir/basename.format(i) (Wavefront OBJ, Mesh.export)."""
+    also written to out_dir/basename.format(i) (Wavefront OBJ, Mesh.export).  The meshes are as extracted: `clean(m)` removes the
+    floaters of each (the signature is pinned by tests/test_query_time_host.py, so there is no `clean=` keyword here)."""
     import os
     axes = [np.linspace(b[0], b[1], resolution) for b in bounds]
     X, Y, Z = np.meshgrid(*axes, indexing='ij')
@@ -313,3 +337,7 @@ def mesh_sequence(net, bounds, times, resolution=64, density_threshold=8, num_vi
             m.export(os.path.join(out_dir, basename.format(i)))
         meshes.append(m)
     return meshes
+
+
+from .meshops import (components, select_components, keep_components, vertex_faces, smooth_step, smooth, vertex_normals,  # noqa: E402,F401
+                      measure, measure_raw, clean, Measurement)
