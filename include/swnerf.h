@@ -485,7 +485,9 @@ int swnerf_tnerf_feature_finish(const float* G, const float* db9, const float* W
  * linear   : y[M,N] = act(x[M,K] . weight[N,K]^T + bias)   torch.nn.functional.linear (+ relu if relu != 0); bias may be NULL
  * gemm_nn  : c[M,N] = a[M,K] . b[K,N]                       input gradient of a linear layer: dX = dY . weight
  * relu_mask: dy[e] = y[e] > 0 ? dy[e] : 0, in place        relu backward
- * The weight gradient is swnerf_gemm_tn.  Any leading dimensions >= the row length; fp32 MFMA, fp32 accumulate. */
+ * The weight gradient is swnerf_gemm_tn.  Any leading dimensions >= the row length; fp32 MFMA, fp32 accumulate.
+ * A NaN at x[r, k] makes exactly row r of y NaN without an activation and under ELU; with relu that row is 0, because fmaxf
+ * returns the non-NaN operand (the fused passes' v_max does the same). */
 int swnerf_linear(const float* x, int ldx, int64_t M, int K, const float* weight /*[N,K]*/, const float* bias /*[N]*/,
                   int N, int relu, float* y, int ldy, void* stream);
 int swnerf_gemm_nn(const float* a, int lda, int64_t M, int K, const float* b, int ldb, int N, float* c, int ldc,

@@ -44,7 +44,10 @@ def _embedded(dev, kw, g):
 
 def test_linear_kernel_shapes(dev):
     """swnerf_linear / swnerf_gemm_nn / swnerf_relu_mask on ragged shapes (M, N, K not multiples of the 64 x 64 x 32
-    tile; K = 63, 319; a strided input) against float64 matmuls."""
+    tile; K = 63, 319) against float64 matmuls.  `x` is sliced out of a wider tensor, but generic.linear copies a strided input
+    before the kernel sees it (_lib.dev_f32), so this covers leading dimension == row length and 16-byte-aligned bases only - and,
+    no K of a 128-tile case being a multiple of 4, none of the 16-byte-load kernels.  Leading dimensions above the row length, offset bases and every kernel of the
+    dispatch are tests/test_gpu_generic_units.py, through the C ABI."""
     from swnerf import generic
     rng = np.random.default_rng(31)
     for M, K, N, relu in ((1, 63, 256, True), (300, 319, 256, True), (65, 90, 5, False), (1000, 256, 3, False), (129, 7, 130, True), (0, 8, 4, False)):
