@@ -27,7 +27,7 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(const float* raw, 
     const float dx = rd[ray * 3], dy = rd[ray * 3 + 1], dz = rd[ray * 3 + 2];
     const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
     CompGrads g = {g_rgb ? g_rgb[ray * 3] : 0.f, g_rgb ? g_rgb[ray * 3 + 1] : 0.f, g_rgb ? g_rgb[ray * 3 + 2] : 0.f,
-                   g_acc ? g_acc[ray] : 0.f, g_depth ? g_depth[ray] : 0.f};
+                   g_acc ? g_acc[ray] : 0.f, g_depth ? g_depth[ray] : 0.f, g_rgb != nullptr};
     const float* zr = zv + ray * S;
     const float4* rr = reinterpret_cast<const float4*>(raw) + ray * S;
     const float* nr = noise ? noise + ray * S : nullptr;

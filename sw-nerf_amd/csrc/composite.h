@@ -4,7 +4,7 @@
 // cumprod precision, white background - changes here and nowhere else (tests/test_host_math.py keeps the literals in this file).
 // With c = sigmoid(rgb), e = exp(-relu(sigma)*dist), a = 1-e, p = 1-a+1e-10, T_i = prod_{j<i} p_j, w = a*T:
 //   G_i   = dL/dw_i = g_rgb.c_i + gA + gD*z_i (+ g_w_i)
-//   dL/da_i = G_i*T_i - (sum_{k>i} G_k*w_k)/p_i ,   da/dsigma = dist*e*[sigma>0]
+//   dL/da_i = G_i*T_i - (sum_{k>i} G_k*w_k)/p_i ,   da/dsigma = dist*e*[not sigma<=0]
 //   dL/drgb_i = w_i * g_rgb * c_i*(1-c_i)
 // Pointwise pieces only.  How a kernel loads raw / z / noise is its own business, and so is the cross-lane scan: the three
 // forms associate differently (wave_dpp.h), so a caller names the one it uses.
@@ -18,8 +18,11 @@ __device__ __forceinline__ float comp_dist(bool more, float zn, float z, float d
     return (more ? (zn - z) : 1e10f) * dnorm;
 }
 
+// relu as ATen has it: a NaN density stays NaN (fmaxf is maxNum and would render it as empty space); every other value as fmaxf(x, 0)
+__device__ __forceinline__ float comp_relu(float sg) { return (sg < 0.f) ? 0.f : sg; }
+
 // e = exp(-relu(sigma) * dist); alpha = 1 - e (ray.py:157).  `sg` already carries the noise (added after `raw` is stored).
-__device__ __forceinline__ float comp_transmit(float sg, float dist) { return expf(-fmaxf(sg, 0.f) * dist); }
+__device__ __forceinline__ float comp_transmit(float sg, float dist) { return expf(-comp_relu(sg) * dist); }
 
 // a lane past the ray's last sample is dead: alpha = 0, so it leaves the product and every sum alone
 __device__ __forceinline__ float comp_alpha(float sg, float dist, bool live) {
@@ -88,7 +91,8 @@ __device__ __forceinline__ void comp_write_maps(float pr, float pg, float pb, fl
 // ---- backward
 // what reaches every sample of a ray alike: d rgb_map, A = dL/d acc, D = dL/d depth.  The caller starts A and D from d(acc_map) and
 // d(depth_map), 0 where it has none; the fold adds the white background (rgb_map += 1 - acc) and disp = 1/max(1e-10, depth/acc).
-struct CompGrads { float r, g, b, A, D; };
+// rgb: d rgb_map is given.  Without it no gradient reaches the colours, whatever they hold: a NaN colour must not enter G as 0 * NaN.
+struct CompGrads { float r, g, b, A, D; bool rgb; };
 
 __device__ __forceinline__ void comp_bwd_fold(CompGrads& g, int white, const float* g_disp, float pd, float pa) {
     if (white) g.A -= (g.r + g.g + g.b);
@@ -100,7 +104,7 @@ __device__ __forceinline__ void comp_bwd_fold(CompGrads& g, int white, const flo
 
 // G = dL/dw of a sample with colours c = sigmoid(rgb), without a d(weights) term (the caller adds its own)
 __device__ __forceinline__ float comp_bwd_G(const CompGrads& g, float c0, float c1, float c2, float z) {
-    return g.r * c0 + g.g * c1 + g.b * c2 + g.A + g.D * z;
+    return (g.rgb ? g.r * c0 + g.g * c1 + g.b * c2 : 0.f) + g.A + g.D * z;
 }
 
 // d raw of a sample: R = sum_{k>i} G_k*w_k in double (the caller's suffix scan), T and w as the forward stored them.
@@ -110,6 +114,7 @@ __device__ __forceinline__ f32x4 comp_bwd_sample(const CompGrads& g, float G, fl
     const float e = comp_transmit(sg, dist);
     const float p = 1.f - (1.f - e) + 1e-10f;
     const float dLda = G * T - (float)(R / (double)p);
-    const float dsig = (sg > 0.f) ? dLda * dist * e : 0.f;
+    const float dsig = (sg <= 0.f) ? 0.f : dLda * dist * e;                  // ATen's threshold backward: a NaN sigma passes the gradient
+    if (!g.rgb) return {0.f, 0.f, 0.f, dsig};
     return {w * g.r * c0 * (1.f - c0), w * g.g * c1 * (1.f - c1), w * g.b * c2 * (1.f - c2), dsig};
 }

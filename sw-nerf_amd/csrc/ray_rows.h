@@ -52,6 +52,17 @@ __device__ __forceinline__ void pack_row(float* o, int cols, float ox, float oy,
     o[k] = v0; o[k + 1] = v1; o[k + 2] = v2;
 }
 
+// |rays_d| of a row as the compositing scales its dists by it (ray.py:173) - and NaN when any of the row's o, d, near, far or frame
+// time (0.f where the row has none) is not finite.  One test per ray: every dist of such a ray is then NaN, and through it every
+// weight and every map, as the reference has them; the per-sample code of the passes stays as it is (the hidden ReLU of the
+// per-row MLP is maxNum, so `raw` of such a row would come back finite, from the biases).  A finite row keeps its bits.
+__device__ __forceinline__ float row_dnorm(float ox, float oy, float oz, float dx, float dy, float dz, float near, float far, float ft) {
+    const bool finite = __builtin_isfinite(ox) && __builtin_isfinite(oy) && __builtin_isfinite(oz) && __builtin_isfinite(dx) &&
+                        __builtin_isfinite(dy) && __builtin_isfinite(dz) && __builtin_isfinite(near) && __builtin_isfinite(far) &&
+                        __builtin_isfinite(ft);
+    return finite ? sqrtf(dx * dx + dy * dy + dz * dz) : __builtin_nanf("");
+}
+
 // A block's 256 rows, assembled in LDS, leave as 16-byte stores of the block's contiguous 256 * cols floats of the batch (a
 // row-per-thread store pattern writes `cols` dwords at a 4 * cols-byte stride: every store instruction touches 22 lines for
 // 256 useful bytes).  The last, partial block - and an `out` that is not 16-byte aligned - stores dword-wise.  Call after

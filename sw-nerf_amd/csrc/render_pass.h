@@ -15,6 +15,7 @@
 #include "mlp_core_x3.h"
 #include "resample.h"
 #include "composite.h"
+#include "ray_rows.h"
 
 #define SW_LDS_SC 256                    // max coarse samples when resampling
 #define SW_LDS_SORT 1024                 // max S + n_importance (padded to a power of two)
@@ -165,7 +166,7 @@ template <bool VEC4>
 __device__ __forceinline__ void comp_bwd_ray(const float* raw, int oc, const float* zv, const float* noise, int S, int lane, float dnorm,
                                              int white, const float* g_rgb, const float* g_disp, const float* g_acc,
                                              float* T_, float* W_, float* dR) {
-    CompGrads g = {g_rgb ? g_rgb[0] : 0.f, g_rgb ? g_rgb[1] : 0.f, g_rgb ? g_rgb[2] : 0.f, g_acc ? g_acc[0] : 0.f, 0.f};
+    CompGrads g = {g_rgb ? g_rgb[0] : 0.f, g_rgb ? g_rgb[1] : 0.f, g_rgb ? g_rgb[2] : 0.f, g_acc ? g_acc[0] : 0.f, 0.f, g_rgb != nullptr};
     double Tc = 1.0;
     float pa = 0.f, pd = 0.f;
     for (int base = 0; base < S; base += 64) {
@@ -280,7 +281,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     const float near = rb[6], far = rb[7];
     const float ft = (a.cols == 12) ? rb[8] : 0.f;
     const float v0 = VIEWS ? rb[a.cols - 3] : 0.f, v1 = VIEWS ? rb[a.cols - 2] : 0.f, v2 = VIEWS ? rb[a.cols - 1] : 0.f;
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);                  // ray.py:173
+    const float dnorm = row_dnorm(ox, oy, oz, dx, dy, dz, near, far, ft);    // ray.py:173; NaN for a row that is not finite
 
     WStream ws;
     XStream xs;

@@ -13,13 +13,17 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// Ascending in-place sort of buf[0..n) by one wave, ONLY if it is not already sorted (wave-uniform test); n_pow2 =
-// power of two >= n, buf has room for n_pow2 floats (the pad is filled with +inf).  Bitonic network.
+// The order of torch.sort: ascending, NaN behind everything (+inf included), all NaNs equal.  A total preorder, so the sort
+// and the merge below give every element a slot of its own whatever the lists hold; on lists without NaN it is `a < b`.
+__device__ __forceinline__ bool nan_last_lt(float a, float b) { return (a < b) || (b != b && a == a); }
+
+// Ascending (NaN last) in-place sort of buf[0..n) by one wave, ONLY if it is not already sorted (wave-uniform test); n_pow2 =
+// power of two >= n, buf has room for n_pow2 floats (the pad is filled with NaN: behind every element).  Bitonic network.
 __device__ __forceinline__ void wave_sort_if_unsorted(float* buf, int n, int n_pow2, int lane) {
     bool sorted = true;
-    for (int m = lane; m + 1 < n; m += 64) sorted = sorted && (buf[m] <= buf[m + 1]);
+    for (int m = lane; m + 1 < n; m += 64) sorted = sorted && !nan_last_lt(buf[m + 1], buf[m]);
     if (__all(sorted)) return;
-    for (int i = n + lane; i < n_pow2; i += 64) buf[i] = __builtin_inff();
+    for (int i = n + lane; i < n_pow2; i += 64) buf[i] = __builtin_nanf("");
     wave_lds_sync();
     for (int k = 2; k <= n_pow2; k <<= 1) {
         for (int jj = k >> 1; jj > 0; jj >>= 1) {
@@ -28,7 +32,7 @@ __device__ __forceinline__ void wave_sort_if_unsorted(float* buf, int n, int n_p
                 const int l = i + jj;
                 const float x = buf[i], y = buf[l];
                 const bool up = (i & k) == 0;
-                if ((x > y) == up) { buf[i] = y; buf[l] = x; }
+                if (nan_last_lt(y, x) == up) { buf[i] = y; buf[l] = x; }
             }
             wave_lds_sync();
         }
@@ -95,7 +99,9 @@ __device__ __forceinline__ float wave_zstd(double sm, const float* smp, int Ni, 
 // not at all for random u - so both are CHECKED and only an unsorted list is sorted first (bitonic, on that list alone;
 // sort_s / sort_n = powers of two >= S / Ni, the buffers hold that many floats).  Then each element's slot = its own index +
 // the number of elements of the other list in front of it (ties: coarse depths first), by binary search in LDS: 13
-// dependent LDS reads per lane instead of the 36 barrier-separated stages of a 256-element bitonic sort.
+// dependent LDS reads per lane instead of the 36 barrier-separated stages of a 256-element bitonic sort.  Both steps order
+// by nan_last_lt: non-finite weights make every sample NaN, and under plain `<` all of them would claim slot 0 and leave the
+// tail of z_fine unwritten.  With it the S + Ni slots are a permutation of 0 .. S+Ni-1 for any input.
 __device__ __forceinline__ void wave_rank_merge(float* zc, int S, int sort_s, float* smp, int Ni, int sort_n, float* zf, int lane) {
     wave_sort_if_unsorted(smp, Ni, sort_n, lane);
     wave_sort_if_unsorted(zc, S, sort_s, lane);
@@ -104,7 +110,7 @@ __device__ __forceinline__ void wave_rank_merge(float* zc, int S, int sort_s, fl
         int lo = 0, hi = Ni;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (smp[mid] < v) lo = mid + 1; else hi = mid;
+            if (nan_last_lt(smp[mid], v)) lo = mid + 1; else hi = mid;
         }
         zf[i + lo] = v;
     }
@@ -113,7 +119,7 @@ __device__ __forceinline__ void wave_rank_merge(float* zc, int S, int sort_s, fl
         int lo = 0, hi = S;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (zc[mid] <= v) lo = mid + 1; else hi = mid;
+            if (!nan_last_lt(v, zc[mid])) lo = mid + 1; else hi = mid;
         }
         zf[m + lo] = v;
     }

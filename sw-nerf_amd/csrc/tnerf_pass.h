@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_render_kernel
     const float* rb = a.ray_batch + ray * 12;    // [o, d, near, far, t, viewdirs] (run_tnerf.py:156-164)
     const float ox = rb[0], oy = rb[1], oz = rb[2], dx = rb[3], dy = rb[4], dz = rb[5];
     const float near = rb[6], far = rb[7], ft = rb[8];
-    const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);                  // run_tnerf.py:362
+    const float dnorm = row_dnorm(ox, oy, oz, dx, dy, dz, near, far, ft);    // run_tnerf.py:362; NaN for a row that is not finite
 
     const int ntiles = (S + 31) >> 5;
     WStream ws;

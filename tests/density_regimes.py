@@ -3,7 +3,12 @@ tests/test_gpu_op_domain.py (the standalone ops) and tests/test_gpu_fused_tail.p
 
 REGIMES are the five the standalone ops have been held to since they were written; their seeds and arrays must not move
 (test_gpu_op_domain.py derives its seeds from REGIMES.index).  ALL_REGIMES adds `spike`: one opaque sample per ray, everything
-else empty, the spike placed on the samples where a tile or sweep boundary of the fused kernels falls."""
+else empty, the spike placed on the samples where a tile or sweep boundary of the fused kernels falls.
+
+POISONS and the poison_* helpers are the non-finite cases of tests/test_gpu_nonfinite.py: NaN, +Inf or -Inf on ONE sample of every
+other ray - in the density (through `noise`), in a colour column of `raw`, or in a coarse weight of sample_pdf - on the same
+boundary samples as the spikes.  tests/test_nonfinite_host.py checks on the CPU that the float32 and the float64 oracle agree on
+the non-finite pattern of every such case, so that a pattern difference on the GPU is the kernel's."""
 import numpy as np
 import torch
 
@@ -74,6 +79,73 @@ def spike_positions(S, N, rng):
     n = min(N, len(must))
     j[:n] = must[:n]
     return j[:, None]
+
+
+POISONS = {"nan": float("nan"), "+inf": float("inf"), "-inf": float("-inf")}
+POISON_S = (2, 33, 65, 257)            # compositing: one tile, a tile and a sweep boundary; 257: the standalone op's fifth sweep
+POISON_PDF = ((64, 128), (64, 1), (1, 64), (128, 64))       # (S, Ni) at nb = 65: S > Ni, S < Ni, Ni = 1, S = 1
+POISON_NB = 65
+
+
+def poison_positions(S, N, rng):
+    """-> (rays [k], samples [k]): the poisoned rays are the odd ones - k = N // 2, so more than half of the rays stay clean and
+    a prefix of 3 or 5 rays holds both kinds - and each has ONE poisoned sample, placed by spike_positions' rule: sample 0, the
+    last one, 31 | 32 and 63 | 64 where S allows, over the first poisoned rays; random behind."""
+    rays = np.arange(1, N, 2)
+    assert 2 * len(rays) <= N
+    return rays, spike_positions(S, len(rays), rng)[:, 0]
+
+
+def poison_comp_inputs(S, kind, where, N=41):
+    """comp_inputs' mild regime (|sigma| and |rgb| of a few units, depths in 2 .. 6: nothing float32 overflows and float64 does
+    not) with POISONS[kind] on one sample of every odd ray: where = "density" (through noise, so raw stays finite) or "colour"
+    (column ray-index mod 3 of raw) -> (raw, z, d, noise, ups, rays, samples)"""
+    seed = 100 * S + 10 * list(POISONS).index(kind) + ("density", "colour").index(where)
+    raw, z, d, noise, ups = comp_inputs("mild", S, 424200 + seed, N=N)
+    rays, j = poison_positions(S, N, np.random.default_rng(seed))
+    if where == "density":
+        noise[rays, j] = POISONS[kind]
+    else:
+        raw[rays, j, rays % 3] = POISONS[kind]
+    return raw, z, d, noise, ups, rays, j
+
+
+def poison_pdf_inputs(S, Ni, kind, mode, target="weight", N=41):
+    """sample_pdf (+ merge) at nb = 65 bins: sorted bins and coarse depths in 2 .. 6, weights in 0.5 .. 1.5, u absent (mode "det") or
+    random.  target "weight": POISONS[kind] in one weight of every odd ray; "u": in one draw (mode "random" only)
+    -> (bins, w, u or None, z, rays, positions)"""
+    seed = 1000 * S + 10 * Ni + list(POISONS).index(kind) + 3 * (mode == "random") + 7 * (target == "u")
+    rng = np.random.default_rng(515100 + seed)
+    bins = np.sort(rng.uniform(2, 6, (N, POISON_NB)).astype(np.float32), -1)
+    w = rng.uniform(0.5, 1.5, (N, POISON_NB - 1)).astype(np.float32)
+    z = np.sort(rng.uniform(2, 6, (N, S)).astype(np.float32), -1)
+    u = None if mode == "det" else rng.uniform(0, 1, (N, Ni)).astype(np.float32)
+    rays, j = poison_positions(Ni if target == "u" else POISON_NB - 1, N, rng)
+    if target == "u":
+        u[rays, j] = POISONS[kind]
+    else:
+        w[rays, j] = POISONS[kind]
+    return bins, w, u, z, rays, j
+
+
+POISON_UPS = ("rgb", "acc", "depth", "weights", ("rgb", "acc", "depth", "weights"))     # no disparity: the gradient of
+#                                                 max(1e-10, NaN) is an ATen implementation detail, not a rule of the reference
+
+
+def poison_fused_noise(S, kind, sigma, N=41):
+    """the `noise` operand that turns a net's constant density `sigma` into comp_inputs' mild densities, with POISONS[kind] on one
+    sample of every odd ray, and sorted depths to give the pass -> (noise, z, rays, samples)"""
+    raw, z, _, _, _ = comp_inputs("mild", S, 636300 + S, N=N)
+    noise = (raw[..., 3] - np.float32(sigma)).astype(np.float32)
+    rays, j = poison_positions(S, N, np.random.default_rng(S + list(POISONS).index(kind)))
+    noise[rays, j] = POISONS[kind]
+    return noise, z, rays, j
+
+
+def same_nonfinite(a, b):
+    """equal NaN positions, and equal Inf positions and signs (b is the reference)"""
+    a, b = _np(a), _np(b)
+    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.where(np.isinf(b), b, 0), np.where(np.isinf(a), a, 0))
 
 
 def comp_inputs(regime, S, seed, N=41):

@@ -5,7 +5,8 @@ The domain edges are where the kernels change code path: embed halves its rows p
 leaves the float4 store when a block's image is not a multiple of 4 floats; raw2outputs and its backward carry a transmittance
 and a suffix sum from one 64-sample sweep to the next; sample_pdf sorts with a bitonic network padded to a power of two and merges
 by rank.  Every reference is a vectorised float64 evaluation (numpy / the CPU oracle on float64 tensors) of the same float32
-inputs; every element of every case is held to the tolerance - no "mostly" clause.  Finite inputs only.
+inputs; every element of every case is held to the tolerance - no "mostly" clause.  Finite inputs only: NaN and Inf are
+tests/test_gpu_nonfinite.py.
 
 Tolerances are the project's existing ones for these ops (tests/test_gpu_parity.py, tests/test_gpu_backward.py):
   embed 3e-7 abs; raw2outputs atol 2e-6 + rtol 2e-5; its backward atol 2e-6 + rtol 2e-4; sample_pdf atol 5e-5;
