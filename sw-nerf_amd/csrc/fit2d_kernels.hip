@@ -14,18 +14,11 @@
 #include "swnerf_common.h"
 #include "host_util.h"
 #include "render_pass.h"
+#include "fit2d_cols.h"
 
-// ---- the encoder ----------------------------------------------------------------------------------------------------
-// Lane half h = 0 holds the x coordinate's terms, h = 1 the y coordinate's: both halves run one instruction stream.
-// B-operand slot a = 0..47 (k-tile a >> 4, register a & 15) of half h carries encoding column sw_fit2d_col(a, h, L).
-#define SW_F2_MAX_L 23                     // 2 * 23 + 1 slots per half fit three 16-register k-tiles
+// ---- the encoder (the slot map sw_fit2d_col and SW_F2_MAX_L: fit2d_cols.h) --------------------------------------------
 #define SW_F2_MAX_LAYERS 64                // bias-style tiles of the whole net sit in LDS (1 KiB per layer)
 #define SW_F2_L0_STEPS 96                  // 8 n-tiles x 3 k-tiles
-static inline __host__ __device__ int sw_fit2d_col(int a, int h, int L) {
-    if (a < 2 * SW_F2_MAX_L) { const int i = a >> 1, s = a & 1; return i < L ? 2 + 4 * i + 2 * s + h : -1; }
-    if (a == 2 * SW_F2_MAX_L) return h;
-    return -1;
-}
 
 // xn = 2 * (p / max) - 1: a correctly rounded division and two more roundings (encoding.py:27; -ffp-contract=off)
 __device__ __forceinline__ float fit2d_normalise(float p, float maxv) { return 2.f * (p / maxv) - 1.f; }
