@@ -904,6 +904,52 @@ int     swnerf_mesh_vertex_normals(const float* verts, const int32_t* faces, con
 int     swnerf_mesh_measure(const float* verts, const int32_t* faces, const int32_t* offsets, const int32_t* items, int64_t V,
                             int64_t F, void* workspace, double* values, int64_t* counts, void* stream);
 
+/* ---- mesh welding and decimation by vertex clustering (trimesh's process=True merge and simplify_*; csrc/meshops_math.h,
+ * meshops_kernels.hip, DESIGN.md 6b "Welding and decimation") -----------------------------------------------------------------
+ * The same conventions as above (nothing allocated, no host synchronisation, one launch per phase, integer atomics only), with a
+ * workspace of its own: swnerf_mesh_simplify_workspace_bytes of (V, F) bytes (0 for refused sizes; mesh_cluster needs that of
+ * (V, 0)).  It holds an open-addressing table of 64-bit cell keys with a power-of-two capacity of at least 2 V (all ones = empty;
+ * a slot is claimed by atomicCAS and takes the atomicMin of its vertex indices; at most `capacity` probes, then counts[2] is set)
+ * and the per-label lists.  No result depends on which slot a key landed in: the same bits on every run.
+ * Cell of a vertex p for the origin o (float32 [3]) and the cell size h (float32, finite, > 0), in fp64: i_k = floor((p_k - o_k) / h);
+ *   valid iff 0 <= i_k < 2^21 on every axis (a NaN or an infinity is not); key = i_x | i_y << 21 | i_z << 42.
+ * mesh_cluster: vlabel int32 [V] = the smallest vertex index that shares the vertex's cell (every vertex, referenced or not).
+ *   origin = DEVICE float32 [3], or NULL: the per-axis minimum over all V vertices (integer atomicMin on ordered keys).
+ *   origin_out float32 [3] = the origin used.  counts int32 [3] = {clusters, invalid vertices, table overflow}.  With an invalid
+ *   vertex (or an overflow) vlabel and origin_out are not written.
+ * mesh_collapse: g = (vlabel[a], vlabel[b], vlabel[c]) for every face.  A face with two equal entries is degenerate; of the
+ *   others, those with the same triple after rotating the smallest label to the front are duplicates (the reversed triple is a
+ *   different face) and the smallest face index survives.  fpos int32 [F+1] = exclusive scan of the survivor flags, vmap int32
+ *   [V+1] = exclusive scan of "label of a surviving face": element i is in use iff its scan value differs from the next one's,
+ *   and that value is its output row.  counts int32 [5] = {V', F', degenerate, duplicate, bad indices}.  A face index (or a label)
+ *   outside 0..V-1 is counted and never followed; then vmap and fpos are not written and V' = F' = 0.
+ * mesh_collapse_emit: faces_out [F_out,3] = vmap[g] of the surviving faces in input order with their own corner order;
+ *   verts_out [V_out,3] (colors_out likewise when colors is given) = one row per label in use, ascending, by `placement`:
+ *   SWNERF_MESH_WELD     the rows of vertex l itself, bit for bit; normals_out too when normals is given
+ *   SWNERF_MESH_MEAN     per coordinate the fp64 sum over the members of l (all vertices labelled l, ascending) divided by their
+ *                        number, rounded once to float32
+ *   SWNERF_MESH_QUADRIC  colours as MEAN; the position minimises the sum of squared area-weighted plane distances of every input
+ *                        face with a corner labelled l (each once, ascending), regularised by eps times the trace toward the mean
+ *                        and solved by adjugate over determinant in fp64, in the term order csrc/meshops_math.h
+ *                        (meshops_quadric_point) writes down; the mean instead when the trace or the determinant is not a finite
+ *                        positive number, the result is not finite, or it leaves the closed cell of l
+ *   MEAN and QUADRIC write no normals (recompute them with mesh_incidence + mesh_vertex_normals on the output).  origin and cell are
+ *   those of mesh_cluster; V_out and F_out are counts[0] and counts[1] of mesh_collapse: rows past them are never written.
+ *   status int32 [1] = bad indices; nothing else is written then. */
+#define SWNERF_MESH_WELD 0
+#define SWNERF_MESH_MEAN 1
+#define SWNERF_MESH_QUADRIC 2
+int64_t swnerf_mesh_simplify_workspace_bytes(int64_t V, int64_t F);
+int     swnerf_mesh_cluster(const float* verts, int64_t V, const float* origin /* may be NULL */, float cell, void* workspace,
+                            int32_t* vlabel, float* origin_out, int32_t* counts, void* stream);
+int     swnerf_mesh_collapse(const int32_t* faces, const int32_t* vlabel, int64_t V, int64_t F, void* workspace, int32_t* vmap,
+                             int32_t* fpos, int32_t* counts, void* stream);
+int     swnerf_mesh_collapse_emit(const float* verts, const int32_t* faces, const float* normals /* may be NULL */,
+                                  const float* colors /* may be NULL */, const int32_t* vlabel, const int32_t* vmap,
+                                  const int32_t* fpos, const float* origin, float cell, int64_t V, int64_t F, int placement, double eps,
+                                  void* workspace, int64_t V_out, int64_t F_out, float* verts_out, int32_t* faces_out,
+                                  float* normals_out, float* colors_out, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

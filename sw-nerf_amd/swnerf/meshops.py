@@ -10,6 +10,10 @@ include/swnerf.h; csrc/meshops_kernels.hip, meshops_math.h); `swnerf.mesh` re-ex
   vertex_normals(verts, faces)        area-weighted normals
   measure(verts, faces)               area, volume, centroid, bounding box, edge statistics, Euler characteristic, closedness
   clean(mesh, ...)                    components -> selection -> compaction -> optional smoothing (+ normals) -> Mesh
+  cluster(verts, cell)                vertex labels of a uniform grid (the smallest vertex index of each cell)
+  weld(mesh, tolerance)               merge the vertices of one cell (trimesh's process=True); degenerate / duplicate faces go
+  decimate(mesh, cell | target_faces) vertex clustering with a quadric (volume-keeping), mean or weld representative per cell
+  decimation_cell(mesh, target_faces) the cell size that leaves at most target_faces faces (bisection of log2 cell)
 
 A mesh argument is a `Mesh`, the 4-tuple of `marching_cubes`, an OBJ path, or verts and faces (tensors or arrays); host data is
 uploaded.  A face index outside 0..V-1 raises ValueError naming how many there are; it is never dereferenced."""
@@ -290,12 +294,303 @@ def measure(m, faces=None, incidence=None):
                        euler=int(counts[5]), closed=bool(counts[6]))
 
 
+# ---------------------------------------------------------------------------------------------------- welding and decimation
+PLACEMENTS = {"weld": 0, "mean": 1, "quadric": 2}                  # SWNERF_MESH_WELD, _MEAN, _QUADRIC
+CELL_LIMIT = 2 ** 21                                               # cells an axis (the 21-bit index of the 64-bit cell key)
+
+
+def _check_cell(cell, what="cell"):
+    """-> the cell size as the float32 value the kernels use"""
+    try:
+        c = float(np.float32(cell))
+    except (TypeError, ValueError):
+        raise ValueError(f"swnerf.mesh: {what} must be a finite positive number, got {cell!r}") from None
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError(f"swnerf.mesh: {what} must be a finite positive number, got {cell!r}")
+    return c
+
+
+def _check_placement(placement, eps):
+    if placement not in PLACEMENTS:
+        raise ValueError(f"swnerf.mesh: unknown placement {placement!r} (one of {sorted(PLACEMENTS)})")
+    if not (np.isfinite(eps) and eps >= 0):
+        raise ValueError(f"swnerf.mesh: eps must be finite and >= 0, got {eps!r}")
+
+
+def _check_decimate(cell, target_faces, placement, eps):
+    if (cell is None) == (target_faces is None):
+        raise ValueError("swnerf.mesh.decimate: give exactly one of cell and target_faces")
+    _check_placement(placement, eps)
+    if cell is not None:
+        return _check_cell(cell), None
+    if not (isinstance(target_faces, (int, np.integer)) and not isinstance(target_faces, bool) and target_faces >= 1):
+        raise ValueError(f"swnerf.mesh.decimate: target_faces must be an integer >= 1, got {target_faces!r}")
+    return None, int(target_faces)
+
+
+def _raw(m, faces=None):
+    """The mesh argument with an OBJ path loaded and a Mesh opened, so that its vertices can be looked at before any upload"""
+    from . import mesh as _mesh
+    if faces is None:
+        if isinstance(m, str):
+            m = _mesh.load_obj(m)
+        if isinstance(m, _mesh.Mesh):
+            m = (m.vertices, m.faces, m.vertex_normals, m.vertex_colors)
+    return m
+
+
+def _extent(verts):
+    """The largest bounding-box extent over the finite coordinates (0.0 when there is none): numpy for host data, so a refusal that
+    depends on it needs no GPU."""
+    try:
+        if isinstance(verts, torch.Tensor):
+            v = verts.detach().reshape(-1, 3).to(torch.float32)
+            if v.shape[0] == 0:
+                return 0.0
+            fin = torch.isfinite(v)
+            lo = torch.where(fin, v, torch.full_like(v, float("inf"))).amin(0).cpu().numpy().astype(np.float64)
+            hi = torch.where(fin, v, torch.full_like(v, float("-inf"))).amax(0).cpu().numpy().astype(np.float64)
+        else:
+            v = np.asarray(verts, np.float32).reshape(-1, 3)
+            if v.shape[0] == 0:
+                return 0.0
+            fin = np.isfinite(v)
+            lo = np.where(fin, v, np.inf).min(0).astype(np.float64)
+            hi = np.where(fin, v, -np.inf).max(0).astype(np.float64)
+    except (TypeError, ValueError, RuntimeError):
+        return 0.0                                                 # not [V,3] numbers: the conversion that follows says so
+    ext = np.where(hi >= lo, hi - lo, 0.0)
+    return float(ext.max())
+
+
+def _check_grid(extent, cell):
+    if extent / cell >= CELL_LIMIT:
+        raise ValueError(f"swnerf.mesh: a cell of {cell:g} over an extent of {extent:g} needs {extent / cell:.3g} cells an axis; "
+                         f"the cell index has 21 bits (fewer than {CELL_LIMIT})")
+
+
+def default_tolerance(extent):
+    """weld()'s default cell: the largest extent x 2^-20, the finest grid the 21-bit cell index allows with a factor 2 to spare
+    (1.0 for a mesh without extent: every vertex is in one cell then, whatever its size)."""
+    t = float(np.float32(extent * 2.0 ** -20))
+    return t if np.isfinite(t) and t > 0 else 1.0
+
+
+def _simplify_workspace(V, F, device):
+    _sizes(V, F)
+    return torch.empty(int(_lib.lib().swnerf_mesh_simplify_workspace_bytes(V, F)), dtype=torch.uint8, device=device)
+
+
+def _cluster(v, cell, origin=None, ws=None):
+    """-> (vlabel int32 [V], clusters, origin float32 [3]) on v's device; reading the counts is the host synchronisation"""
+    V, dev = v.shape[0], v.device
+    if origin is not None:
+        origin = torch.as_tensor(np.asarray(origin, np.float32).reshape(3)).to(dev) if not isinstance(origin, torch.Tensor) \
+            else origin.to(dev, torch.float32).reshape(3).contiguous()
+    vlabel = torch.empty(V, dtype=torch.int32, device=dev)
+    used = torch.zeros(3, dtype=torch.float32, device=dev)
+    counts = torch.empty(3, dtype=torch.int32, device=dev)
+    ws = _simplify_workspace(V, 0, dev) if ws is None else ws
+    _lib.check(_lib.lib().swnerf_mesh_cluster(_lib.ptr(v), V, _lib.ptr(origin), cell, _lib.ptr(ws), _lib.ptr(vlabel), _lib.ptr(used),
+                                              _lib.ptr(counts), _lib.stream_of(v)), "mesh_cluster")
+    n, invalid, full = (int(x) for x in counts.cpu())
+    if invalid:
+        raise ValueError(f"swnerf.mesh: {invalid} vertices have no cell: a coordinate is not finite, or lies below the origin or "
+                         f"2^21 cells of {cell:g} or more above it")
+    if full:
+        raise RuntimeError("swnerf.mesh: the cell table overflowed (it holds at least 2 V slots: this is a bug)")
+    return vlabel, n, used
+
+
+def _collapse(f, vlabel, V, ws=None):
+    """-> (vmap int32 [V+1], fpos int32 [F+1], (V', F', degenerate, duplicate)); reading the counts is the host synchronisation"""
+    F, dev = f.shape[0], f.device
+    vmap = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    fpos = torch.empty(F + 1, dtype=torch.int32, device=dev)
+    counts = torch.empty(5, dtype=torch.int32, device=dev)
+    ws = _simplify_workspace(V, F, dev) if ws is None else ws
+    _lib.check(_lib.lib().swnerf_mesh_collapse(_lib.ptr(f), _lib.ptr(vlabel), V, F, _lib.ptr(ws), _lib.ptr(vmap), _lib.ptr(fpos),
+                                               _lib.ptr(counts), _lib.stream_of(f)), "mesh_collapse")
+    c = [int(x) for x in counts.cpu()]
+    _bad(c[4])
+    return vmap, fpos, tuple(c[:4])
+
+
+def cluster(verts, cell, origin=None):
+    """-> (vlabel int32 [V] device tensor, number of clusters): vlabel[v] is the smallest vertex index in v's cell of the uniform
+    grid of size `cell` at `origin` (default: the per-axis minimum of the vertices, found on the device).  In fp64 the cell index is
+    floor((p - origin) / cell) per axis; a vertex whose index is not in [0, 2^21) on every axis - a NaN among them - raises
+    ValueError naming how many there are."""
+    c = _check_cell(cell)
+    _check_grid(_extent(verts), c)
+    v = _rows3(verts, "verts")
+    vlabel, n, _ = _cluster(v, c, origin)
+    return vlabel, n
+
+
+def collapse_counts(verts, faces, cell, origin=None):
+    """-> dict(vertices, faces, degenerate, duplicate, clusters): what simplify_arrays would leave at this cell size, from the
+    cluster and collapse phases alone (nothing is emitted)."""
+    c = _check_cell(cell)
+    _check_grid(_extent(verts), c)
+    v = _rows3(verts, "verts")
+    f = _faces(faces, v.device).to(v.device)
+    ws = _simplify_workspace(v.shape[0], f.shape[0], v.device)
+    vlabel, n, _ = _cluster(v, c, origin, ws)
+    _, _, (Vo, Fo, ndeg, ndup) = _collapse(f, vlabel, v.shape[0], ws)
+    return dict(vertices=Vo, faces=Fo, degenerate=ndeg, duplicate=ndup, clusters=n)
+
+
+def simplify_arrays(verts, faces, normals=None, colors=None, cell=1., placement="quadric", eps=1e-3, origin=None):
+    """Vertex clustering on device tensors -> (verts', faces', normals' or None, colors' or None): cluster on the grid of size
+    `cell`, send every face through the clustering (degenerate faces and duplicates go; the survivors keep their order and their
+    corner order), and place one vertex per remaining cluster ('weld': the cluster's smallest vertex, bit for bit; 'mean'; 'quadric':
+    Lindstrom's volume-keeping point inside the cell).  Normals are copied by 'weld' and recomputed (area-weighted) by the other
+    two when normals came in."""
+    c = _check_cell(cell)
+    _check_placement(placement, eps)
+    _check_grid(_extent(verts), c)
+    v = _rows3(verts, "verts")
+    f = _faces(faces, v.device).to(v.device)
+    n = None if normals is None else _rows3(normals, "normals", like=v)
+    col = None if colors is None else _rows3(colors, "colors", like=v)
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    ws = _simplify_workspace(V, F, dev)
+    vlabel, _, used = _cluster(v, c, origin, ws)
+    vmap, fpos, (Vo, Fo, _, _) = _collapse(f, vlabel, V, ws)
+    vo = torch.empty((Vo, 3), dtype=torch.float32, device=dev)
+    fo = torch.empty((Fo, 3), dtype=torch.int32, device=dev)
+    copy_normals = n is not None and placement == "weld"
+    no = torch.empty_like(vo) if copy_normals else None
+    co = torch.empty_like(vo) if col is not None else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().swnerf_mesh_collapse_emit(_lib.ptr(v), _lib.ptr(f), _lib.ptr(n) if copy_normals else None, _lib.ptr(col),
+                                                    _lib.ptr(vlabel), _lib.ptr(vmap), _lib.ptr(fpos), _lib.ptr(used), c, V, F,
+                                                    PLACEMENTS[placement], float(eps), _lib.ptr(ws), Vo, Fo, _lib.ptr(vo), _lib.ptr(fo),
+                                                    _lib.ptr(no), _lib.ptr(co), _lib.ptr(status), _lib.stream_of(v)), "mesh_collapse_emit")
+    _bad(int(status.cpu()))
+    if n is not None and not copy_normals:
+        no = vertex_normals(vo, fo)
+    return vo, fo, no, co
+
+
+def weld_arrays(verts, faces, normals=None, colors=None, tolerance=None):
+    """weld() on device tensors -> (verts, faces, normals, colors)"""
+    tol = default_tolerance(_extent(verts)) if tolerance is None else _check_cell(tolerance, "tolerance")
+    return simplify_arrays(verts, faces, normals, colors, tol, "weld")
+
+
+def weld(m, tolerance=None, faces=None):
+    """Merge coincident vertices (trimesh's process=True): the vertices of one cell of a grid of size `tolerance` become the
+    smallest-indexed of them, faces that collapse or repeat go, unreferenced vertices go -> Mesh.  The default tolerance is the
+    largest bounding-box extent x 2^-20.  Like trimesh's rounding merge this is a grid merge, not a distance merge: two vertices
+    closer than the tolerance that straddle a cell boundary stay apart."""
+    from . import mesh as _mesh
+    tol = None if tolerance is None else _check_cell(tolerance, "tolerance")
+    raw = _raw(m, faces)
+    ext = _extent(raw if faces is not None else raw[0])
+    tol = default_tolerance(ext) if tol is None else tol
+    _check_grid(ext, tol)
+    return _mesh._to_mesh(_filled(weld_arrays(*as_arrays(raw, faces), tolerance=tol)))
+
+
+def _filled(out):
+    """Mesh wants normals: area-weighted ones when none came in"""
+    v, f, n, c = out
+    return v, f, vertex_normals(v, f) if n is None else n, c
+
+
+def _decimation_cell(v, f, N, extent):
+    if not extent > 0:
+        return 1.0                                                 # one cell whatever its size: no face survives
+    ws = _simplify_workspace(v.shape[0], f.shape[0], v.device)
+
+    def faces_at(x):
+        h = _check_cell(2.0 ** x)
+        vlabel, _, _ = _cluster(v, h, None, ws)
+        return _collapse(f, vlabel, v.shape[0], ws)[2][1]
+
+    hi = float(np.log2(extent))
+    lo = hi - 20.0
+    if faces_at(hi) > N:
+        raise ValueError(f"swnerf.mesh.decimate: even one cell of the mesh's extent leaves more than target_faces = {N} faces")
+    if faces_at(lo) <= N:
+        return _check_cell(2.0 ** lo)
+    for _ in range(24):
+        mid = 0.5 * (lo + hi)
+        if faces_at(mid) <= N:
+            hi = mid
+        else:
+            lo = mid
+    return _check_cell(2.0 ** hi)
+
+
+def decimation_cell(m, target_faces, faces=None):
+    """The cell size decimate(m, target_faces=N) uses: log2 of the cell is bisected in 24 steps between the largest bounding-box
+    extent x 2^-20 and the extent itself, keeping faces(hi) <= N < faces(lo), and the upper end is returned (the lower end when
+    even the finest grid leaves at most N faces).  Each probe runs the cluster and collapse phases only.  ValueError when a single
+    cell of the extent still leaves more than N faces."""
+    _, N = _check_decimate(None, target_faces, "quadric", 1e-3)
+    raw = _raw(m, faces)
+    ext = _extent(raw if faces is not None else raw[0])
+    v, f, _, _ = as_arrays(raw, faces)
+    return _decimation_cell(v, f, N, ext)
+
+
+def decimate_arrays(verts, faces, normals=None, colors=None, cell=None, target_faces=None, placement="quadric", eps=1e-3):
+    """decimate() on device tensors -> (verts, faces, normals, colors); with target_faces >= F the input tensors themselves"""
+    cell, N = _check_decimate(cell, target_faces, placement, eps)
+    if N is not None:
+        if len(faces) <= N:
+            return verts, faces, normals, colors
+        v = _rows3(verts, "verts")
+        cell = _decimation_cell(v, _faces(faces, v.device).to(v.device), N, _extent(verts))
+    return simplify_arrays(verts, faces, normals, colors, cell, placement, eps)
+
+
+def decimate(m, cell=None, target_faces=None, placement="quadric", eps=1e-3, faces=None):
+    """Decimate by vertex clustering -> Mesh: one vertex per occupied cell of a grid of size `cell` (or of decimation_cell(m,
+    target_faces), which leaves at most target_faces faces; a mesh that already has no more is returned unchanged).  placement:
+    'quadric' (the default: the point that keeps the cluster's faces' planes, and with them the volume), 'mean' or 'weld'; eps is
+    the quadric's regularisation toward the mean.  Fully parallel and bit-reproducible; exactly one of cell and target_faces."""
+    from . import mesh as _mesh
+    cell, N = _check_decimate(cell, target_faces, placement, eps)
+    raw = _raw(m, faces)
+    if cell is not None:
+        _check_grid(_extent(raw if faces is not None else raw[0]), cell)
+    v, f, n, c = as_arrays(raw, faces)
+    if N is not None and f.shape[0] <= N:
+        return _mesh._to_mesh(_filled((v, f, n, c)))
+    return _mesh._to_mesh(_filled(decimate_arrays(v, f, n, c, cell, N, placement, eps)))
+
+
+_DECIMATE_KEYS = {"cell", "target_faces", "placement", "eps"}
+
+
+def _check_clean_extras(weld, decimate):
+    """-> (weld tolerance or None when weld is True, decimate keywords), both checked; no GPU"""
+    if not (weld is None or weld is False or weld is True):
+        weld = _check_cell(weld, "weld")
+    if decimate is not None:
+        if not isinstance(decimate, dict) or set(decimate) - _DECIMATE_KEYS:
+            raise TypeError(f"swnerf.mesh: decimate must be None or a dict of decimate()'s keywords {sorted(_DECIMATE_KEYS)}, got {decimate!r}")
+        _check_decimate(decimate.get("cell"), decimate.get("target_faces"), decimate.get("placement", "quadric"), decimate.get("eps", 1e-3))
+    return weld, decimate
+
+
 # --------------------------------------------------------------------------------------------------------------------- clean
-def clean_arrays(verts, faces, normals=None, colors=None, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53):
+def clean_arrays(verts, faces, normals=None, colors=None, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53, weld=None,
+                 decimate=None):
     """clean() on device tensors -> (verts, faces, normals, colors) device tensors; the normals are recomputed iff smoothing ran
-    (and when none came in)."""
+    (and when none came in).  weld (None, True or a tolerance) is applied first, decimate (None or a dict of decimate()'s
+    keywords) after the component selection and before the smoothing."""
     _check_smoothing(smooth_iterations, lam, mu)
+    weld, decimate = _check_clean_extras(weld, decimate)
+    if weld is not None and weld is not False:
+        verts, faces, normals, colors = weld_arrays(verts, faces, normals, colors, None if weld is True else weld)
     v, f, n, c, _ = keep_components(verts, faces, normals, colors, keep, min_faces)
+    if decimate is not None:
+        v, f, n, c = decimate_arrays(v, f, n, c, **decimate)
     if smooth_iterations > 0 or n is None:
         inc = vertex_faces(f, v.shape[0])
         if smooth_iterations > 0:
@@ -313,17 +608,21 @@ def clean_options(clean):
         return {}
     if not isinstance(clean, dict):
         raise TypeError(f"swnerf.mesh: clean must be None, True or a dict of clean()'s keywords, got {type(clean).__name__}")
-    extra = set(clean) - {"keep", "min_faces", "smooth_iterations", "lam", "mu"}
+    extra = set(clean) - {"keep", "min_faces", "smooth_iterations", "lam", "mu", "weld", "decimate"}
     if extra:
         raise TypeError(f"swnerf.mesh: unknown clean option(s) {sorted(extra)}")
+    _check_clean_extras(clean.get("weld"), clean.get("decimate"))
     return dict(clean)
 
 
-def clean(m, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53):
-    """Remove floaters and (optionally) the marching-cubes staircase: components -> the `keep` largest of at least `min_faces`
-    faces -> compaction -> `smooth_iterations` of Taubin smoothing -> Mesh.  Vertex normals are recomputed iff smoothing ran."""
+def clean(m, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53, weld=None, decimate=None):
+    """Remove floaters and (optionally) the marching-cubes staircase: [weld ->] components -> the `keep` largest of at least
+    `min_faces` faces -> compaction [-> decimate] -> `smooth_iterations` of Taubin smoothing -> Mesh.  weld: None, True (the default
+    tolerance of weld()) or a tolerance; decimate: None or a dict of decimate()'s keywords.  Vertex normals are recomputed iff
+    smoothing or a 'mean' / 'quadric' decimation ran."""
     from . import mesh as _mesh
     _check_selection(keep, min_faces)
     _check_smoothing(smooth_iterations, lam, mu)
+    _check_clean_extras(weld, decimate)
     v, f, n, c = as_arrays(m)
-    return _mesh._to_mesh(clean_arrays(v, f, n, c, keep, min_faces, smooth_iterations, lam, mu))
+    return _mesh._to_mesh(clean_arrays(v, f, n, c, keep, min_faces, smooth_iterations, lam, mu, weld, decimate))
