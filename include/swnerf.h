@@ -950,6 +950,54 @@ int     swnerf_mesh_collapse_emit(const float* verts, const int32_t* faces, cons
                                   void* workspace, int64_t V_out, int64_t F_out, float* verts_out, int32_t* faces_out,
                                   float* normals_out, float* colors_out, int32_t* status, void* stream);
 
+/* ---- mesh hole filling: boundary loops and fan caps (trimesh's fill_holes; csrc/meshops_math.h, meshops_kernels.hip, DESIGN.md 6b
+ * "Hole filling"; tests/meshfill_ref.py is the numpy replay) -------------------------------------------------------------------
+ * This block was added without a step of SWNERF_VERSION: it only adds entry points, nothing above changes, and the version is
+ * what a binding compares against the library it loads, where a missing symbol is an error of its own.
+ * The same conventions as above (nothing allocated, no host synchronisation, one launch per phase, integer atomics only, nothing
+ * depends on scheduling), with a workspace of its own: swnerf_mesh_fill_workspace_bytes of (V, F) bytes (0 for refused sizes, else
+ * a multiple of 256; every phase starts at its first byte).  The inputs are never written.
+ * Half-edge c = 3 f + k runs from faces[f][k] (tail) to faces[f][(k+1)%3] (head).  It is a boundary half-edge iff tail != head and
+ *   its undirected edge occurs exactly once over all faces: their number is mesh_measure's boundary-edge count (which has no
+ *   tail != head clause: it also counts the edge x - x of a face that repeats an index, when that occurs once).
+ * A vertex is simple iff exactly one boundary half-edge leaves it and exactly one enters it.  next(c) is the boundary half-edge
+ *   leaving head(c), defined iff that head is simple.  A loop is a cycle of next (n >= 3 always); its leader is its smallest
+ *   half-edge id, which has rank 0, and ranks follow next; p_r is the tail of the rank-r half-edge.  Boundary half-edges on no
+ *   cycle (a bow-tie, a chain through a pinched vertex) are unfillable: counted, never touched.
+ * mesh_boundary: builds the corner list of every vertex in the workspace (unsorted: an edge's occurrences are counted from the
+ *   shorter list of its two end points, whatever their order) and classifies every half-edge.  bhe int32 [3F] (capacity; the first
+ *   nb are written) = the boundary half-edges in ascending order; bnext int32 [3F] likewise = next as an index into bhe, or -1.
+ *   counts int32 [2] = {nb, bad indices}.  A face index outside 0..V-1 is counted by the first kernel that reads `faces` and never
+ *   followed; then nb = 0 and nothing else is written.  V = 0 or F = 0: counts = {0, 0}.  6 memsets and 11 launches.
+ * mesh_boundary_loops: nb = counts[0] of mesh_boundary.  Pointer jumping over bnext between two buffers, one launch per round,
+ *   ceil(log2 nb) rounds carrying (jump target, smallest id seen): every element of a cycle ends with its leader, every element of
+ *   a chain with "none".  Each cycle is cut in front of its leader and the same rounds run again carrying the distance to the end,
+ *   which gives the ranks.  2 ceil(log2 nb) + 16 launches whatever the loops' lengths.  Loops are numbered in ascending leader
+ *   order.  table int32 [nb/3, 2] (capacity; L rows written) = (leader, n); loop_offsets int32 [nb/3 + 1] (L + 1 written) and
+ *   loop_vertices int32 [nb] (loop_offsets[L] written) = the CSR of p_0 .. p_{n-1} per loop.  A loop is filled iff max_edges == 0
+ *   or n <= max_edges (max_edges 0 or >= 3); loop_vnew / loop_fnew int32 [nb/3 + 1] = the exclusive scans of "gets a new vertex"
+ *   (filled and n >= 4) and of the new faces (1 for n == 3, else n), so the totals stand at [L].  counts int32 [8] = {L, listed
+ *   vertices, filled loops, filled edges, new vertices, new faces, 0, 0}.  nb = 0: counts = 0 and the three [0] entries are 0.
+ * mesh_fill_emit: L, M = counts[0], counts[1]; V_out = V + new vertices, F_out = F + new faces.  The first V rows of verts_out
+ *   (colors_out when colors is given) and the first F of faces_out are the inputs, bit for bit.  Loop i with a new vertex gets row
+ *   V + loop_vnew[i]; its new faces follow from row F + loop_fnew[i] in rank order: n == 3 adds the one face (p_1, p_0, p_2) and no
+ *   vertex, n >= 4 the fan (p_{(r+1) % n}, p_r, new vertex) for r = 0 .. n-1.  Every new face holds the reverse of a boundary
+ *   half-edge, so the winding continues the surface.  The new vertex is, per coordinate, the fp64 sum of p_0 .. p_{n-1} taken as
+ *   partial sums over consecutive runs of 64 ranks (each added in rank order from 0.0), the partial sums added in run order from
+ *   0.0, divided by (double)n and rounded once to float32; colours likewise.  The partial sums are one thread each, parallel over
+ *   the runs; one thread per loop adds them.  Normals are not written (mesh_incidence + mesh_vertex_normals on the output).
+ *   status int32 [1] = entries of loop_vertices outside 0..V-1 (never followed).  Rows past V_out / F_out are never written. */
+int64_t swnerf_mesh_fill_workspace_bytes(int64_t V, int64_t F);
+int     swnerf_mesh_boundary(const int32_t* faces, int64_t V, int64_t F, void* workspace, int32_t* bhe, int32_t* bnext, int32_t* counts,
+                             void* stream);
+int     swnerf_mesh_boundary_loops(const int32_t* faces, const int32_t* bhe, const int32_t* bnext, int64_t V, int64_t F, int64_t nb,
+                                   int64_t max_edges, void* workspace, int32_t* table, int32_t* loop_offsets, int32_t* loop_vertices,
+                                   int32_t* loop_vnew, int32_t* loop_fnew, int32_t* counts, void* stream);
+int     swnerf_mesh_fill_emit(const float* verts, const int32_t* faces, const float* colors /* may be NULL */, int64_t V, int64_t F,
+                              const int32_t* loop_offsets, const int32_t* loop_vertices, const int32_t* loop_vnew,
+                              const int32_t* loop_fnew, int64_t L, int64_t M, void* workspace, int64_t V_out, int64_t F_out,
+                              float* verts_out, int32_t* faces_out, float* colors_out, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

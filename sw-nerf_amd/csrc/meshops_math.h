@@ -1,7 +1,8 @@
 // meshops_math.h - the per-vertex, per-face and per-cluster arithmetic of mesh clean-up, measurement, welding and decimation,
 // written once for the device kernels (meshops_kernels.hip) and for plain host C++ (g++ compiles this header;
-// tests/meshops_host_main.cpp, tests/meshsimp_host_main.cpp).  DESIGN.md 6b "Clean-up and measurement" and "Welding and decimation"
-// state the definitions; tests/meshops_ref.py and tests/meshsimp_ref.py replay them in numpy.
+// tests/meshops_host_main.cpp, tests/meshsimp_host_main.cpp, tests/meshfill_host_main.cpp).  DESIGN.md 6b "Clean-up and measurement",
+// "Welding and decimation" and "Hole filling"
+// state the definitions; tests/meshops_ref.py, tests/meshsimp_ref.py and tests/meshfill_ref.py replay them in numpy.
 // Everything is fp64 on float32 inputs, one rounding per operation (both builds use -ffp-contract=off) and a fixed order of
 // additions, so every result is a pure function of the inputs: the same bits on the device, on the host and in the replay.
 // A corner id is c = 3 f + k: vertex k of face f.  An incidence slice lists the corners at one vertex in ascending order.
@@ -282,3 +283,57 @@ MESHOPS_HD void meshops_place_vertex(int placement, const float* P, const float*
         for (int k = 0; k < 3; ++k) col[k] = (float)m[k];
     }
 }
+
+// ---- hole filling (DESIGN.md 6b "Hole filling"; tests/meshfill_ref.py replays it) ------------------------------------------------
+#define MESHOPS_FILL_RUN 64            // ranks per partial sum of a new vertex
+
+// Is the half-edge c = 3 f + k (faces[f][k] -> faces[f][(k+1)%3]) a boundary half-edge: tail != head and its undirected edge occurs
+// exactly once over all faces (measure's boundary edge).  The shorter of the two incidence slices is scanned.  false when an end
+// point is outside 0..V-1: it is compared, never followed.
+MESHOPS_HD bool meshops_boundary_halfedge(const int32_t* faces, const int32_t* offsets, const int32_t* items, int32_t c, int64_t V, int64_t F) {
+    const int32_t f = c / 3, k = c - 3 * f;
+    const int32_t a = faces[c], b = faces[3 * f + (k + 1) % 3];
+    if (a == b || !meshops_index_ok(a, V) || !meshops_index_ok(b, V)) return false;
+    const bool from_a = offsets[a + 1] - offsets[a] <= offsets[b + 1] - offsets[b];
+    const int32_t x = from_a ? a : b, y = from_a ? b : a;
+    const MeshopsEdge e = meshops_edge_scan(faces, items, offsets[x], offsets[x + 1], x, y, F);
+    return e.n_xy + e.n_yx == 1;
+}
+
+// The new face of rank r of a loop p[0 .. n) (n >= 3): n == 3 has the single face (p1, p0, p2) at r == 0; n >= 4 has the fan faces
+// (p[(r+1)%n], p[r], newv).  Each holds the reverse of a boundary half-edge, so the winding continues the surface.
+MESHOPS_HD void meshops_fill_face(const int32_t* p, int32_t n, int32_t r, int32_t newv, int32_t out[3]) {
+    out[0] = p[r + 1 < n ? r + 1 : 0];
+    out[1] = p[r];
+    out[2] = n == 3 ? p[2] : newv;
+}
+
+// fp64 sum of the rows A[p[lo .. hi)] added in that order from 0.0 (one run of a blocked mean); an index outside 0..V-1 is skipped
+MESHOPS_HD void meshops_run_sum(const float* A, const int32_t* p, int32_t lo, int32_t hi, int64_t V, double s[3]) {
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int32_t q = lo; q < hi; ++q) {
+        const int32_t v = p[q];
+        if (!meshops_index_ok(v, V)) continue;
+        sx += (double)A[3 * (int64_t)v];
+        sy += (double)A[3 * (int64_t)v + 1];
+        sz += (double)A[3 * (int64_t)v + 2];
+    }
+    s[0] = sx; s[1] = sy; s[2] = sz;
+}
+
+// The blocked mean of n rows from the sums of its ceil(n / 64) runs (part[3 q ..], run order): added in that order from 0.0, divided
+// by n, rounded once to float32
+MESHOPS_HD void meshops_blocked_mean(const double* part, int32_t nruns, int32_t n, float out[3]) {
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int32_t q = 0; q < nruns; ++q) {
+        sx += part[3 * (int64_t)q];
+        sy += part[3 * (int64_t)q + 1];
+        sz += part[3 * (int64_t)q + 2];
+    }
+    const double d = (double)n;
+    out[0] = (float)(sx / d); out[1] = (float)(sy / d); out[2] = (float)(sz / d);
+}
+
+// The slot of run k of loop li (its vertices start at offset off of the loop-ordered list) in a partial-sum array: strictly
+// increasing over (li, k), below M / 64 + L + 1 for M listed vertices in L loops
+MESHOPS_HD int64_t meshops_fill_slot(int64_t off, int64_t li, int64_t k) { return off / MESHOPS_FILL_RUN + li + k; }

@@ -15,7 +15,8 @@ DirectTemporalNeRF (deformation net, gamma(x + dx), canonical trunk once per poi
 Clean-up and measurement of the extracted mesh (connected components, Taubin smoothing, normals, area / volume / extents) are in
 swnerf.meshops and re-exported here: `components`, `keep_components`, `vertex_faces`, `smooth`, `vertex_normals`, `measure`,
 `clean`, and the `clean=` keyword of `generate_mesh` / `nerf_to_mesh`; so are welding and decimation by vertex clustering:
-`cluster`, `weld`, `decimate`, `decimation_cell` (and the `weld` / `decimate` keys of `clean`)."""
+`cluster`, `weld`, `decimate`, `decimation_cell` (and the `weld` / `decimate` keys of `clean`), and hole filling: `boundary_loops`,
+`fill_holes` (and the `fill_holes` key of `clean`)."""
 import ctypes
 
 import numpy as np
@@ -342,4 +343,4 @@ def mesh_sequence(net, bounds, times, resolution=64, density_threshold=8, num_vi
 
 from .meshops import (components, select_components, keep_components, vertex_faces, smooth_step, smooth, vertex_normals,  # noqa: E402,F401
                       measure, measure_raw, clean, Measurement, cluster, collapse_counts, weld, decimate, decimation_cell,
-                      simplify_arrays, weld_arrays, decimate_arrays)
+                      simplify_arrays, weld_arrays, decimate_arrays, boundary_loops, fill_holes, fill_holes_arrays)

@@ -14,6 +14,8 @@ include/swnerf.h; csrc/meshops_kernels.hip, meshops_math.h); `swnerf.mesh` re-ex
   weld(mesh, tolerance)               merge the vertices of one cell (trimesh's process=True); degenerate / duplicate faces go
   decimate(mesh, cell | target_faces) vertex clustering with a quadric (volume-keeping), mean or weld representative per cell
   decimation_cell(mesh, target_faces) the cell size that leaves at most target_faces faces (bisection of log2 cell)
+  boundary_loops(faces, n_vertices)   the boundary as loops: (leader half-edge, length) table and the loop-ordered vertex lists
+  fill_holes(mesh, max_edges)         close every boundary loop with a face or a fan around its mean (trimesh's fill_holes)
 
 A mesh argument is a `Mesh`, the 4-tuple of `marching_cubes`, an OBJ path, or verts and faces (tensors or arrays); host data is
 uploaded.  A face index outside 0..V-1 raises ValueError naming how many there are; it is never dereferenced."""
@@ -564,11 +566,121 @@ def decimate(m, cell=None, target_faces=None, placement="quadric", eps=1e-3, fac
     return _mesh._to_mesh(_filled(decimate_arrays(v, f, n, c, cell, N, placement, eps)))
 
 
+# -------------------------------------------------------------------------------------------------------------- hole filling
+INFO_KEYS = ("boundary_edges", "loops", "filled_loops", "filled_edges", "skipped_loops", "unfillable_edges", "new_vertices", "new_faces")
+
+
+def _check_max_edges(max_edges, what="max_edges"):
+    """-> max_edges as the kernels take it (0: no limit); no GPU"""
+    if max_edges is None:
+        return 0
+    if not (isinstance(max_edges, (int, np.integer)) and not isinstance(max_edges, bool) and 3 <= max_edges < 2 ** 31):
+        raise ValueError(f"swnerf.mesh: {what} must be None or an integer >= 3 (a loop has at least 3 edges), got {max_edges!r}")
+    return int(max_edges)
+
+
+def _check_fill(fill_holes):
+    """clean()'s fill_holes: None / False -> None, True -> 0 (no limit), an integer >= 3 -> itself; no GPU"""
+    if fill_holes is None or fill_holes is False:
+        return None
+    return 0 if fill_holes is True else _check_max_edges(fill_holes, "fill_holes")
+
+
+def _fill_workspace(V, F, device):
+    _sizes(V, F)
+    return torch.empty(int(_lib.lib().swnerf_mesh_fill_workspace_bytes(V, F)), dtype=torch.uint8, device=device)
+
+
+def _loops(f, V, max_edges, ws):
+    """boundary and loops phases -> (table, loop_offsets, loop_vertices, loop_vnew, loop_fnew, info); the device tensors are cut to
+    the L loops found.  Reading the counts after each phase is the host synchronisation."""
+    F, dev = f.shape[0], f.device
+    L_, st = _lib.lib(), _lib.stream_of(f)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    nb = 0
+    if V > 0 and F > 0:
+        bhe, bnext, counts = i32(3 * F), i32(3 * F), i32(2)
+        _lib.check(L_.swnerf_mesh_boundary(_lib.ptr(f), V, F, _lib.ptr(ws), _lib.ptr(bhe), _lib.ptr(bnext), _lib.ptr(counts), st), "mesh_boundary")
+        nb, bad = (int(x) for x in counts.cpu())
+        _bad(bad)
+    cap = nb // 3
+    table, loop_offsets, loop_vertices, vnew, fnew, counts = i32(cap, 2), i32(cap + 1), i32(nb), i32(cap + 1), i32(cap + 1), i32(8)
+    if nb > 0:
+        _lib.check(L_.swnerf_mesh_boundary_loops(_lib.ptr(f), _lib.ptr(bhe), _lib.ptr(bnext), V, F, nb, max_edges, _lib.ptr(ws), _lib.ptr(table),
+                                                 _lib.ptr(loop_offsets), _lib.ptr(loop_vertices), _lib.ptr(vnew), _lib.ptr(fnew),
+                                                 _lib.ptr(counts), st), "mesh_boundary_loops")
+        L, M, nfill, efill, Vn, Fn = (int(x) for x in counts[:6].cpu())
+    else:
+        L = M = nfill = efill = Vn = Fn = 0
+        for t in (loop_offsets, vnew, fnew):
+            t.zero_()
+    info = dict(boundary_edges=nb, loops=L, filled_loops=nfill, filled_edges=efill, skipped_loops=L - nfill, unfillable_edges=nb - M,
+                new_vertices=Vn, new_faces=Fn)
+    return table[:L], loop_offsets[:L + 1], loop_vertices[:M], vnew[:L + 1], fnew[:L + 1], info
+
+
+def boundary_loops(faces, n_vertices):
+    """The boundary of a mesh as loops -> (table int64 numpy [L,2], loop_offsets int32 [L+1], loop_vertices int32 device tensors, info).
+    Half-edge c = 3 f + k runs faces[f][k] -> faces[f][(k+1)%3]; it is a boundary half-edge when its edge occurs once over all faces.
+    A loop is a cycle of boundary half-edges through vertices with exactly one entering and one leaving; table row i is (its
+    smallest half-edge id, its length), rows ascending, and loop_vertices[loop_offsets[i]:loop_offsets[i+1]] are its vertices in
+    order from that half-edge's tail (index them into verts for perimeters).  info: boundary_edges, loops, unfillable_edges
+    (boundary half-edges on no loop: a bow-tie, a chain through a pinched vertex) and the fill counts without a length limit."""
+    V = int(n_vertices)
+    if V < 0:
+        raise ValueError(f"swnerf.mesh.boundary_loops: n_vertices must be >= 0, got {V}")
+    f = _faces(faces)
+    table, loop_offsets, loop_vertices, _, _, info = _loops(f, V, 0, _fill_workspace(V, f.shape[0], f.device))
+    return table.cpu().numpy().astype(np.int64), loop_offsets, loop_vertices, info
+
+
+def fill_holes_arrays(verts, faces, normals=None, colors=None, max_edges=None):
+    """fill_holes() on device tensors -> (verts, faces, normals or None, colors or None, info).  The input rows come first, bit for
+    bit; new vertices and faces follow in ascending leader order.  Normals are recomputed (area-weighted) when normals came in and
+    anything was added; when nothing was added the input tensors themselves are returned."""
+    me = _check_max_edges(max_edges)
+    v = _rows3(verts, "verts")
+    f = _faces(faces, v.device).to(v.device)
+    n = None if normals is None else _rows3(normals, "normals", like=v)
+    c = None if colors is None else _rows3(colors, "colors", like=v)
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    ws = _fill_workspace(V, F, dev)
+    _, loop_offsets, loop_vertices, vnew, fnew, info = _loops(f, V, me, ws)
+    if info["new_faces"] == 0:
+        return v, f, n, c, info
+    Vo, Fo = V + info["new_vertices"], F + info["new_faces"]
+    _sizes(Vo, Fo)
+    vo = torch.empty((Vo, 3), dtype=torch.float32, device=dev)
+    fo = torch.empty((Fo, 3), dtype=torch.int32, device=dev)
+    co = torch.empty_like(vo) if c is not None else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().swnerf_mesh_fill_emit(_lib.ptr(v), _lib.ptr(f), _lib.ptr(c), V, F, _lib.ptr(loop_offsets), _lib.ptr(loop_vertices),
+                                                _lib.ptr(vnew), _lib.ptr(fnew), info["loops"], loop_vertices.shape[0], _lib.ptr(ws), Vo, Fo,
+                                                _lib.ptr(vo), _lib.ptr(fo), _lib.ptr(co), _lib.ptr(status), _lib.stream_of(v)), "mesh_fill_emit")
+    _bad(int(status.cpu()))
+    return vo, fo, None if n is None else vertex_normals(vo, fo), co, info
+
+
+def fill_holes(m, max_edges=None, faces=None):
+    """Close the holes of a mesh (trimesh's fill_holes) -> Mesh with the counts as `.fill_info`: every boundary loop of at most
+    max_edges edges (None: any length) gets one face when it is a triangle, else one new vertex at the mean of its vertices and a
+    fan of faces wound like the surface around it, so that measure() sees a closed surface and its volume.  For a planar loop the
+    fan gives the exact cap volume even when the loop is not convex (the triangles may then overlap).  Boundary edges through a
+    vertex with more than one entering or leaving boundary edge are left alone (fill_info['unfillable_edges'])."""
+    from . import mesh as _mesh
+    _check_max_edges(max_edges)
+    *out, info = fill_holes_arrays(*as_arrays(m, faces), max_edges=max_edges)
+    r = _mesh._to_mesh(_filled(out))
+    r.fill_info = info
+    return r
+
+
 _DECIMATE_KEYS = {"cell", "target_faces", "placement", "eps"}
 
 
-def _check_clean_extras(weld, decimate):
-    """-> (weld tolerance or None when weld is True, decimate keywords), both checked; no GPU"""
+def _check_clean_extras(weld, decimate, fill_holes=None):
+    """-> (weld tolerance or None when weld is True, decimate keywords), both checked, and fill_holes checked; no GPU"""
+    _check_fill(fill_holes)
     if not (weld is None or weld is False or weld is True):
         weld = _check_cell(weld, "weld")
     if decimate is not None:
@@ -580,17 +692,20 @@ def _check_clean_extras(weld, decimate):
 
 # --------------------------------------------------------------------------------------------------------------------- clean
 def clean_arrays(verts, faces, normals=None, colors=None, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53, weld=None,
-                 decimate=None):
+                 decimate=None, fill_holes=None):
     """clean() on device tensors -> (verts, faces, normals, colors) device tensors; the normals are recomputed iff smoothing ran
     (and when none came in).  weld (None, True or a tolerance) is applied first, decimate (None or a dict of decimate()'s
-    keywords) after the component selection and before the smoothing."""
+    keywords) after the component selection, then fill_holes (None, True or a max_edges), both before the smoothing."""
     _check_smoothing(smooth_iterations, lam, mu)
-    weld, decimate = _check_clean_extras(weld, decimate)
+    weld, decimate = _check_clean_extras(weld, decimate, fill_holes)
+    fill = _check_fill(fill_holes)
     if weld is not None and weld is not False:
         verts, faces, normals, colors = weld_arrays(verts, faces, normals, colors, None if weld is True else weld)
     v, f, n, c, _ = keep_components(verts, faces, normals, colors, keep, min_faces)
     if decimate is not None:
         v, f, n, c = decimate_arrays(v, f, n, c, **decimate)
+    if fill is not None:
+        v, f, n, c, _ = fill_holes_arrays(v, f, n, c, fill or None)
     if smooth_iterations > 0 or n is None:
         inc = vertex_faces(f, v.shape[0])
         if smooth_iterations > 0:
@@ -608,21 +723,22 @@ def clean_options(clean):
         return {}
     if not isinstance(clean, dict):
         raise TypeError(f"swnerf.mesh: clean must be None, True or a dict of clean()'s keywords, got {type(clean).__name__}")
-    extra = set(clean) - {"keep", "min_faces", "smooth_iterations", "lam", "mu", "weld", "decimate"}
+    extra = set(clean) - {"keep", "min_faces", "smooth_iterations", "lam", "mu", "weld", "decimate", "fill_holes"}
     if extra:
         raise TypeError(f"swnerf.mesh: unknown clean option(s) {sorted(extra)}")
-    _check_clean_extras(clean.get("weld"), clean.get("decimate"))
+    _check_clean_extras(clean.get("weld"), clean.get("decimate"), clean.get("fill_holes"))
     return dict(clean)
 
 
-def clean(m, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53, weld=None, decimate=None):
+def clean(m, keep=1, min_faces=1, smooth_iterations=0, lam=0.5, mu=-0.53, weld=None, decimate=None, fill_holes=None):
     """Remove floaters and (optionally) the marching-cubes staircase: [weld ->] components -> the `keep` largest of at least
-    `min_faces` faces -> compaction [-> decimate] -> `smooth_iterations` of Taubin smoothing -> Mesh.  weld: None, True (the default
-    tolerance of weld()) or a tolerance; decimate: None or a dict of decimate()'s keywords.  Vertex normals are recomputed iff
-    smoothing or a 'mean' / 'quadric' decimation ran."""
+    `min_faces` faces -> compaction [-> decimate] [-> fill_holes] -> `smooth_iterations` of Taubin smoothing -> Mesh.  weld: None,
+    True (the default tolerance of weld()) or a tolerance; decimate: None or a dict of decimate()'s keywords; fill_holes: None, True
+    or the longest loop to fill (fill_holes()'s max_edges) - the caps are smoothed with the rest.  Vertex normals are recomputed
+    iff smoothing, a 'mean' / 'quadric' decimation or a fill ran."""
     from . import mesh as _mesh
     _check_selection(keep, min_faces)
     _check_smoothing(smooth_iterations, lam, mu)
-    _check_clean_extras(weld, decimate)
+    _check_clean_extras(weld, decimate, fill_holes)
     v, f, n, c = as_arrays(m)
-    return _mesh._to_mesh(clean_arrays(v, f, n, c, keep, min_faces, smooth_iterations, lam, mu, weld, decimate))
+    return _mesh._to_mesh(clean_arrays(v, f, n, c, keep, min_faces, smooth_iterations, lam, mu, weld, decimate, fill_holes))
