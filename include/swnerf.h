@@ -905,7 +905,7 @@ int     swnerf_mesh_measure(const float* verts, const int32_t* faces, const int3
                             int64_t F, void* workspace, double* values, int64_t* counts, void* stream);
 
 /* ---- mesh welding and decimation by vertex clustering (trimesh's process=True merge and simplify_*; csrc/meshops_math.h,
- * meshops_kernels.hip, DESIGN.md 6b "Welding and decimation") -----------------------------------------------------------------
+ * meshsimp_kernels.hip, DESIGN.md 6b "Welding and decimation") ----------------------------------------------------------------
  * The same conventions as above (nothing allocated, no host synchronisation, one launch per phase, integer atomics only), with a
  * workspace of its own: swnerf_mesh_simplify_workspace_bytes of (V, F) bytes (0 for refused sizes; mesh_cluster needs that of
  * (V, 0)).  It holds an open-addressing table of 64-bit cell keys with a power-of-two capacity of at least 2 V (all ones = empty;
@@ -950,7 +950,7 @@ int     swnerf_mesh_collapse_emit(const float* verts, const int32_t* faces, cons
                                   void* workspace, int64_t V_out, int64_t F_out, float* verts_out, int32_t* faces_out,
                                   float* normals_out, float* colors_out, int32_t* status, void* stream);
 
-/* ---- mesh hole filling: boundary loops and fan caps (trimesh's fill_holes; csrc/meshops_math.h, meshops_kernels.hip, DESIGN.md 6b
+/* ---- mesh hole filling: boundary loops and fan caps (trimesh's fill_holes; csrc/meshops_math.h, meshfill_kernels.hip, DESIGN.md 6b
  * "Hole filling"; tests/meshfill_ref.py is the numpy replay) -------------------------------------------------------------------
  * This block was added without a step of SWNERF_VERSION: it only adds entry points, nothing above changes, and the version is
  * what a binding compares against the library it loads, where a missing symbol is an error of its own.

@@ -23,6 +23,7 @@
 #include "../../include/swnerf.h"
 #include "host_util.h"
 #include "marker_math.h"
+#include "par_prims.h"
 
 #define MK_THREADS 256
 #define MK_TILE 32                      // label tile side; 256 threads own 4 rows each
@@ -146,30 +147,7 @@ __global__ __launch_bounds__(MK_THREADS) void mk_threshold_kernel(const uint8_t*
     }
 }
 
-// ---- labels ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int mk_find(const int* L, int x) {
-    int l;
-    while ((l = __atomic_load_n(L + x, __ATOMIC_RELAXED)) != x) x = l;
-    return x;
-}
-
-// link the larger root to the smaller until both ends share one
-__device__ __forceinline__ void mk_union(int* L, int a, int b) {
-    for (;;) {
-        a = mk_find(L, a);
-        b = mk_find(L, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(L + b, a);                       // a < b
-        if (old == b) return;
-        b = old;
-    }
-}
-
+// ---- labels (uf_find / uf_union of par_prims.h) ------------------------------------------------------------------------
 // grid (ceil(W / 32), ceil(H / 32), n), 256 threads as 32 x 8
 __global__ __launch_bounds__(MK_THREADS) void mk_label_tile_kernel(const uint8_t* __restrict__ mask, int H, int W, int32_t* __restrict__ labels) {
     __shared__ int L[MK_TILE * MK_TILE];
@@ -188,11 +166,11 @@ __global__ __launch_bounds__(MK_THREADS) void mk_label_tile_kernel(const uint8_t
     for (int k = 0; k < 4; ++k) {
         const int r = ty + 8 * k, me = r * MK_TILE + tx;
         if (!dark[k]) continue;
-        if (tx > 0 && L[me - 1] >= 0) mk_union(L, me, me - 1);
+        if (tx > 0 && L[me - 1] >= 0) uf_union(L, me, me - 1);
         if (r > 0) {
-            if (tx > 0 && L[me - MK_TILE - 1] >= 0) mk_union(L, me, me - MK_TILE - 1);
-            if (L[me - MK_TILE] >= 0) mk_union(L, me, me - MK_TILE);
-            if (tx < MK_TILE - 1 && L[me - MK_TILE + 1] >= 0) mk_union(L, me, me - MK_TILE + 1);
+            if (tx > 0 && L[me - MK_TILE - 1] >= 0) uf_union(L, me, me - MK_TILE - 1);
+            if (L[me - MK_TILE] >= 0) uf_union(L, me, me - MK_TILE);
+            if (tx < MK_TILE - 1 && L[me - MK_TILE + 1] >= 0) uf_union(L, me, me - MK_TILE + 1);
         }
     }
     __syncthreads();
@@ -202,7 +180,7 @@ __global__ __launch_bounds__(MK_THREADS) void mk_label_tile_kernel(const uint8_t
         if (gx >= W || gy >= H) continue;
         int out = -1;
         if (dark[k]) {
-            const int root = mk_find(L, r * MK_TILE + tx);
+            const int root = uf_find(L, r * MK_TILE + tx);
             out = (gy0 + (root >> 5)) * W + blockIdx.x * MK_TILE + (root & 31);
         }
         labels[f + (int64_t)gy * W + gx] = out;
@@ -218,11 +196,11 @@ __global__ __launch_bounds__(MK_THREADS) void mk_label_border_kernel(int H, int 
         const int y = p / W, x = p - y * W;
         const bool col0 = (x & (MK_TILE - 1)) == 0, row0 = (y & (MK_TILE - 1)) == 0, col31 = (x & (MK_TILE - 1)) == MK_TILE - 1;
         if (!(col0 || row0 || col31) || L[p] < 0) continue;
-        if (col0 && x > 0 && L[p - 1] >= 0) mk_union(L, p, p - 1);
+        if (col0 && x > 0 && L[p - 1] >= 0) uf_union(L, p, p - 1);
         if (y > 0) {
-            if ((col0 || row0) && x > 0 && L[p - W - 1] >= 0) mk_union(L, p, p - W - 1);
-            if (row0 && L[p - W] >= 0) mk_union(L, p, p - W);
-            if ((col31 || row0) && x + 1 < W && L[p - W + 1] >= 0) mk_union(L, p, p - W + 1);
+            if ((col0 || row0) && x > 0 && L[p - W - 1] >= 0) uf_union(L, p, p - W - 1);
+            if (row0 && L[p - W] >= 0) uf_union(L, p, p - W);
+            if ((col31 || row0) && x + 1 < W && L[p - W + 1] >= 0) uf_union(L, p, p - W + 1);
         }
     }
 }
@@ -232,7 +210,7 @@ __global__ __launch_bounds__(MK_THREADS) void mk_label_flatten_kernel(int H, int
     const int HW = H * W;
     for (int p = blockIdx.x * MK_THREADS + threadIdx.x; p < HW; p += gridDim.x * MK_THREADS)
         if (L[p] >= 0) {
-            const int root = mk_find(L, p);
+            const int root = uf_find(L, p);
             if (root != p) __atomic_store_n(L + p, root, __ATOMIC_RELAXED);
         }
 }

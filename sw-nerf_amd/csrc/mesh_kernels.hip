@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/swnerf.h"
 #include "host_util.h"
+#include "par_prims.h"                 // block_exclusive_scan
 #define SW_MC_TABLE_QUAL static __constant__ const
 #include "mc_tables.h"
 
@@ -50,30 +51,6 @@ static McWs mc_ws(void* ws, const McGrid& g) {
     w.tv = (int64_t*)p;                    p += mc_round256(8 * g.ntiles);
     w.tt = (int64_t*)p;
     return w;
-}
-
-// deterministic block-wide exclusive scan (wave prefix by shuffles, then the wave totals in order)
-template <typename T, int NT>
-__device__ __forceinline__ T block_exclusive_scan(T x, T* lds, T* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    T pre = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < NT / 64; ++q) {
-        const T s = lds[q];
-        pre += (q < w) ? s : (T)0;
-        tot += s;
-    }
-    __syncthreads();                   // lds may be reused by the next call
-    *total = tot;
-    return pre + inc - x;
 }
 
 // 5 values of one grid row from k0 on (k0 + t < nz; the others are never read): float4 + 1 when vectorised

@@ -1,5 +1,5 @@
 // meshops_math.h - the per-vertex, per-face and per-cluster arithmetic of mesh clean-up, measurement, welding and decimation,
-// written once for the device kernels (meshops_kernels.hip) and for plain host C++ (g++ compiles this header;
+// written once for the device kernels (meshops_kernels.hip, meshsimp_kernels.hip, meshfill_kernels.hip) and for plain host C++ (g++ compiles this header;
 // tests/meshops_host_main.cpp, tests/meshsimp_host_main.cpp, tests/meshfill_host_main.cpp).  DESIGN.md 6b "Clean-up and measurement",
 // "Welding and decimation" and "Hole filling"
 // state the definitions; tests/meshops_ref.py, tests/meshsimp_ref.py and tests/meshfill_ref.py replay them in numpy.

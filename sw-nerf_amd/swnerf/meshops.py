@@ -1,7 +1,7 @@
 """Mesh clean-up and measurement on the device (DESIGN.md 6b "Clean-up and measurement"): what a trimesh user does after
 nerf/extract_mesh.py and nerf/transform_mesh.py - `split()` / keep the object, `smoothed()`, then read extents, area and volume.
 All of it runs on the [V,3] float32 / [F,3] int32 arrays `mesh.marching_cubes` leaves on the GPU (swnerf_mesh_* of
-include/swnerf.h; csrc/meshops_kernels.hip, meshops_math.h); `swnerf.mesh` re-exports every name here.
+include/swnerf.h; csrc/meshops_kernels.hip, meshsimp_kernels.hip, meshfill_kernels.hip, meshops_math.h); `swnerf.mesh` re-exports every name here.
 
   components(faces, n_vertices)       vertex labels (the smallest vertex index of the component) and the (label, faces, vertices) table
   keep_components(verts, faces, ...)  the `keep` largest components of at least `min_faces` faces, compacted

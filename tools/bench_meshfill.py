@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Mesh hole filling (swnerf.meshops boundary / loops / emit, csrc/meshops_kernels.hip) on a mesh that is already on the device, in
+"""Mesh hole filling (swnerf.meshops boundary / loops / emit, csrc/meshfill_kernels.hip) on a mesh that is already on the device, in
 the manner of tools/bench_meshsimp.py, on two meshes: the unpadded R^3 noise mesh extracted by swnerf.mesh.marching_cubes (many
 short loops) and one long loop, the cone fan(n) of tests/meshops_ref.py with its faces permuted (next jumps at random).  Per phase
 - boundary (corner lists, classify, scan, compact, next), loops (pointer jumping, ranks,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Mesh welding and decimation by vertex clustering (swnerf.meshops cluster / collapse / emit, csrc/meshops_kernels.hip) on a mesh
+"""Mesh welding and decimation by vertex clustering (swnerf.meshops cluster / collapse / emit, csrc/meshsimp_kernels.hip) on a mesh
 that is already on the device, in the manner of tools/bench_meshops.py: the R^3 noise mesh extracted by
 swnerf.mesh.marching_cubes, at cells of 2 and 4 grid spacings.  Per phase - cluster (table insert and labels), collapse (corner
 lists, degenerate / duplicate faces, the two scans), emit in each placement (weld, mean, quadric; mean and quadric build their
