@@ -327,6 +327,15 @@ typedef struct swnerf_pass_args {
 
 int swnerf_render_pass(const swnerf_pass_args* args /*HOST*/, void* stream);
 
+/* swnerf_render_pass with a workspace for its deferred colour branch: view_ws = [n_rays, 64, 256] floats of scratch, or NULL
+ * (= swnerf_render_pass).  With it the pass evaluates the view layer and the rgb head only on a ray's sample 0 and on its
+ * samples with alpha != 0 - a sample with alpha == 0 enters no output with its colour - compacted into tiles of 32; without
+ * it on every sample.  Same outputs either way (bit for bit unless a colour that was left out is non-finite).
+ * Used for SWNERF_NET_CANON launches without `raw` and with n_samples <= 240; every other launch ignores it and runs as
+ * swnerf_render_pass does.  view_ws != NULL with view_ws_floats < n_rays * 64 * 256 is SWNERF_E_ARG.  Launches that may
+ * overlap (different streams) need a workspace each. */
+int swnerf_render_pass_ws(const swnerf_pass_args* args /*HOST*/, float* view_ws, int64_t view_ws_floats, void* stream);
+
 /* ---- opt-in reduced-cost precision: "bf16x3" ----------------------------------------------------------------
  * swnerf_render_pass with the MLPs on the bf16 matrix pipe: every fp32 weight and activation is split into two bf16
  * halves (hi + lo, 16 significant bits) and each product is three v_mfma_f32_32x32x16_bf16 with fp32 accumulation

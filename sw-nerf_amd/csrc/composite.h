@@ -71,6 +71,19 @@ __device__ __forceinline__ void comp_accumulate(const float& w, const float& c0,
     pa += w;
 }
 
+// The same sums in two parts, for the pass that knows a tile's colours later than its weights (render_pass.h, the deferred colour
+// branch): every sum is its own chain of additions, so the parts give the bits of the whole.
+__device__ __forceinline__ void comp_accumulate_density(const float& w, const float& z, float& pd, float& pa) {
+    pd += w * z;
+    pa += w;
+}
+__device__ __forceinline__ void comp_accumulate_colour(const float& w, const float& c0, const float& c1, const float& c2,
+                                                       float& pr, float& pg, float& pb) {
+    pr += w * comp_sigmoid(c0);
+    pg += w * comp_sigmoid(c1);
+    pb += w * comp_sigmoid(c2);
+}
+
 // the maps of `ray` from the reduced sums; every pointer may be NULL
 __device__ __forceinline__ void comp_write_maps(float pr, float pg, float pb, float pd, float pa, int white, int64_t ray,
                                                 float* rgb_map, float* disp_map, float* acc_map, float* depth_map) {

@@ -47,6 +47,7 @@ struct WStream {
     const float* ring;       // the same ring as a pointer, + lane*4 floats (for ds_read_b128)
     f32x4 a_cur;             // A operands of the CURRENT step (already read from LDS)
     const float* bias;       // LDS: this lane-half's 16 biases of the CURRENT output tile
+    const char* cont;        // wave-uniform, read by REDIR segments only: where the stream continues behind the segment
 };
 
 template <int N>
@@ -133,7 +134,7 @@ struct SideFetch {
     const char* base; unsigned voff, lds_addr;
 };
 
-template <int S, int NS, int NT, int KT, int INIT, int SK, int FK = 0>
+template <int S, int NS, int NT, int KT, int INIT, int SK, int FK = 0, bool REDIR = false>
 __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)[KT], WStream& ws, f32x16& binit, float scale,
                                           const SideStore& ss, const SideFetch& sf = SideFetch{nullptr, 0u, 0u}) {
     if constexpr (S < NS) {
@@ -163,8 +164,10 @@ __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)
         out[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], kin[kt][4 * q + 2], out[n], 0, 0, 0);
         out[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], kin[kt][4 * q + 3], out[n], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);       // ... and the refill BEHIND them (WAR on the slot)
-        // refill the slot of step S (read during step S-1) with step S + SW_RING
-        ws_dma(ws.base + (S + SW_RING) * 1024, ws.voff, ws.lds_addr + slot * 1024);
+        // refill the slot of step S (read during step S-1) with step S + SW_RING (REDIR: the steps behind the segment's end
+        // come from ws.cont, not from the bytes that follow the segment - scalar address work only)
+        if constexpr (REDIR && S + SW_RING >= NS) ws_dma(ws.cont + (S + SW_RING - NS) * 1024, ws.voff, ws.lds_addr + slot * 1024);
+        else ws_dma(ws.base + (S + SW_RING) * 1024, ws.voff, ws.lds_addr + slot * 1024);
         if constexpr (SK > 0) {
             constexpr int total = 4 * SK, every = NS / total;
             static_assert(every >= 1, "segment too short for its side stores");
@@ -187,7 +190,7 @@ __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)
             }
         }
         ws.a_cur = a_next;
-        seg_steps<S + 1, NS, NT, KT, INIT, SK, FK>(out, kin, ws, binit, scale, ss, sf);
+        seg_steps<S + 1, NS, NT, KT, INIT, SK, FK, REDIR>(out, kin, ws, binit, scale, ss, sf);
     }
 }
 
@@ -197,7 +200,9 @@ __device__ __forceinline__ void seg_steps(f32x16 (&out)[NT], const f32x16 (&kin)
 //   SEG_ZERO zeros | SEG_BIAS_SCALED the bias tile times a per-lane scalar (backward: w_alpha * d sigma)
 // SK > 0: the first SK k-tiles of `kin` are written out through `ss` while the segment runs (SideStore).
 // FK > 0: FK tiles are fetched into an LDS slot through `sf` while the segment runs (SideFetch).
-template <int NT, int KT, int INIT, int SK = 0, int FK = 0>
+// REDIR: the stream continues at ws.cont behind this segment (the ring's last SW_RING prefetches go there), so a caller can
+// leave out or repeat what follows in the blob without draining the ring (the deferred colour branch of render_pass.h).
+template <int NT, int KT, int INIT, int SK = 0, int FK = 0, bool REDIR = false>
 __device__ __forceinline__ void seg_mfma(f32x16 (&out)[NT], const f32x16 (&kin)[KT], WStream& ws, float scale = 1.f,
                                          const SideStore& ss = SideStore{nullptr, nullptr, {0.f, 0.f, 0.f, 0.f}},
                                          const SideFetch& sf = SideFetch{nullptr, 0u, 0u}) {
@@ -205,9 +210,10 @@ __device__ __forceinline__ void seg_mfma(f32x16 (&out)[NT], const f32x16 (&kin)[
     static_assert(NS % SW_RING == 0, "segment must keep the ring phase");
     f32x16 binit;
     seg_init_read<INIT>(binit, ws, 0);
-    seg_steps<0, NS, NT, KT, INIT, SK, FK>(out, kin, ws, binit, scale, ss, sf);
+    seg_steps<0, NS, NT, KT, INIT, SK, FK, REDIR>(out, kin, ws, binit, scale, ss, sf);
     if (INIT == SEG_BIAS || INIT == SEG_BIAS_SCALED) ws.bias += NT * SW_BIAS_TILE_FLOATS;
-    ws.base += NS * 1024;
+    if constexpr (REDIR) ws.base = ws.cont;
+    else ws.base += NS * 1024;
 }
 
 // ---- ReLU bit masks (training) -----------------------------------------------------------------------
@@ -408,11 +414,15 @@ __device__ __forceinline__ void tile_fetch(const float* lds_tile, int lane, f32x
 // NOHEAD: stop after layer 7 (`in` = relu(h7)); the caller applies its own head (output_linear of a net without view
 // directions, head_valu_rt).
 // TB (D-NeRF, fused passes): layer 0 of the deformation pass starts from the per-ray TIME tile lds_tb (see below).
-template <bool DNERF, bool TRAIN = false, bool XS = false, bool NOHEAD = false, bool TB = false>
+// REDIR (inference): behind layer 7 the stream continues at cont7 (wave-uniform; nullptr = at the bytes that follow, as without
+// REDIR) - how a tile that leaves out the view layer keeps the ring on the head of the next tile (render_pass.h).
+template <bool DNERF, bool TRAIN = false, bool XS = false, bool NOHEAD = false, bool TB = false, bool REDIR = false>
 __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_emb, float t, bool deform_pass, int h,
                                            f32x16 (&in)[8], f32x16 (&out)[8], float (&head)[3], WStream& ws,
                                            float* act_row = nullptr, float* mask_tile = nullptr, bool store_last = false,
-                                           f32x4* mb = nullptr, float* xs_row = nullptr, const float* lds_tb = nullptr) {
+                                           f32x4* mb = nullptr, float* xs_row = nullptr, const float* lds_tb = nullptr,
+                                           const char* cont7 = nullptr) {
+    static_assert(!REDIR || (!TRAIN && !DNERF && !NOHEAD), "the redirect serves the static inference pass");
     const int lane_ = threadIdx.x & 63;
     emb_park(lds_emb, lane_, emb);
     f32x4 mbits = {0.f, 0.f, 0.f, 0.f};
@@ -456,6 +466,10 @@ __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_em
             if (TRAIN) {
                 const SideStore ss{act_row + 256 * (l - 1), mask_tile + 256 * (l - 1), mbits};
                 seg_mfma<8, 8, SEG_BIAS, TRAIN ? 8 : 0>(out, in, ws, 1.f, ss);
+            } else if constexpr (REDIR) {
+                const char* next = ws.base + SW_STEPS_TRUNK * 1024;
+                ws.cont = (l == 7 && cont7) ? cont7 : next;
+                seg_mfma<8, 8, SEG_BIAS, 0, 0, true>(out, in, ws);
             } else {
                 seg_mfma<8, 8, SEG_BIAS>(out, in, ws);
             }
@@ -547,11 +561,13 @@ __device__ __forceinline__ void time_bias_tile(float t, int h, float* lds_tb, in
     __builtin_amdgcn_wave_barrier();
 }
 
+// REDIR: behind the view layer the stream continues at ws.cont (set by the caller), see seg_mfma.
+template <bool REDIR = false>
 __device__ __forceinline__ void canon_tail(const f32x16 (&in)[8], const float* lds_vb, float (&rgb)[3], const float* hb_rgb, WStream& ws) {
     f32x16 hv[4];
     const float* keep = ws.bias;
     ws.bias = lds_vb + (threadIdx.x & 32 ? 16 : 0);
-    seg_mfma<4, 8, SEG_BIAS>(hv, in, ws);
+    seg_mfma<4, 8, SEG_BIAS, 0, 0, REDIR>(hv, in, ws);
     ws.bias = keep;
 #pragma unroll
     for (int n = 0; n < 4; ++n)

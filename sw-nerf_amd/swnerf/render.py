@@ -187,6 +187,23 @@ def pass_args(rb, kind, packed, bands, S, out_ch, run_deform, inputs, outputs, n
     return a, out, keep
 
 
+# Workspace of the fused inference pass's deferred colour branch (include/swnerf.h swnerf_render_pass_ws): 64 rows of 256
+# floats per ray, scratch.  One grow-only tensor per (device, stream): launches on one stream run in order and may share it,
+# launches on different streams (parallel.frame_renderer) may overlap and must not.  D-NeRF launches pass none: the library
+# takes the branch for the static net alone.
+VIEW_WS_FLOATS_PER_RAY = 64 * 256
+VIEW_WS_SMAX = 240                                       # above it the pass's per-wave scratch does not fit: the library runs in line
+_VIEW_WS = {}
+
+
+def view_workspace(rb, n_rays):
+    key = (rb.device, torch.cuda.current_stream(rb.device).cuda_stream)
+    ws = _VIEW_WS.get(key)
+    if ws is None or ws.numel() < n_rays * VIEW_WS_FLOATS_PER_RAY:
+        _VIEW_WS[key] = ws = torch.empty(n_rays * VIEW_WS_FLOATS_PER_RAY, dtype=torch.float32, device=rb.device)
+    return ws
+
+
 def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand=None, noise=None, white_bkgd=False,
                 want=("rgb_map", "disp_map", "acc_map"), n_importance=0, u=None, run_deform=True, precision=None):
     """One launch of `swnerf_render_pass` (include/swnerf.h).  Returns a dict of the requested
@@ -219,7 +236,12 @@ def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand
     if terms:
         _lib.check(_lib.lib().swnerf_render_pass_x3(a, terms, _lib.stream_of(rb)), "render_pass_x3")
     else:
-        _lib.check(_lib.lib().swnerf_render_pass(a, _lib.stream_of(rb)), "render_pass")
+        # the deferred colour branch (include/swnerf.h swnerf_render_pass_ws) wherever the library takes it
+        if kind == _lib.NET_CANON and "raw" not in want and S <= VIEW_WS_SMAX and N > 0:
+            ws = view_workspace(rb, N)
+            _lib.check(_lib.lib().swnerf_render_pass_ws(a, _lib.ptr(ws), ws.numel(), _lib.stream_of(rb)), "render_pass")
+        else:
+            _lib.check(_lib.lib().swnerf_render_pass(a, _lib.stream_of(rb)), "render_pass")
     if PASS_HOOK is not None:
         PASS_HOOK("end", N, S)
     return out
