@@ -327,14 +327,21 @@ typedef struct swnerf_pass_args {
 
 int swnerf_render_pass(const swnerf_pass_args* args /*HOST*/, void* stream);
 
-/* swnerf_render_pass with a workspace for its deferred colour branch: view_ws = [n_rays, 64, 256] floats of scratch, or NULL
- * (= swnerf_render_pass).  With it the pass evaluates the view layer and the rgb head only on a ray's sample 0 and on its
- * samples with alpha != 0 - a sample with alpha == 0 enters no output with its colour - compacted into tiles of 32; without
- * it on every sample.  Same outputs either way (bit for bit unless a colour that was left out is non-finite).
+/* swnerf_render_pass with a workspace for its deferred colour branch: view_ws = view_ws_floats floats of scratch, or NULL
+ * (= swnerf_render_pass).  With it the launch evaluates the view layer and the rgb head only on a ray's sample 0 and on its
+ * samples with alpha != 0 - a sample with alpha == 0 enters no output with its colour; without it on every sample.  Three
+ * kernels on `stream`: the pass itself stashes those rows' last trunk activations in the workspace and writes every output
+ * but rgb_map; a persistent kernel runs the view layer and the rgb head on the stashed rows of the whole launch, packed 32
+ * to an MFMA segment across rays; a last one forms each ray's colour sums and writes rgb_map.  Same outputs either way
+ * (bit for bit unless a colour that was left out is non-finite).
+ * The workspace's size decides how many rows a ray can stash; a 32-sample tile whose rows are not certain to fit runs the view
+ * layer in line.  swnerf_view_ws_floats(n_rays, n_samples) is the size at which every tile stashes (n_samples rows of 257
+ * floats per ray plus bookkeeping); n_rays * 64 * 256 floats is the least accepted (about 60 rows per ray): view_ws != NULL
+ * with fewer is SWNERF_E_ARG.  view_ws must be 16-byte aligned; its contents are scratch before and after.
  * Used for SWNERF_NET_CANON launches without `raw` and with n_samples <= 240; every other launch ignores it and runs as
- * swnerf_render_pass does.  view_ws != NULL with view_ws_floats < n_rays * 64 * 256 is SWNERF_E_ARG.  Launches that may
- * overlap (different streams) need a workspace each. */
+ * swnerf_render_pass does.  Launches that may overlap (different streams) need a workspace each. */
 int swnerf_render_pass_ws(const swnerf_pass_args* args /*HOST*/, float* view_ws, int64_t view_ws_floats, void* stream);
+int64_t swnerf_view_ws_floats(int64_t n_rays, int n_samples);
 
 /* ---- opt-in reduced-cost precision: "bf16x3" ----------------------------------------------------------------
  * swnerf_render_pass with the MLPs on the bf16 matrix pipe: every fp32 weight and activation is split into two bf16

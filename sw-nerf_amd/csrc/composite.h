@@ -84,15 +84,19 @@ __device__ __forceinline__ void comp_accumulate_colour(const float& w, const flo
     pb += w * comp_sigmoid(c2);
 }
 
+// rgb_map of `ray` from the reduced colour sums and acc (the white background, ray.py:195-196) - on its own for the launch that forms
+// the colour sums in a later kernel than the density sums (render_pass.h, the deferred colour branch)
+__device__ __forceinline__ void comp_write_rgb(float pr, float pg, float pb, float pa, int white, int64_t ray, float* rgb_map) {
+    const float bg = white ? (1.f - pa) : 0.f;
+    rgb_map[ray * 3 + 0] = pr + bg;
+    rgb_map[ray * 3 + 1] = pg + bg;
+    rgb_map[ray * 3 + 2] = pb + bg;
+}
+
 // the maps of `ray` from the reduced sums; every pointer may be NULL
 __device__ __forceinline__ void comp_write_maps(float pr, float pg, float pb, float pd, float pa, int white, int64_t ray,
                                                 float* rgb_map, float* disp_map, float* acc_map, float* depth_map) {
-    if (rgb_map) {
-        const float bg = white ? (1.f - pa) : 0.f;                           // ray.py:195-196
-        rgb_map[ray * 3 + 0] = pr + bg;
-        rgb_map[ray * 3 + 1] = pg + bg;
-        rgb_map[ray * 3 + 2] = pb + bg;
-    }
+    if (rgb_map) comp_write_rgb(pr, pg, pb, pa, white, ray, rgb_map);
     if (depth_map) depth_map[ray] = pd;
     if (acc_map) acc_map[ray] = pa;
     if (disp_map) {

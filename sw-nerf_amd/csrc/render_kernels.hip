@@ -45,6 +45,8 @@ __global__ void __launch_bounds__(256, 1) query_points_kernel(QueryDev P) {
 }
 
 int sw_tnerf_render_launch(const swnerf_pass_args& a, hipStream_t st);     // tnerf_kernels.hip
+// colour_kernels.hip: phases B and C of a launch whose tiles stashed their live rows (render_pass.h, the deferred colour branch)
+int sw_colour_split_launch(const swnerf_pass_args& a, const ViewWs& vw, const float* b0, int nbias, const float* wvl, hipStream_t st);
 
 extern "C" int swnerf_render_pass_ws(const swnerf_pass_args* args, float* view_ws, int64_t view_ws_floats, void* stream) {
     static const PassAccepts accepts = {"render_pass", {SW_COLS(11) | SW_COLS(12), SW_COLS(11) | SW_COLS(12), SW_COLS(8), ~0u /* checked by its launch */},
@@ -66,14 +68,12 @@ extern "C" int swnerf_render_pass_ws(const swnerf_pass_args* args, float* view_w
     P.time_steps = (a.kind == SWNERF_NET_DNERF && P.two_pass) ? SW_STEPS_TIME : 0;
     size_t lds = SW_LDS_FIXED_FLOATS * sizeof(float);
     if ((rc = pass_resampling(accepts.name, a, P, lds))) return rc;
-    // the deferred colour branch (render_pass.h): static net, no `raw` (which needs every row's colour), and a sample count whose
-    // per-wave scratch fits; every other launch runs the view layer in line.  A launch without resampling has no per-wave
-    // scratch yet: allocate it.
+    // the deferred colour branch (render_pass.h): static net, no `raw` (which needs every row's colour) and a sample count whose
+    // bookkeeping leaves rows in the least workspace; every other launch runs the view layer in line
     if (view_ws && view_ws_floats < a.n_rays * (int64_t)SW_DEFER_WS_FLOATS)
         return sw_fail(SWNERF_E_ARG, "render_pass: view_ws holds %lld floats, %lld rays need %lld", (long long)view_ws_floats,
                        (long long)a.n_rays, (long long)(a.n_rays * (int64_t)SW_DEFER_WS_FLOATS));
-    P.view_ws = (a.kind == SWNERF_NET_CANON && !a.raw && a.n_samples <= SW_DEFER_SMAX) ? view_ws : nullptr;
-    if (P.view_ws && a.n_importance <= 0) lds += 4 * SW_DEFER_LDS_FLOATS * sizeof(float);
+    if (view_ws && a.kind == SWNERF_NET_CANON && !a.raw && a.n_samples <= SW_DEFER_SMAX) P.vw = view_ws_layout(view_ws, view_ws_floats, a.n_rays, a.n_samples);
     if (a.n_rays == 0) return 0;
     if (P.time_steps) {                          // the four waves' per-ray TIME tiles, behind everything else
         P.tb_off = (int)(lds / sizeof(float));
@@ -92,11 +92,22 @@ extern "C" int swnerf_render_pass_ws(const swnerf_pass_args* args, float* view_w
             if (rc) return rc;
         }
         hipLaunchKernelGGL(render_pass_kernel<false>, grid, block, lds, st, P);
+        // the stashed rows' colours and rgb_map (nobody reads the colours of a launch without rgb_map)
+        if (P.vw.base && a.rgb_map) {
+            if ((rc = sw_check(hipGetLastError(), "render_pass launch"))) return rc;
+            return sw_colour_split_launch(a, P.vw, P.b0, P.nbias, views_loop_ptr(a.kind, a.packed), st);
+        }
     }
     return sw_check(hipGetLastError(), "render_pass launch");
 }
 
 extern "C" int swnerf_render_pass(const swnerf_pass_args* args, void* stream) { return swnerf_render_pass_ws(args, nullptr, 0, stream); }
+
+extern "C" int64_t swnerf_view_ws_floats(int64_t n_rays, int n_samples) {
+    if (n_rays <= 0 || n_samples <= 0) return 0;
+    const int64_t full = view_ws_full(n_rays, n_samples), least = n_rays * (int64_t)SW_DEFER_WS_FLOATS;
+    return full > least ? full : least;
+}
 
 // Coarse sampling alone (nerf/run.py:355-385; API parity for the op-by-op path - the fused pass does this in
 // registers): z_vals [N,S] and, when asked, pts = o + d*z [N,S,3].  Same device functions as the fused pass.

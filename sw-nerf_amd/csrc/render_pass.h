@@ -24,27 +24,68 @@
 // ---- the deferred colour branch of the static fp32 inference pass (swnerf_render_pass_ws) ------------------------------
 // A sample's colour enters the outputs as w.c with w = alpha.T, and alpha = 1 - exp(-relu(sigma).dist) is exactly 0 for every
 // sample with sigma <= 0: the view layer and the rgb head of such a row (512 of a tile's 8192 MFMAs + the tail) are multiplied
-// by an exact zero.  With a workspace the pass evaluates them on the LIVE rows only - alpha != 0 (NaN counts), and sample 0 of
-// the ray as a canary, so that a non-finite view/rgb weight, bias or direction still reaches rgb_map - compacted over the tiles
-// of the ray:
-//   * after a tile's trunk and sigma head its live rows' h7 go to the ray's 64-row ring in the workspace, [slot 64][h 2][128]:
-//     the 128 floats lane (slot, h) holds as B operand of the view segment, contiguous, so that a stash and a reload are 32
-//     16-byte accesses off ONE per-lane address (immediate offsets; 32 separate addresses get hoisted out of the tile loop and
-//     spill); the rows' sample indices go to LDS;
-//   * a tile that starts with >= 32 rows pending runs the one view segment behind its trunk, on its own live rows where they
-//     are and, in the other lanes, on the oldest pending rows loaded in place (decided BEFORE the trunk, so that layer 7's last
-//     prefetches can go to the right place: WStream.cont); every other tile stashes and leaves the view segment out.  Behind
-//     the last tile up to two view-only turns of the loop drain the rest, a partial tile padded with copies of a pending row.
-//     Never more than 63 rows are pending behind a turn;
-//   * an evaluated row's raw colours go to LDS at its sample index (dead rows: 0); weights, depth and acc accumulate in the tile
-//     loop as ever, the colour sums in a last sweep over the tiles - the same operations in the same order, so that the outputs
-//     are the in-line path's bit for bit whenever the colours left out were finite.
-// Per-wave LDS: w[S], c[3][S], slot -> sample index [64]; S <= 240 fits SW_DEFER_LDS_FLOATS, which is the `srt` region of a
-// launch that resamples (free until wave_sample_pdf) and its own scratch otherwise.
+// by an exact zero.  With a workspace the launch evaluates them on the LIVE rows only - alpha != 0 (NaN counts), and sample 0 of
+// the ray as a canary, so that a non-finite view/rgb weight, bias or direction still reaches rgb_map - packed 32 to a view
+// segment ACROSS rays.  A view segment needs a row's ReLU'd h7 and its direction and no per-ray state, and the columns of an
+// MFMA are independent, so which rows share a segment changes no bit.  Three kernels on one stream:
+//   A  render_pass_kernel<false> (this file): trunk, sigma head, density compositing, resampling and every per-sample output as
+//      ever.  A tile whose rows are certain to fit the ray's region of the workspace (decided BEFORE the trunk, so that layer
+//      7's last prefetches go to the head of the next tile: WStream.cont) stashes its live rows' h7 and leaves the view segment
+//      out; any other tile runs it in line on its own rows.  Per ray the region also takes w[S], the raw colours c[3][S] (0 for
+//      dead and for stashed rows), the sample index of every stashed row and acc, the launch header their count.  No rgb_map.
+//   B  colour_rows_kernel (colour_kernels.hip): persistent waves; segment g = stashed rows 32g .. 32g+31 of the launch in ray
+//      order, located through the prefix of the rays' counts (colour_scan_kernel in front of it).  Each lane loads its row,
+//      forms gamma(d) of the row's ray and runs the 4 x 9 view layer from the blob's views-loop stream and the rgb head
+//      (mlp_kernels.h views_mean with rows read instead of computed: the sum order of DIR + VIEWSH), then scatters the raw
+//      colour to c[.][sample] of its ray.
+//   C  colour_maps_kernel (same unit): one wave per ray forms the colour sums as the tile loop does in line - lane j takes sample
+//      32 t + j, tiles ascending - and writes rgb_map.
+// The same operations in the same order, so the outputs are the in-line launch's bit for bit whenever the colours left out were
+// finite.
+//
+// Workspace (floats; ViewWs below):  launch header | n_rays regions of `per_ray`
+//   header: int off[n_rays + 1] (A: a ray's count; the scan: their exclusive prefix; padded to 4) | int segray[8 n_rays] (the ray
+//           that holds row 32g)
+//   region: float acc, 3 pad | w[Sp] | c[3][Sp] | int sample[R] | rows [g 32][h 2][slot R][4]                  (Sp = S up to 4)
+// rows: register group g of lane (slot, h)'s B operand - ONE store instruction writes adjacent 16-byte cells for adjacent slots.
+// R follows from the workspace's size (at most Sp: then every tile stashes); n_rays x 64 x 256 floats is the accepted minimum.
 #define SW_DEFER_SMAX 240
-#define SW_DEFER_LDS_FLOATS (4 * SW_DEFER_SMAX + 64)
-#define SW_DEFER_WS_FLOATS (64 * 256)            // workspace floats per ray
-static_assert(SW_DEFER_LDS_FLOATS <= SW_LDS_SORT, "the deferred colour scratch shares the sort region");
+#define SW_DEFER_WS_FLOATS (64 * 256)            // least workspace floats per ray
+#define SW_DEFER_SEGS_PER_RAY ((SW_DEFER_SMAX + 31) / 32)
+
+struct ViewWs {
+    float* base;            // NULL = the launch runs the colour branch in line
+    int64_t hdr, per_ray;   // floats: launch header, one ray's region
+    int rows, sp;           // R, Sp
+};
+
+static inline int64_t view_ws_hdr(int64_t n_rays) { return ((n_rays + 1 + 3) & ~(int64_t)3) + SW_DEFER_SEGS_PER_RAY * n_rays; }
+// floats with which every tile of every ray stashes
+static inline int64_t view_ws_full(int64_t n_rays, int S) {
+    const int64_t sp = (S + 3) & ~3;
+    return view_ws_hdr(n_rays) + n_rays * (4 + 4 * sp + 257 * sp);
+}
+static inline ViewWs view_ws_layout(float* base, int64_t floats, int64_t n_rays, int S) {
+    ViewWs v = {};
+    v.base = base;
+    v.sp = (S + 3) & ~3;
+    v.hdr = view_ws_hdr(n_rays);
+    const int64_t avail = n_rays > 0 ? ((floats - v.hdr) / n_rays) & ~(int64_t)3 : 0;
+    int64_t r = ((avail - 4 - 4 * v.sp) / 257) & ~(int64_t)3;
+    if (r > v.sp) r = v.sp;
+    v.rows = r > 0 ? (int)r : 0;
+    v.per_ray = 4 + 4 * (int64_t)v.sp + 257 * (int64_t)v.rows;
+    return v;
+}
+__device__ __forceinline__ int* vw_off(const ViewWs& v) { return reinterpret_cast<int*>(v.base); }
+__device__ __forceinline__ int* vw_segray(const ViewWs& v, int64_t n_rays) { return reinterpret_cast<int*>(v.base) + ((n_rays + 1 + 3) & ~(int64_t)3); }
+__device__ __forceinline__ float* vw_ray(const ViewWs& v, int64_t ray) { return v.base + v.hdr + ray * v.per_ray; }
+__device__ __forceinline__ float* vw_w(const ViewWs& v, float* reg) { return reg + 4; }
+__device__ __forceinline__ float* vw_c(const ViewWs& v, float* reg) { return reg + 4 + v.sp; }
+__device__ __forceinline__ int* vw_sample(const ViewWs& v, float* reg) { return reinterpret_cast<int*>(reg + 4 + 4 * v.sp); }
+// this lane's cell of register group 0 of `slot`; group g is g * vw_group_stride() floats further on
+__device__ __forceinline__ float* vw_row(const ViewWs& v, float* reg, int slot, int h) { return reg + 4 + 4 * v.sp + v.rows + (h * v.rows + slot) * 4; }
+__device__ __forceinline__ int vw_group_stride(const ViewWs& v) { return 8 * v.rows; }
 
 struct PassDev {
     swnerf_pass_args a;
@@ -69,7 +110,7 @@ struct PassDev {
     int warm_blocks;        // workgroups per XCD that share the warm-up (blocks b with b < 8 * warm_blocks take part)
     int skew_mode;          // 0 none | 1 per workgroup | 2 per wave
     int skew_unit;          // s_sleep argument of one skew class (units of 64 clocks)
-    float* view_ws;         // swnerf_render_pass_ws: the deferred colour branch's workspace [n_rays, 64, 256], or NULL = in line
+    ViewWs vw;              // swnerf_render_pass_ws: the deferred colour branch's workspace (vw.base NULL = in line)
 };
 
 __device__ __forceinline__ float wave32_sum(float v) {   // sum over the 32 lanes of each half
@@ -343,24 +384,14 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     const int ntiles = (S + 31) >> 5;
     // the deferred colour branch (top of this file); DEFER_OK = false compiles every line of it away
     constexpr bool DEFER_OK = !DNERF && !TRAIN && PREC == 0 && VIEWS;
-    const bool defer = DEFER_OK && P.view_ws != nullptr;
-    float* dW = resample ? srt : lds_all + PassLds<DNERF, TRAIN>::FIXED + wv * SW_DEFER_LDS_FLOATS;   // [S] w | 3 x [S] raw colour | [64] sample of a slot
-    float* dC = dW + SW_DEFER_SMAX;
-    int* dIdx = reinterpret_cast<int*>(dW + 4 * SW_DEFER_SMAX);
-    float* vrow = DEFER_OK ? P.view_ws + ray * SW_DEFER_WS_FLOATS + h * 128 : nullptr;
+    const bool defer = DEFER_OK && P.vw.base != nullptr;
+    float* vreg = defer ? vw_ray(P.vw, ray) : nullptr;                     // this ray's region of the workspace
     const char* main_head = reinterpret_cast<const char*>(P.w0 + (P.dir_steps + P.time_steps) * SW_STEP_FLOATS);
-    const char* viewsh_head = main_head + (SW_CANON_MAIN_STEPS - SW_STEPS_VIEWSH) * 1024;
-    int pend = 0, wr = 0, rd = 0;                 // wave-uniform: rows pending in the ring, rows written / read so far
-    if constexpr (DEFER_OK) {
-        if (defer) {
-            for (int i = lane; i < 3 * SW_DEFER_SMAX; i += 64) dC[i] = 0.f;
-            wave_lds_sync();
-        }
-    }
+    int wr = 0;                                   // wave-uniform: rows stashed so far
 #pragma nounroll
-    for (int tile = 0; tile < ntiles || (DEFER_OK && pend > 0); ++tile) {
-        const bool is_tile = !DEFER_OK || tile < ntiles;                  // else: a view-only turn that drains the ring
-        const bool flush = !defer || !is_tile || pend >= 32;              // this turn runs the view segment
+    for (int tile = 0; tile < ntiles; ++tile) {
+        // this tile stashes its live rows and leaves the view segment out: all the rows it may hold are certain to fit
+        const bool stash = defer && wr + min(32, S - tile * 32) <= P.vw.rows;
         const int s = tile * 32 + j;
         const bool live = s < S && !ghost;
         const int sc = live ? s : S - 1;
@@ -385,7 +416,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         f32x16 emb[2], in[8], out[8];
         float head[3], rgb[3];
         float extra = 0.f;                          // VIEWS = false, out_ch == 5: the fifth channel of output_linear (only `raw` shows it)
-        if (is_tile) pe_pos(px, py, pz, h, emb);
+        pe_pos(px, py, pz, h, emb);
         if (DNERF && TRAIN) {
             // deformation net, then the canonical net on gamma(x + dx) (model.py:128-151); both save what their dX
             // chains and weight-gradient GEMMs need, as side stores (see the static branch below).  Always both passes:
@@ -506,94 +537,70 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             rgb[0] = o5[0] + ws.bias[0]; rgb[1] = o5[1] + ws.bias[1]; rgb[2] = o5[2] + ws.bias[2];
             head[0] = o5[3] + ws.bias[3]; head[1] = 0.f; head[2] = 0.f;
             extra = o5[4] + ws.bias[4];
-        } else if (is_tile) {
-            // a tile that leaves the view segment out continues at the head of MAIN behind layer 7 (the last tile: at VIEWSH, where it
-            // is anyway, for the view-only turns that follow)
+        } else {
+            // a tile that leaves the view segment out continues at the head of MAIN behind layer 7
             trunk_pass<false, false, false, false, false, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws, nullptr, nullptr, false,
-                                                                nullptr, nullptr, nullptr, (flush || tile + 1 >= ntiles) ? nullptr : main_head);
+                                                                nullptr, nullptr, nullptr, stash ? main_head : nullptr);
         }
 
         // ---- raw2outputs on this tile (composite.h), the density side; both lane halves mirror each other
-        const float sg_raw = is_tile ? head[0] : 0.f;
+        const float sg_raw = head[0];
         float sg = sg_raw;
         if (a.noise) sg += a.noise[ray * S + sc];
-        const float alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live && is_tile);
-        float w = 0.f;
-        if (is_tile) {
-            w = alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
-            if (live) {
-                if (a.weights && h == 0) a.weights[ray * S + s] = w;
-                if (a.z_out && h == 0) a.z_out[ray * S + s] = z;
-                if (resample && h == 0) { zc[s] = z; wc[s] = w; }
-            }
-            comp_accumulate_density(w, z, pd, pa);
+        const float alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live);
+        const float w = alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
+        if (live) {
+            if (a.weights && h == 0) a.weights[ray * S + s] = w;
+            if (a.z_out && h == 0) a.z_out[ray * S + s] = z;
+            if (resample && h == 0) { zc[s] = z; wc[s] = w; }
         }
+        comp_accumulate_density(w, z, pd, pa);
 
-        // ---- the deferred colour branch.  A turn without the view segment stashes the tile's live rows.  A turn with it keeps the
-        // tile's live rows where they are, in `in`, and fills the OTHER lanes with the oldest pending rows, loaded in place (which
-        // rows share a view segment changes no bit: the columns of an MFMA are independent): no stash in such a turn, so never more
-        // than 63 rows pending, and no second copy of the 128 activation registers, which is what this kernel cannot afford
-        int src_s = s;                               // the sample whose colour this lane's row of the view segment is
-        bool src_ok = live;
+        // ---- the deferred colour branch: the tile's live rows go to the ray's region, packed in sample order
+        bool lit = live;                             // this row's colour enters the outputs
         if constexpr (DEFER_OK) {
             if (defer) {
-                const bool lit = is_tile && live && (!(alpha == 0.f) || s == 0);
-                const unsigned m = (unsigned)__ballot(lit);              // lanes 0..31: one bit per row
-                const unsigned below = (1u << j) - 1u;
-                const int cnt = __builtin_amdgcn_readfirstlane(__popc(m));
-                if (live && is_tile && h == 0) dW[s] = w;
-                if (!flush) {
-                    const int slot = (wr + __popc(m & below)) & 63;
+                lit = live && (!(alpha == 0.f) || s == 0);
+                if (live && h == 0) vw_w(P.vw, vreg)[s] = w;
+                if (stash) {
+                    const unsigned m = (unsigned)__ballot(lit);          // lanes 0..31: one bit per row
+                    const int slot = wr + __popc(m & ((1u << j) - 1u));
                     if (lit) {
-                        if (h == 0) dIdx[slot] = s;
-                        float* q = vrow + slot * 256;
+                        if (h == 0) vw_sample(P.vw, vreg)[slot] = s;
+                        float* q = vw_row(P.vw, vreg, slot, h);
+                        const int gs = vw_group_stride(P.vw);
 #pragma unroll
                         for (int c = 0; c < 32; ++c) {
                             const f32x4 v = {in[c >> 2][4 * (c & 3)], in[c >> 2][4 * (c & 3) + 1], in[c >> 2][4 * (c & 3) + 2], in[c >> 2][4 * (c & 3) + 3]};
-                            *reinterpret_cast<f32x4*>(q + c * 4) = v;
+                            *reinterpret_cast<f32x4*>(q + (size_t)c * gs) = v;
                         }
                     }
-                    wr += cnt; pend += cnt;
-                } else {
-                    const int room = 32 - cnt, nv = pend < room ? pend : room;   // a view-only turn has pend > 0, so nv > 0 there
-                    const int rank = __popc(~m & below);
-                    src_ok = lit || rank < nv;
-                    // a view-only turn pads its free lanes with copies of a pending row (a tile's free lanes keep their own dead row)
-                    if (!lit && (rank < nv || !is_tile)) {
-                        const int slot = (rd + (rank < nv ? rank : nv - 1)) & 63;
-                        src_s = dIdx[slot];
-                        const float* p = vrow + slot * 256;
-#pragma unroll
-                        for (int c = 0; c < 32; ++c) {
-                            const f32x4 v = *reinterpret_cast<const f32x4*>(p + c * 4);
-                            in[c >> 2][4 * (c & 3) + 0] = v[0]; in[c >> 2][4 * (c & 3) + 1] = v[1];
-                            in[c >> 2][4 * (c & 3) + 2] = v[2]; in[c >> 2][4 * (c & 3) + 3] = v[3];
-                        }
-                    }
-                    rd += nv; pend -= nv;
-                    if (!is_tile) ws.bias = lds_bias + (SW_DIR_BIAS_TILES + 64 + 8 + 1) * SW_BIAS_TILE_FLOATS + h * 16;   // where a trunk leaves it
+                    wr += __builtin_amdgcn_readfirstlane(__popc(m));
                 }
-                wave_lds_sync();
             }
         }
-        const bool drain_next = DEFER_OK && tile + 1 >= ntiles && pend > 0;     // the next turn of the loop is view-only
         if (!TRAIN && PREC == 0 && VIEWS) {
-            if (flush) {
-                if constexpr (DEFER_OK) ws.cont = drain_next ? viewsh_head : ws.base + SW_STEPS_VIEWSH * 1024;
+            if (!stash) {
+                if constexpr (DEFER_OK) ws.cont = ws.base + SW_STEPS_VIEWSH * 1024;
                 canon_tail<DEFER_OK>(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws);
+            } else {
+                rgb[0] = 0.f; rgb[1] = 0.f; rgb[2] = 0.f;
             }
         }
         // back to the head of MAIN (behind the per-ray DIR prefix and its b_vf tiles)
         if constexpr (PREC == 0) {               // back to MAIN: behind the per-ray prefixes (DIR, and TIME with its 8 bias tiles)
             ws_rewind(ws, P.w0 + (P.dir_steps + P.time_steps) * SW_STEP_FLOATS,
                       lds_bias + ((P.dir_steps ? SW_DIR_BIAS_TILES : 0) + (P.time_steps ? 8 : 0)) * SW_BIAS_TILE_FLOATS, lane);
-            if (drain_next) ws.base = viewsh_head;
         }
 
         // ---- the colour side
         const float c0 = rgb[0], c1 = rgb[1], c2 = rgb[2];
-        if (DEFER_OK && defer) {
-            if (flush && src_ok && h == 0) { dC[src_s] = c0; dC[SW_DEFER_SMAX + src_s] = c1; dC[2 * SW_DEFER_SMAX + src_s] = c2; }
+        if (DEFER_OK && defer) {                 // a stashed row's colour: phase B; the sums: phase C
+            if (live && h == 0) {
+                float* c = vw_c(P.vw, vreg);
+                const bool here = lit && !stash;
+                c[s] = here ? c0 : 0.f; c[P.vw.sp + s] = here ? c1 : 0.f; c[2 * P.vw.sp + s] = here ? c2 : 0.f;
+            }
             continue;
         }
         if (a.raw && live && h == 0) {
@@ -608,23 +615,12 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         comp_accumulate_colour(w, c0, c1, c2, pr, pg, pb);
     }
 
-    if constexpr (DEFER_OK) {
-        if (defer) {
-            // the colour sums, as the tile loop forms them in line: lane j takes sample 32 t + j, tiles ascending
-            wave_lds_sync();
-#pragma nounroll
-            for (int t = 0; t < ntiles; ++t) {
-                const int s = t * 32 + j;
-                const int sc = s < S ? s : S - 1;
-                const float w = s < S ? dW[sc] : 0.f;
-                const float c0 = dC[sc], c1 = dC[SW_DEFER_SMAX + sc], c2 = dC[2 * SW_DEFER_SMAX + sc];
-                comp_accumulate_colour(w, c0, c1, c2, pr, pg, pb);
-            }
-        }
-    }
     pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
     pd = wave32_sum(pd); pa = wave32_sum(pa);
-    if (lane == 0 && !ghost) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
+    if (lane == 0 && !ghost) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, defer ? nullptr : a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
+    if constexpr (DEFER_OK) {
+        if (defer && lane == 0) { vw_off(P.vw)[ray] = wr; vreg[0] = pa; }
+    }
     if (!resample || ghost) return;
 
     // ---- sample_pdf (ray.py:96-153) on bins = mid-points, weights[1:-1]; z_std; then sort (nerf/run.py:396-400, 416) as a rank

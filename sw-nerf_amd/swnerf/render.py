@@ -187,20 +187,27 @@ def pass_args(rb, kind, packed, bands, S, out_ch, run_deform, inputs, outputs, n
     return a, out, keep
 
 
-# Workspace of the fused inference pass's deferred colour branch (include/swnerf.h swnerf_render_pass_ws): 64 rows of 256
-# floats per ray, scratch.  One grow-only tensor per (device, stream): launches on one stream run in order and may share it,
-# launches on different streams (parallel.frame_renderer) may overlap and must not.  D-NeRF launches pass none: the library
-# takes the branch for the static net alone.
+# Workspace of the fused inference pass's deferred colour branch (include/swnerf.h swnerf_render_pass_ws), scratch.  The library
+# derives from its size how many of a ray's live rows it can stash for the packed colour kernels; a tile whose rows may not fit
+# runs the view layer in line.  Sized so that EVERY tile stashes - S rows of 257 floats per ray plus the bookkeeping,
+# swnerf_view_ws_floats: 0.82 GB at 4096 rays x 192 samples, 6.6 GB at render()'s default chunk of 32 768 rays - as far as
+# VIEW_WS_BUDGET_BYTES allows, and never below the accepted minimum of 64 x 256 floats per ray (about 60 rows per ray).  One
+# grow-only tensor per (device, stream): launches on one stream run in order and may share it, launches on different streams
+# (parallel.frame_renderer) may overlap and must not.  D-NeRF launches pass none: the library takes the branch for the static
+# net alone.
 VIEW_WS_FLOATS_PER_RAY = 64 * 256
-VIEW_WS_SMAX = 240                                       # above it the pass's per-wave scratch does not fit: the library runs in line
+VIEW_WS_BUDGET_BYTES = 8 << 30
+VIEW_WS_SMAX = 240                                       # above it the library runs in line
 _VIEW_WS = {}
 
 
-def view_workspace(rb, n_rays):
+def view_workspace(rb, n_rays, n_samples):
+    full = int(_lib.lib().swnerf_view_ws_floats(n_rays, n_samples))
+    floats = max(n_rays * VIEW_WS_FLOATS_PER_RAY, min(full, VIEW_WS_BUDGET_BYTES // 4))
     key = (rb.device, torch.cuda.current_stream(rb.device).cuda_stream)
     ws = _VIEW_WS.get(key)
-    if ws is None or ws.numel() < n_rays * VIEW_WS_FLOATS_PER_RAY:
-        _VIEW_WS[key] = ws = torch.empty(n_rays * VIEW_WS_FLOATS_PER_RAY, dtype=torch.float32, device=rb.device)
+    if ws is None or ws.numel() < floats:
+        _VIEW_WS[key] = ws = torch.empty(floats, dtype=torch.float32, device=rb.device)
     return ws
 
 
@@ -238,7 +245,7 @@ def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand
     else:
         # the deferred colour branch (include/swnerf.h swnerf_render_pass_ws) wherever the library takes it
         if kind == _lib.NET_CANON and "raw" not in want and S <= VIEW_WS_SMAX and N > 0:
-            ws = view_workspace(rb, N)
+            ws = view_workspace(rb, N, S)
             _lib.check(_lib.lib().swnerf_render_pass_ws(a, _lib.ptr(ws), ws.numel(), _lib.stream_of(rb)), "render_pass")
         else:
             _lib.check(_lib.lib().swnerf_render_pass(a, _lib.stream_of(rb)), "render_pass")
