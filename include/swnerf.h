@@ -337,7 +337,8 @@ int swnerf_render_pass(const swnerf_pass_args* args /*HOST*/, void* stream);
  * The workspace's size decides how many rows a ray can stash; a 32-sample tile whose rows are not certain to fit runs the view
  * layer in line.  swnerf_view_ws_floats(n_rays, n_samples) is the size at which every tile stashes (n_samples rows of 257
  * floats per ray plus bookkeeping); n_rays * 64 * 256 floats is the least accepted (about 60 rows per ray): view_ws != NULL
- * with fewer is SWNERF_E_ARG.  view_ws must be 16-byte aligned; its contents are scratch before and after.
+ * with fewer is SWNERF_E_ARG.  view_ws must be 16-byte aligned; its contents are scratch before and after (the layout:
+ * csrc/view_ws.h).
  * Used for SWNERF_NET_CANON launches without `raw` and with n_samples <= 240; every other launch ignores it and runs as
  * swnerf_render_pass does.  Launches that may overlap (different streams) need a workspace each. */
 int swnerf_render_pass_ws(const swnerf_pass_args* args /*HOST*/, float* view_ws, int64_t view_ws_floats, void* stream);

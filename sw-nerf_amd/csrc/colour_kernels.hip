@@ -1,4 +1,4 @@
-// colour_kernels.hip - phases B and C of the deferred colour branch of the static fp32 inference pass (render_pass.h, top):
+// colour_kernels.hip - phases B and C of the deferred colour branch of the static fp32 inference pass (view_ws.h):
 // the view layer and the rgb head on the rows that phase A (render_pass_kernel<false>) stashed in the workspace, packed 32 to
 // a view segment across rays, then the colour sums and rgb_map per ray.  Three kernels behind phase A on its stream:
 //   colour_scan_kernel   exclusive prefix of the rays' stashed-row counts, and for every segment the ray that holds its first row
@@ -10,8 +10,8 @@
 #include "swnerf_common.h"
 #include "mlp_core.h"
 #include "host_util.h"
-#include "mlp_kernels.h"
-#include "render_pass.h"
+#include "composite.h"
+#include "view_ws.h"
 
 // ---- phase A left every ray's stashed-row count in off[ray]; in place: off[r] = stashed rows of the rays below r, off[n_rays] =
 // their total; segray[g] = the ray that holds row 32 g.  One workgroup: thread t takes the rays [t K, (t + 1) K) - its own
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(256) colour_maps_kernel(ViewWs vw, int64_t n_r
     const int64_t ray = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
     float* reg = vw_ray(vw, ray);
-    const float* wq = vw_w(vw, reg);
+    const float* wq = vw_w(reg);
     const float* cq = vw_c(vw, reg);
     float pr = 0.f, pg = 0.f, pb = 0.f;
     const int ntiles = (S + 31) >> 5;

@@ -260,6 +260,14 @@ __device__ __forceinline__ float relu1(float x) {
     return y;
 }
 
+template <int NT>
+__device__ __forceinline__ void relu_tiles(const f32x16 (&x)[NT], f32x16 (&y)[NT]) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) y[n][r] = relu1(x[n][r]);
+}
+
 // ---- 1- and 3-output heads on the VALU ---------------------------------------------------------------
 // res[o] = sum_f W[o][f] * x[f]  over the NT*32 features of a row.  Lane (j,h) holds the 16*NT features
 // 32n + frow(r,h) of row j in x[n][r]; W[o] is stored like a bias vector (tile n: [h][r]), so each lane
@@ -323,6 +331,15 @@ __device__ __forceinline__ void tiles_store(float* rowp, const f32x16 (&t)[NT]) 
             f32x4 v = {t[n][4 * g], t[n][4 * g + 1], t[n][4 * g + 2], t[n][4 * g + 3]};
             *reinterpret_cast<f32x4*>(rowp + 32 * n + 8 * g) = v;
         }
+}
+
+// one 16-float encoding k-tile into the slot-ordered xs row (sw_xs_col): p = the row + the k-tile's first column + 4h
+__device__ __forceinline__ void xs_store_tile(float* p, const f32x16& t) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 v = {t[4 * g], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3]};
+        *reinterpret_cast<f32x4*>(p + 8 * g) = v;
+    }
 }
 
 // cooperative copy of a bias stream into LDS (whole block; ends with a barrier)
@@ -405,23 +422,34 @@ __device__ __forceinline__ void tile_fetch(const float* lds_tile, int lane, f32x
 // deform_pass: layer 0 also takes the time-embedding k-tile (model.py:129: cat[new_pts, t]).
 // Returns with `in` = relu(layer-7 output) and head[0..2] = the head applied to it on every lane:
 // alpha_linear (head[0] = sigma) for the canonical net, _time_out (dx) for the deformation net.
-// TRAIN: every layer's post-ReLU activation h_l goes to act_row[256*l ...] (this lane's row of the row-major
-// [M, SW_ACT_LD] buffer, + 4h) and its ReLU bit mask to mask_tile[256*l] (this lane's 16 bytes of the tile's
-// SW_MASK_TILE_FLOATS), both as side stores of the NEXT segment, whose B operand h_l is.  h_7 has no next
-// segment here: store_last writes it on the spot, otherwise the caller side-stores it (in `in`, mask in *mb).
-// XS (fused training pass): the two position-encoding k-tiles go to xs_row (+ 4h; slot order, sw_xs_col) as side
-// stores of layer 0, whose B operand they are.
+// TRAIN: every layer's post-ReLU activation h_l goes to side.act_row[256*l ...] and its ReLU bit mask to
+// side.mask_tile[256*l], both as side stores of the NEXT segment, whose B operand h_l is.  h_7 has no next
+// segment here: side.store_last writes it on the spot, otherwise the caller side-stores it (in `in`, mask in *side.mb).
+// XS (fused training pass): the two position-encoding k-tiles go to side.xs_row as side stores of layer 0, whose B
+// operand they are.
 // NOHEAD: stop after layer 7 (`in` = relu(h7)); the caller applies its own head (output_linear of a net without view
 // directions, head_valu_rt).
 // TB (D-NeRF, fused passes): layer 0 of the deformation pass starts from the per-ray TIME tile lds_tb (see below).
 // REDIR (inference): behind layer 7 the stream continues at cont7 (wave-uniform; nullptr = at the bytes that follow, as without
 // REDIR) - how a tile that leaves out the view layer keeps the ring on the head of the next tile (render_pass.h).
-template <bool DNERF, bool TRAIN = false, bool XS = false, bool NOHEAD = false, bool TB = false, bool REDIR = false>
-__device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_emb, float t, bool deform_pass, int h,
-                                           f32x16 (&in)[8], f32x16 (&out)[8], float (&head)[3], WStream& ws,
-                                           float* act_row = nullptr, float* mask_tile = nullptr, bool store_last = false,
-                                           f32x4* mb = nullptr, float* xs_row = nullptr, const float* lds_tb = nullptr,
-                                           const char* cont7 = nullptr) {
+
+// where one row's training side outputs go (TRAIN / XS; all unused otherwise)
+struct TrunkSide {
+    float* act_row;         // this lane's row of the row-major [M, SW_ACT_LD] buffer, + 4h
+    float* mask_tile;       // this lane's 16 bytes of the tile's SW_MASK_TILE_FLOATS
+    bool store_last;        // h_7 and its mask are stored on the spot ...
+    f32x4* mb;              // ... or its mask is handed to the caller here
+    float* xs_row;          // XS: this lane's row of xs, + 4h (slot order, sw_xs_col)
+};
+
+// The pass itself, the members of `side` as separate arguments.  Call sites use trunk_pass() below; the one exception is the
+// two-pass loop of the fp32 D-NeRF passes (render_pass.h): through the aggregate render_pass_kernel<true, true> came out at
+// 510 or 512 registers instead of 508, with every other figure unchanged.
+template <bool DNERF, bool TRAIN, bool XS, bool NOHEAD, bool TB, bool REDIR>
+__device__ __forceinline__ void trunk_pass_flat(const f32x16 (&emb)[2], float* lds_emb, float t, bool deform_pass, int h,
+                                                f32x16 (&in)[8], f32x16 (&out)[8], float (&head)[3], WStream& ws,
+                                                float* act_row, float* mask_tile, bool store_last, f32x4* mb, float* xs_row,
+                                                const float* lds_tb, const char* cont7) {
     static_assert(!REDIR || (!TRAIN && !DNERF && !NOHEAD), "the redirect serves the static inference pass");
     const int lane_ = threadIdx.x & 63;
     emb_park(lds_emb, lane_, emb);
@@ -432,7 +460,7 @@ __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_em
             if (DNERF && deform_pass) {
                 // _time.0 on cat[gamma(x), gamma(t)] (model.py:129) as TWO segments of the stream: TIME (bias + the gamma(t) columns),
                 // then the gamma(x) columns on top.  TB (the fused passes: ONE time per ray): the wave has evaluated TIME
-                // once (time_bias_tile) and this tile's accumulators start from that per-ray tile - 128 MFMAs per tile less; otherwise (time
+                // once (ray_init_tile) and this tile's accumulators start from that per-ray tile - 128 MFMAs per tile less; otherwise (time
                 // per ROW: mlp_forward, the training forward of the op path): both segments here.  The same sequence of additions
                 // either way, so the two paths give the same bits.
                 if constexpr (TB) {
@@ -442,11 +470,7 @@ __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_em
                         seg_mfma<8, 2, SEG_BIAS, 2>(out, emb, ws, 1.f, SideStore{xs_row, nullptr, mbits});   // gamma(x) -> xs ...
                         f32x16 tt;
                         pe_time(t, h, tt);                                                                    // ... and gamma(t), on the spot
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const f32x4 v = {tt[4 * g], tt[4 * g + 1], tt[4 * g + 2], tt[4 * g + 3]};
-                            *reinterpret_cast<f32x4*>(xs_row + 64 + 8 * g) = v;
-                        }
+                        xs_store_tile(xs_row + 64, tt);
                     } else {
                         seg_mfma<8, 2, SEG_BIAS>(out, emb, ws);
                     }
@@ -479,10 +503,7 @@ __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_em
                 seg_mfma<8, 2, SEG_ACC>(out, e2, ws);
             }
         }
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) in[n][r] = relu1(out[n][r]);
+        relu_tiles<8>(out, in);
         if (TRAIN) mbits = relu_bits<8>(in);
     }
     if (TRAIN) {
@@ -507,6 +528,15 @@ __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_em
     ws.bias += SW_BIAS_TILE_FLOATS;
 }
 
+template <bool DNERF, bool TRAIN = false, bool XS = false, bool NOHEAD = false, bool TB = false, bool REDIR = false>
+__device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_emb, float t, bool deform_pass, int h,
+                                           f32x16 (&in)[8], f32x16 (&out)[8], float (&head)[3], WStream& ws,
+                                           const TrunkSide& side = TrunkSide{}, const float* lds_tb = nullptr,
+                                           const char* cont7 = nullptr) {
+    trunk_pass_flat<DNERF, TRAIN, XS, NOHEAD, TB, REDIR>(emb, lds_emb, t, deform_pass, h, in, out, head, ws, side.act_row, side.mask_tile,
+                                                         side.store_last, side.mb, side.xs_row, lds_tb, cont7);
+}
+
 // ---- canonical tail: [feature_linear folded into] views_linears[0] + relu -> rgb_linear ---
 // `in` = relu(layer 7).  On return rgb[0..2] = raw rgb of row j on every lane (model.py:49-58).
 // feature_linear has no activation, so the packed stream carries W_vf = Wv[:, :256] . W_f and b_vf = Wv[:, :256] . b_f + b_v
@@ -516,20 +546,25 @@ __device__ __forceinline__ void trunk_pass(const f32x16 (&emb)[2], float* lds_em
 // Two forms of the view layer:
 //  * canon_tail_rows: directions vary per ROW (mlp_forward on embedded rows, the point query): one 4 x 9 segment on
 //    [gamma(d) | h7] taken from the blob's views-loop stream (ws_restart), initialised from the b_vf tiles;
-//  * canon_tail / canon_tail_train: the fused passes, ONE direction per ray: the wave has evaluated
-//    c = Wv[:, 256:] gamma(d) + b_vf once (view_bias_tile below: 64 MFMAs per RAY) and every tile runs a 4 x 8 segment on h7
-//    whose accumulators start from c - 64 MFMAs per TILE less.
+//  * canon_tail: the fused passes, ONE direction per ray: the wave has evaluated c = Wv[:, 256:] gamma(d) + b_vf once
+//    (ray_init_tile below on gamma(d): 64 MFMAs per RAY) and every tile runs a 4 x 8 segment on h7 whose accumulators start
+//    from c - 64 MFMAs per TILE less.
 #define SW_VB_LDS_FLOATS (4 * SW_BIAS_TILE_FLOATS)       // per wave: the per-ray init tiles of the view layer, [n][h][r]
+#define SW_TB_LDS_FLOATS (8 * SW_BIAS_TILE_FLOATS)       // per wave: the per-ray init tiles of _time.0 (D-NeRF fused passes)
 
-// once per ray, right after ws_start on a stream that begins with the DIR prefix: vb[n][h][r] = c[32n + frow(r,h)]
-__device__ __forceinline__ void view_bias_tile(const f32x16& demb, float* lds_vb, int lane, WStream& ws) {
-    f32x16 k1[1], c[4];
-    k1[0] = demb;
-    seg_mfma<4, 1, SEG_BIAS>(c, k1, ws);                     // every column j of the result is the same: gamma(d) is the ray's
+// once per ray (or per wave, where the wave's rows share it): c = bias + W[:, cols of k] . k for the constant k-tile `k` - every
+// column j of the result is the same - into lds_t[n][h][r] = c[32n + frow(r,h)], the accumulator-init layout of a bias tile.
+// The segment is the next one of the stream: the DIR prefix on gamma(d) (NT = 4: b_vf + Wv[:, 256:] gamma(d)), the TIME segment
+// behind it on gamma(t) (NT = 8: _time.0.bias + _time.0.weight[:, Cpos:] gamma(t)), the T-NeRF prefixes (tnerf_pass.h).
+template <int NT>
+__device__ __forceinline__ void ray_init_tile(const f32x16& k, float* lds_t, int lane, WStream& ws) {
+    f32x16 k1[1], c[NT];
+    k1[0] = k;
+    seg_mfma<NT, 1, SEG_BIAS>(c, k1, ws);
     if ((lane & 31) == 0) {
-        float* o = lds_vb + (lane >> 5) * 16;
+        float* o = lds_t + (lane >> 5) * 16;
 #pragma unroll
-        for (int n = 0; n < 4; ++n)
+        for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 v = {c[n][4 * g], c[n][4 * g + 1], c[n][4 * g + 2], c[n][4 * g + 3]};
@@ -540,65 +575,30 @@ __device__ __forceinline__ void view_bias_tile(const f32x16& demb, float* lds_vb
     __builtin_amdgcn_wave_barrier();
 }
 
-// The same for the deformation net's layer 0 (D-NeRF fused passes, right behind view_bias_tile: the stream's TIME segment follows
-// its DIR prefix): tb[n][h][r] = (_time.0.bias + _time.0.weight[:, Cpos:] gamma(t))[32n + frow(r,h)], 8 tiles, once per ray.
-#define SW_TB_LDS_FLOATS (8 * SW_BIAS_TILE_FLOATS)
-__device__ __forceinline__ void time_bias_tile(float t, int h, float* lds_tb, int lane, WStream& ws) {
-    f32x16 k1[1], c[8];
-    pe_time(t, h, k1[0]);
-    seg_mfma<8, 1, SEG_BIAS>(c, k1, ws);
-    if ((lane & 31) == 0) {
-        float* o = lds_tb + (lane >> 5) * 16;
-#pragma unroll
-        for (int n = 0; n < 8; ++n)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v = {c[n][4 * g], c[n][4 * g + 1], c[n][4 * g + 2], c[n][4 * g + 3]};
-                *reinterpret_cast<f32x4*>(o + n * SW_BIAS_TILE_FLOATS + 4 * g) = v;
-            }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// REDIR: behind the view layer the stream continues at ws.cont (set by the caller), see seg_mfma.
-template <bool REDIR = false>
-__device__ __forceinline__ void canon_tail(const f32x16 (&in)[8], const float* lds_vb, float (&rgb)[3], const float* hb_rgb, WStream& ws) {
-    f32x16 hv[4];
-    const float* keep = ws.bias;
-    ws.bias = lds_vb + (threadIdx.x & 32 ? 16 : 0);
-    seg_mfma<4, 8, SEG_BIAS, 0, 0, REDIR>(hv, in, ws);
-    ws.bias = keep;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hv[n][r] = relu1(hv[n][r]);
-    head_valu<3, 4>(hv, ws, rgb);
-    rgb[0] += hb_rgb[1]; rgb[1] += hb_rgb[2]; rgb[2] += hb_rgb[3];
-}
-
-// The same tail in the fused training passes: h7 (`in`, ReLU mask `mb`) is side-stored by the view layer's segment, whose B
-// operand it is; the view hidden layer and its mask are stored on the spot (act_row / mask_tile: trunk_pass).  `feature` does
+// TRAIN (the fused training passes): h7 (`in`, ReLU mask *side.mb) is side-stored by the view layer's segment, whose B operand
+// it is; the view hidden layer and its mask are stored on the spot (side.act_row / side.mask_tile: trunk_pass).  `feature` does
 // not exist: the weight gradients on both sides of feature_linear follow from G = d pre_hv^T . h7 (swnerf_feature_finish).
-__device__ __forceinline__ void canon_tail_train(const f32x16 (&in)[8], const float* lds_vb, float (&rgb)[3], const float* hb_rgb,
-                                                 WStream& ws, float* act_row, float* mask_tile, const f32x4& mb) {
+// REDIR: behind the view layer the stream continues at ws.cont (set by the caller), see seg_mfma.
+template <bool TRAIN = false, bool REDIR = false>
+__device__ __forceinline__ void canon_tail(const f32x16 (&in)[8], const float* lds_vb, float (&rgb)[3], const float* hb_rgb, WStream& ws,
+                                           const TrunkSide& side = TrunkSide{}) {
     f32x16 hv[4];
     const float* keep = ws.bias;
     ws.bias = lds_vb + (threadIdx.x & 32 ? 16 : 0);
-    seg_mfma<4, 8, SEG_BIAS, 8>(hv, in, ws, 1.f, SideStore{act_row + 256 * 7, mask_tile + 256 * 7, mb});
+    if constexpr (TRAIN) seg_mfma<4, 8, SEG_BIAS, 8>(hv, in, ws, 1.f, SideStore{side.act_row + 256 * 7, side.mask_tile + 256 * 7, *side.mb});
+    else seg_mfma<4, 8, SEG_BIAS, 0, 0, REDIR>(hv, in, ws);
     ws.bias = keep;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hv[n][r] = relu1(hv[n][r]);
-    tiles_store<4>(act_row + SW_ACT_HV, hv);
-    *reinterpret_cast<f32x4*>(mask_tile + 256 * 8) = relu_bits<4>(hv);
+    relu_tiles<4>(hv, hv);
+    if constexpr (TRAIN) {
+        tiles_store<4>(side.act_row + SW_ACT_HV, hv);
+        *reinterpret_cast<f32x4*>(side.mask_tile + 256 * 8) = relu_bits<4>(hv);
+    }
     head_valu<3, 4>(hv, ws, rgb);
     rgb[0] += hb_rgb[1]; rgb[1] += hb_rgb[2]; rgb[2] += hb_rgb[3];
 }
 
 // Per-row directions: the 4 x 9 view layer from the views-loop stream, whose k-tile order is [gamma(d) | h7] - the accumulators
-// take b_vf, then the direction terms, then the h7 terms: EXACTLY the sequence of view_bias_tile + canon_tail, so the op path and
+// take b_vf, then the direction terms, then the h7 terms: EXACTLY the sequence of ray_init_tile on gamma(d) + canon_tail, so the op path and
 // the fused pass produce the same bits (the resampling downstream is a discontinuous function of the coarse weights: two paths of
 // one library must not differ in the last bit there).  The caller has put the ring onto `wvl` (ws_restart, or a
 // previous turn whose tail is the stream's own head) and ws.base = wvl; bvf: the b_vf tiles (LDS, + 16 h).
@@ -611,8 +611,5 @@ __device__ __forceinline__ void canon_tail_rows(const f32x16 (&in)[8], const f32
     ws.bias = bvf;
     seg_mfma<4, 9, SEG_BIAS>(hv, k9, ws);
     ws.bias = keep;
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hv[n][r] = relu1(hv[n][r]);
+    relu_tiles<4>(hv, hv);
 }

@@ -109,6 +109,7 @@ __global__ void __launch_bounds__(256, 1) mlp_forward_kernel(MlpDev P) {
     float* act_row = TRAIN ? P.act + rt.rr * SW_ACT_LD + 4 * h : nullptr;
     float* mask_tile = TRAIN ? P.bits + rt.tile * SW_MASK_TILE_FLOATS + rt.lane * 4 : nullptr;
     f32x4 mb = {0.f, 0.f, 0.f, 0.f};
+    const TrunkSide side = {act_row, mask_tile, false, &mb, nullptr};     // h7 and its mask: stored below, on the spot
     WStream ws;
     // per-row directions: skip the per-ray DIR prefix of the stream (and its b_vf tiles), take the view layer from the views loop
     ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, rt.lds_ring, rt.lane);
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(256, 1) mlp_forward_kernel(MlpDev P) {
             }
         }
     } else {
-        trunk_pass<false, TRAIN>(emb, rt.lds_emb, 0.f, false, h, in, out, head, ws, act_row, mask_tile, false, &mb);
+        trunk_pass<false, TRAIN>(emb, rt.lds_emb, 0.f, false, h, in, out, head, ws, side);
     }
     // views_linears[0] on cat[feature, input_views] with feature_linear folded in (swnerf_common.h SW_CANON_STEPS): one
     // segment on [gamma(d) | h7] from the views-loop stream; the view-direction features are gathered like the position ones.

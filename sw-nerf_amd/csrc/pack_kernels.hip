@@ -223,7 +223,7 @@ struct Packer {
         const int eb[3] = {0, 0, Cpos};
         if (Ctime) {
             // layer 0 of the deformation net on cat[gamma(x), gamma(t)] as TWO segments: TIME = bias + the gamma(t) columns (the
-            // fused passes evaluate it once per ray, mlp_core.h time_bias_tile; the per-row kernels run it in line), then the
+            // fused passes evaluate it once per ray, mlp_core.h ray_init_tile; the per-row kernels run it in line), then the
             // gamma(x) columns, accumulating.  A stream that begins here loops back to the gamma(x) segment: TIME is a prefix.
             const int et[1] = {KT_TIME}, ebt[1] = {Cpos};
             const bool first = !have_head;
@@ -287,7 +287,7 @@ static int pack_tnerf(const float* const* params, int L_pos, int L_dir, int L_ti
     const int kt_pos[2] = {KT_POS0, KT_POS1}, kb_pos[2] = {0, 0};
     const int kt4[4] = {KT_TRUNK, KT_TRUNK, KT_TRUNK, KT_TRUNK}, kb4[4] = {0, 32, 64, 96};
     const int kb5[4] = {Cin, Cin + 32, Cin + 64, Cin + 96};
-    // per-ray prefix (evaluated once per ray: tnerf_kernels.hip tn_ray_tile); the ring tail repeats the head of MAIN
+    // per-ray prefix (evaluated once per ray: mlp_core.h ray_init_tile); the ring tail repeats the head of MAIN
     pk.seg(params[0], params[1], 128, Cin, 4, 1, kt_time, kb_time);                 // T0: layers.0 gamma(t) columns + bias
     pk.seg(params[10], params[11], 128, Cin + 128, 4, 1, kt_time, kb_time);         // T5: layers.5 gamma(t) columns + bias
     pk.seg(fold, fold + 64 * SW_TN_FOLD_LD, 64, SW_TN_FOLD_LD, 2, 1, kt_dir, kb_dir);  // DIR: layer_9 gamma(d) columns + b9f

@@ -3,7 +3,7 @@
 // in place of the static network_query_fn).  Inference translation unit: ring depth 8, like render_kernels.hip.
 //
 // D-NeRF (DirectTemporalNeRF.forward, model.py:138-151): one wave per 32 points, 4 waves per workgroup, as query_points_kernel.
-// The frame time is a constant of the LAUNCH, so the gamma(t) columns of _time.0 are evaluated once per wave (time_bias_tile:
+// The frame time is a constant of the LAUNCH, so the gamma(t) columns of _time.0 are evaluated once per wave (ray_init_tile:
 // the TIME segment of the stream) and the deformation net's layer 0 starts from that tile - the same sequence of additions as the
 // in-line form of mlp_forward_kernel<true>, so dx and sigma carry the same bits as the op path.  Then gamma(x + dx), the
 // canonical trunk and the density ONCE per point and only the view branch V times (the views loop of the blob's CANON part).
@@ -38,11 +38,15 @@ __global__ void __launch_bounds__(256, 1) query_points_dnerf_kernel(QueryTimeDev
     // directions vary per loop turn: skip the stream's per-ray DIR prefix (and its b_vf tiles), as mlp_forward_kernel does
     ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, rt.lds_ring, rt.lane);
     // the stream's TIME segment, once per wave: _time.0.bias + its gamma(t) columns (mlp_core.h)
-    if (P.two_pass) time_bias_tile(P.ft, h, lds_tb, rt.lane, ws);
+    if (P.two_pass) {
+        f32x16 temb;
+        pe_time(P.ft, h, temb);
+        ray_init_tile<8>(temb, lds_tb, rt.lane, ws);
+    }
     float ex = 0.f, ey = 0.f, ez = 0.f;                       // run_deform == 0: dx = 0 (model.py:143-145)
 #pragma nounroll
     for (int pass = P.two_pass ? 0 : 1; pass < 2; ++pass) {
-        trunk_pass<true, false, false, false, true>(emb, rt.lds_emb, P.ft, pass == 0, h, in, out, head, ws, nullptr, nullptr, false, nullptr, nullptr, lds_tb);
+        trunk_pass<true, false, false, false, true>(emb, rt.lds_emb, P.ft, pass == 0, h, in, out, head, ws, TrunkSide{}, lds_tb);
         if (pass == 0) {
             ex = head[0]; ey = head[1]; ez = head[2];
             pe_pos(x0 + ex, x1 + ey, x2 + ez, h, emb);        // embed_fn(input_pts_orig + dx) (model.py:148-149)

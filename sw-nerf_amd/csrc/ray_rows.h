@@ -63,6 +63,20 @@ __device__ __forceinline__ float row_dnorm(float ox, float oy, float oz, float d
     return finite ? sqrtf(dx * dx + dy * dy + dz * dz) : __builtin_nanf("");
 }
 
+// One row of the ray batch as the fused passes read it, once per ray: 8 columns [o d near far], 11 = ... viewdirs, 12 = ... t viewdirs.
+// VIEWS = false (the net without view directions) leaves v at 0 and reads no column behind `far`.
+struct RayRow { float o[3], d[3], near, far, ft, v[3], dnorm; };
+template <bool VIEWS>
+__device__ __forceinline__ RayRow ray_row_load(const float* rb, int cols) {
+    RayRow r;
+    r.o[0] = rb[0]; r.o[1] = rb[1]; r.o[2] = rb[2]; r.d[0] = rb[3]; r.d[1] = rb[4]; r.d[2] = rb[5];
+    r.near = rb[6]; r.far = rb[7];
+    r.ft = (cols == 12) ? rb[8] : 0.f;
+    r.v[0] = VIEWS ? rb[cols - 3] : 0.f; r.v[1] = VIEWS ? rb[cols - 2] : 0.f; r.v[2] = VIEWS ? rb[cols - 1] : 0.f;
+    r.dnorm = row_dnorm(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], r.near, r.far, r.ft);
+    return r;
+}
+
 // A block's 256 rows, assembled in LDS, leave as 16-byte stores of the block's contiguous 256 * cols floats of the batch (a
 // row-per-thread store pattern writes `cols` dwords at a 4 * cols-byte stride: every store instruction touches 22 lines for
 // 256 useful bytes).  The last, partial block - and an `out` that is not 16-byte aligned - stores dword-wise.  Call after

@@ -1,13 +1,5 @@
-// render_kernels.hip - fused NeRF render pass for gfx950 (MI355X): ONE wavefront owns ONE ray.
-//
-// For each 32-sample tile of its ray the wave computes depths -> points -> positional
-// encoding (VALU) -> [deformation MLP ->] canonical MLP (MFMA, registers: mlp_core.h) ->
-// alpha compositing (wave scan), and after the last tile optionally the hierarchical
-// resampling (inverse-CDF + rank merge in the wave's LDS slice).  Nothing per-sample
-// touches HBM unless the caller asks for it (raw / weights / dx / z_out).
-//
-// Reference: render_rays nerf/run.py:316-422, d_nerf/run_dnerf.py:354-480; raw2outputs
-// ray.py:155-198; sample_pdf ray.py:96-153; run_network nerf/run.py:73-87.
+// render_kernels.hip - the inference translation unit (ring depth 8): the entry points of the fused render pass (render_pass.h
+// describes the pass), the point query, coarse sampling and model.forward on embedded rows.
 #include <hip/hip_runtime.h>
 #include "../../include/swnerf.h"
 #include "swnerf_common.h"
@@ -45,7 +37,7 @@ __global__ void __launch_bounds__(256, 1) query_points_kernel(QueryDev P) {
 }
 
 int sw_tnerf_render_launch(const swnerf_pass_args& a, hipStream_t st);     // tnerf_kernels.hip
-// colour_kernels.hip: phases B and C of a launch whose tiles stashed their live rows (render_pass.h, the deferred colour branch)
+// colour_kernels.hip: phases B and C of a launch whose tiles stashed their live rows (view_ws.h, the deferred colour branch)
 int sw_colour_split_launch(const swnerf_pass_args& a, const ViewWs& vw, const float* b0, int nbias, const float* wvl, hipStream_t st);
 
 extern "C" int swnerf_render_pass_ws(const swnerf_pass_args* args, float* view_ws, int64_t view_ws_floats, void* stream) {
@@ -68,7 +60,7 @@ extern "C" int swnerf_render_pass_ws(const swnerf_pass_args* args, float* view_w
     P.time_steps = (a.kind == SWNERF_NET_DNERF && P.two_pass) ? SW_STEPS_TIME : 0;
     size_t lds = SW_LDS_FIXED_FLOATS * sizeof(float);
     if ((rc = pass_resampling(accepts.name, a, P, lds))) return rc;
-    // the deferred colour branch (render_pass.h): static net, no `raw` (which needs every row's colour) and a sample count whose
+    // the deferred colour branch (view_ws.h): static net, no `raw` (which needs every row's colour) and a sample count whose
     // bookkeeping leaves rows in the least workspace; every other launch runs the view layer in line
     if (view_ws && view_ws_floats < a.n_rays * (int64_t)SW_DEFER_WS_FLOATS)
         return sw_fail(SWNERF_E_ARG, "render_pass: view_ws holds %lld floats, %lld rays need %lld", (long long)view_ws_floats,
@@ -185,12 +177,12 @@ __global__ void __launch_bounds__(256, 1) mlp_forward_noview_kernel(MlpNoviewDev
     WStream ws;
     ws_start(ws, P.w0, lds_bias, rt.lds_ring, rt.lane);
     trunk_pass<false, false, false, true>(emb, rt.lds_emb, 0.f, false, rt.h, in, out, head, ws);
-    float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    head_valu_rt<8>(in, ws, P.out_ch, o5);
+    float rgb[3], extra;
+    noview_heads(in, ws, P.out_ch, P.out_ch, rgb, head, extra);
     if (rt.live && rt.h == 0) {
         float* o = P.out + rt.row * P.out_ch;
-        o[0] = o5[0] + ws.bias[0]; o[1] = o5[1] + ws.bias[1]; o[2] = o5[2] + ws.bias[2]; o[3] = o5[3] + ws.bias[3];
-        if (P.out_ch == 5) o[4] = o5[4] + ws.bias[4];
+        o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; o[3] = head[0];
+        if (P.out_ch == 5) o[4] = extra;
     }
 }
 

@@ -16,76 +16,11 @@
 #include "resample.h"
 #include "composite.h"
 #include "ray_rows.h"
+#include "view_ws.h"
 
 #define SW_LDS_SC 256                    // max coarse samples when resampling
 #define SW_LDS_SORT 1024                 // max S + n_importance (padded to a power of two)
 #define SW_LDS_WAVE_FLOATS (3 * SW_LDS_SC + SW_LDS_SORT)
-
-// ---- the deferred colour branch of the static fp32 inference pass (swnerf_render_pass_ws) ------------------------------
-// A sample's colour enters the outputs as w.c with w = alpha.T, and alpha = 1 - exp(-relu(sigma).dist) is exactly 0 for every
-// sample with sigma <= 0: the view layer and the rgb head of such a row (512 of a tile's 8192 MFMAs + the tail) are multiplied
-// by an exact zero.  With a workspace the launch evaluates them on the LIVE rows only - alpha != 0 (NaN counts), and sample 0 of
-// the ray as a canary, so that a non-finite view/rgb weight, bias or direction still reaches rgb_map - packed 32 to a view
-// segment ACROSS rays.  A view segment needs a row's ReLU'd h7 and its direction and no per-ray state, and the columns of an
-// MFMA are independent, so which rows share a segment changes no bit.  Three kernels on one stream:
-//   A  render_pass_kernel<false> (this file): trunk, sigma head, density compositing, resampling and every per-sample output as
-//      ever.  A tile whose rows are certain to fit the ray's region of the workspace (decided BEFORE the trunk, so that layer
-//      7's last prefetches go to the head of the next tile: WStream.cont) stashes its live rows' h7 and leaves the view segment
-//      out; any other tile runs it in line on its own rows.  Per ray the region also takes w[S], the raw colours c[3][S] (0 for
-//      dead and for stashed rows), the sample index of every stashed row and acc, the launch header their count.  No rgb_map.
-//   B  colour_rows_kernel (colour_kernels.hip): persistent waves; segment g = stashed rows 32g .. 32g+31 of the launch in ray
-//      order, located through the prefix of the rays' counts (colour_scan_kernel in front of it).  Each lane loads its row,
-//      forms gamma(d) of the row's ray and runs the 4 x 9 view layer from the blob's views-loop stream and the rgb head
-//      (mlp_kernels.h views_mean with rows read instead of computed: the sum order of DIR + VIEWSH), then scatters the raw
-//      colour to c[.][sample] of its ray.
-//   C  colour_maps_kernel (same unit): one wave per ray forms the colour sums as the tile loop does in line - lane j takes sample
-//      32 t + j, tiles ascending - and writes rgb_map.
-// The same operations in the same order, so the outputs are the in-line launch's bit for bit whenever the colours left out were
-// finite.
-//
-// Workspace (floats; ViewWs below):  launch header | n_rays regions of `per_ray`
-//   header: int off[n_rays + 1] (A: a ray's count; the scan: their exclusive prefix; padded to 4) | int segray[8 n_rays] (the ray
-//           that holds row 32g)
-//   region: float acc, 3 pad | w[Sp] | c[3][Sp] | int sample[R] | rows [g 32][h 2][slot R][4]                  (Sp = S up to 4)
-// rows: register group g of lane (slot, h)'s B operand - ONE store instruction writes adjacent 16-byte cells for adjacent slots.
-// R follows from the workspace's size (at most Sp: then every tile stashes); n_rays x 64 x 256 floats is the accepted minimum.
-#define SW_DEFER_SMAX 240
-#define SW_DEFER_WS_FLOATS (64 * 256)            // least workspace floats per ray
-#define SW_DEFER_SEGS_PER_RAY ((SW_DEFER_SMAX + 31) / 32)
-
-struct ViewWs {
-    float* base;            // NULL = the launch runs the colour branch in line
-    int64_t hdr, per_ray;   // floats: launch header, one ray's region
-    int rows, sp;           // R, Sp
-};
-
-static inline int64_t view_ws_hdr(int64_t n_rays) { return ((n_rays + 1 + 3) & ~(int64_t)3) + SW_DEFER_SEGS_PER_RAY * n_rays; }
-// floats with which every tile of every ray stashes
-static inline int64_t view_ws_full(int64_t n_rays, int S) {
-    const int64_t sp = (S + 3) & ~3;
-    return view_ws_hdr(n_rays) + n_rays * (4 + 4 * sp + 257 * sp);
-}
-static inline ViewWs view_ws_layout(float* base, int64_t floats, int64_t n_rays, int S) {
-    ViewWs v = {};
-    v.base = base;
-    v.sp = (S + 3) & ~3;
-    v.hdr = view_ws_hdr(n_rays);
-    const int64_t avail = n_rays > 0 ? ((floats - v.hdr) / n_rays) & ~(int64_t)3 : 0;
-    int64_t r = ((avail - 4 - 4 * v.sp) / 257) & ~(int64_t)3;
-    if (r > v.sp) r = v.sp;
-    v.rows = r > 0 ? (int)r : 0;
-    v.per_ray = 4 + 4 * (int64_t)v.sp + 257 * (int64_t)v.rows;
-    return v;
-}
-__device__ __forceinline__ int* vw_off(const ViewWs& v) { return reinterpret_cast<int*>(v.base); }
-__device__ __forceinline__ int* vw_segray(const ViewWs& v, int64_t n_rays) { return reinterpret_cast<int*>(v.base) + ((n_rays + 1 + 3) & ~(int64_t)3); }
-__device__ __forceinline__ float* vw_ray(const ViewWs& v, int64_t ray) { return v.base + v.hdr + ray * v.per_ray; }
-__device__ __forceinline__ float* vw_w(const ViewWs& v, float* reg) { return reg + 4; }
-__device__ __forceinline__ float* vw_c(const ViewWs& v, float* reg) { return reg + 4 + v.sp; }
-__device__ __forceinline__ int* vw_sample(const ViewWs& v, float* reg) { return reinterpret_cast<int*>(reg + 4 + 4 * v.sp); }
-// this lane's cell of register group 0 of `slot`; group g is g * vw_group_stride() floats further on
-__device__ __forceinline__ float* vw_row(const ViewWs& v, float* reg, int slot, int h) { return reg + 4 + 4 * v.sp + v.rows + (h * v.rows + slot) * 4; }
-__device__ __forceinline__ int vw_group_stride(const ViewWs& v) { return 8 * v.rows; }
 
 struct PassDev {
     swnerf_pass_args a;
@@ -109,15 +44,8 @@ struct PassDev {
     int warm_steps;         // 1-KiB steps of the weight stream to pull into the XCD's L2 at kernel start
     int warm_blocks;        // workgroups per XCD that share the warm-up (blocks b with b < 8 * warm_blocks take part)
     int skew_mode;          // 0 none | 1 per workgroup | 2 per wave
-    int skew_unit;          // s_sleep argument of one skew class (units of 64 clocks)
     ViewWs vw;              // swnerf_render_pass_ws: the deferred colour branch's workspace (vw.base NULL = in line)
 };
-
-__device__ __forceinline__ float wave32_sum(float v) {   // sum over the 32 lanes of each half
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
-    return v;
-}
 
 __device__ __forceinline__ float z_linear(const swnerf_pass_args& a, float near, float far, int s) {
     const float t = sw_linspace(0.f, 1.f, a.n_samples, s);
@@ -161,7 +89,6 @@ __device__ __forceinline__ void pass_startup(const PassDev& P, const float* w0, 
         const int k = (P.skew_mode == 1 ? (int)(b >> 3) : (int)(b >> 3) * 4 + wv) & 15;
 #pragma nounroll
         for (int i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(4);
-        (void)P.skew_unit;
     }
 }
 
@@ -176,7 +103,6 @@ static inline void pass_startup_args(PassDev& P, unsigned grid_x, int steps) {
     P.warm_blocks = (int)(first_round / 8u);
     P.warm_steps = (env_warm && P.warm_blocks > 0) ? steps + SW_TAIL : 0;
     P.skew_mode = env_skew;
-    P.skew_unit = 4;
 }
 
 // ---- host side: what every entry point of the pass checks and sets up (the per-variant checks stay with the entry point) ----
@@ -306,9 +232,88 @@ template <bool DNERF> struct X3Lds {
     static constexpr int FIXED = BIAS + X3_RING_FLOATS + 4 * WAVE;
 };
 
+// ---- the steps of the tile loop, each written once (tnerf_pass.h runs the per-ray and compositing ones too) -----------------
+// this lane's row of a tile: its sample, its lane of the half, the half, and whether the sample exists
+struct TileRow { int s, j, h; bool live; };
+
+// position_delta of sample s, by the lower lane half of a live row
+__device__ __forceinline__ void pass_store_dx(const swnerf_pass_args& a, int64_t ray, int s, bool live, int h, float ex, float ey, float ez) {
+    if (live && h == 0) {
+        float* o = a.dx + (ray * a.n_samples + s) * 3;
+        o[0] = ex; o[1] = ey; o[2] = ez;
+    }
+}
+
+// TRAIN: this lane's padded row of the side buffers of one net (PassDev act / bits / xs); tix = ray * ntiles + tile
+struct TrainRows { float* act_row; float* mask_tile; float* xs_row; };
+__device__ __forceinline__ TrainRows train_rows(float* act, float* bits, float* xs, int64_t tix, int j, int h, int lane) {
+    const int64_t prow = tix * 32 + j;
+    return {act + prow * SW_ACT_LD + 4 * h, bits + tix * SW_MASK_TILE_FLOATS + lane * 4, xs + prow * SW_XS_LD + 4 * h};
+}
+
+// outputs = output_linear(h) (model.py:59-60) as VALU heads behind a NOHEAD trunk: [rgb(3), sigma, (5th, shown by `raw` alone)].
+// nout <= out_ch channels are evaluated; the weight tiles of the others are skipped, so ws.bias ends at the head-bias tile.
+__device__ __forceinline__ void noview_heads(const f32x16 (&in)[8], WStream& ws, int nout, int out_ch, float (&rgb)[3], float (&head)[3], float& extra) {
+    float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    head_valu_rt<8>(in, ws, nout, o5);
+    ws.bias += (out_ch - nout) * 8 * SW_BIAS_TILE_FLOATS;
+    rgb[0] = o5[0] + ws.bias[0]; rgb[1] = o5[1] + ws.bias[1]; rgb[2] = o5[2] + ws.bias[2];
+    head[0] = o5[3] + ws.bias[3]; head[1] = 0.f; head[2] = 0.f;
+    extra = o5[4] + ws.bias[4];
+}
+
+// raw2outputs on one tile, the density side (composite.h; both lane halves mirror each other): noise, alpha, the weight from the
+// exclusive cumprod over the 32 lanes and the transmittance Tc carried across tiles ...
+__device__ __forceinline__ float pass_weight(const swnerf_pass_args& a, int64_t ray, int s, int sc, bool live, int j, float sg, float z, float zn,
+                                             float dnorm, double& Tc, float& alpha) {
+    const int S = a.n_samples;
+    if (a.noise) sg += a.noise[ray * S + sc];
+    alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live);
+    return alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
+}
+// ... and the per-sample outputs of a live row, by its lower lane half
+__device__ __forceinline__ void pass_store_wz(const swnerf_pass_args& a, int64_t ray, int s, int h, float w, float z) {
+    if (a.weights && h == 0) a.weights[ray * a.n_samples + s] = w;
+    if (a.z_out && h == 0) a.z_out[ray * a.n_samples + s] = z;
+}
+
+// after the last tile: the five sums over the 32 lanes (left in place: pa is acc); lane 0 of a wave that is no ghost writes the maps.
+// (lane and ghost apart: the condition formed by the caller and handed in as one bool moved the s_waitcnt count of three kernels.)
+__device__ __forceinline__ void pass_write_maps(float& pr, float& pg, float& pb, float& pd, float& pa, int lane, bool ghost,
+                                                const swnerf_pass_args& a, int64_t ray, float* rgb_map) {
+    pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
+    pd = wave32_sum(pd); pa = wave32_sum(pa);
+    if (lane == 0 && !ghost) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, rgb_map, a.disp_map, a.acc_map, a.depth_map);
+}
+
+// ---- the deferred colour branch, phase A (view_ws.h): a tile that stashes packs its lit rows' h7 (`in`) into the ray's region
+// `vreg` behind the `wr` rows already there, in sample order, with each row's sample index; returns how many it added (wave-uniform)
+__device__ __forceinline__ int defer_stash(const ViewWs& vw, float* vreg, const f32x16 (&in)[8], bool lit, int wr, const TileRow& t) {
+    const unsigned m = (unsigned)__ballot(lit);          // lanes 0..31: one bit per row
+    const int slot = wr + __popc(m & ((1u << t.j) - 1u));
+    if (lit) {
+        if (t.h == 0) vw_sample(vw, vreg)[slot] = t.s;
+        float* q = vw_row(vw, vreg, slot, t.h);
+        const int gs = vw_group_stride(vw);
+#pragma unroll
+        for (int c = 0; c < 32; ++c) {
+            const f32x4 v = {in[c >> 2][4 * (c & 3)], in[c >> 2][4 * (c & 3) + 1], in[c >> 2][4 * (c & 3) + 2], in[c >> 2][4 * (c & 3) + 3]};
+            *reinterpret_cast<f32x4*>(q + (size_t)c * gs) = v;
+        }
+    }
+    return __builtin_amdgcn_readfirstlane(__popc(m));
+}
+// the region's raw colours of sample s: what the tile evaluated in line (`here`), 0 for a dead row and for a stashed one (phase B's)
+__device__ __forceinline__ void defer_colours(const ViewWs& vw, float* vreg, const TileRow& t, bool here, float c0, float c1, float c2) {
+    if (t.live && t.h == 0) {
+        float* c = vw_c(vw, vreg);
+        c[t.s] = here ? c0 : 0.f; c[vw.sp + t.s] = here ? c1 : 0.f; c[2 * vw.sp + t.s] = here ? c2 : 0.f;
+    }
+}
+
 // PREC: 0 = fp32 MFMA (mlp_core.h, the parity path); 3 = bf16x3, 1 = plain bf16 (mlp_core_x3.h; static net, inference)
 // VIEWS = false: the net without view directions (SWNERF_NET_NOVIEW; model.py:59-60, 8-column ray batch nerf/run.py:152-157):
-// the trunk, then output_linear as VALU heads - no feature / view branch, no gamma(d).  Static net, fp32, inference.
+// the trunk, then output_linear as VALU heads - no feature / view branch, no gamma(d).  Static net, fp32, inference or TRAIN.
 template <bool DNERF, bool TRAIN = false, int PREC = 0, bool VIEWS = true>
 __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     static_assert(PREC == 0 || !TRAIN, "the bf16 paths cover the inference passes");
@@ -343,19 +348,14 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
 
     const int S = a.n_samples;
     const bool resample = a.n_importance > 0;
-    const float* rb = a.ray_batch + ray * a.cols;
-    const float ox = rb[0], oy = rb[1], oz = rb[2], dx = rb[3], dy = rb[4], dz = rb[5];
-    const float near = rb[6], far = rb[7];
-    const float ft = (a.cols == 12) ? rb[8] : 0.f;
-    const float v0 = VIEWS ? rb[a.cols - 3] : 0.f, v1 = VIEWS ? rb[a.cols - 2] : 0.f, v2 = VIEWS ? rb[a.cols - 1] : 0.f;
-    const float dnorm = row_dnorm(ox, oy, oz, dx, dy, dz, near, far, ft);    // ray.py:173; NaN for a row that is not finite
+    const RayRow r = ray_row_load<VIEWS>(a.ray_batch + ray * a.cols, a.cols);
 
     WStream ws;
     XStream xs;
     if constexpr (PREC != 0) {
         if (!DNERF) {         // once per ray: the view-direction encoding, parked in LDS (see tile_park)
             f32x16 demb;
-            pe_dir(v0, v1, v2, h, demb);
+            pe_dir(r.v[0], r.v[1], r.v[2], h, demb);
             tile_park(lds_dir, lane, demb);
         }
         x3_start(xs, reinterpret_cast<const char*>(P.w0), lds_bias, lds_ring, lane, wv);
@@ -366,13 +366,17 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         if constexpr (VIEWS) {
             // the stream's DIR prefix, once per ray: c = Wv[:, 256:] gamma(d) + b_vf -> the view layer's init tiles (mlp_core.h)
             f32x16 demb;
-            pe_dir(v0, v1, v2, h, demb);
-            if constexpr (TRAIN) tile_park(lds_dir, lane, demb);             // the training passes also store gamma(d) per row (xs)
-            view_bias_tile(demb, lds_vb, lane, ws);
+            pe_dir(r.v[0], r.v[1], r.v[2], h, demb);
+            if constexpr (TRAIN) tile_park(lds_dir, lane, demb);               // the training passes also store gamma(d) per row (xs)
+            ray_init_tile<4>(demb, lds_vb, lane, ws);
         }
         // D-NeRF with the deformation pass: the stream's TIME segment, once per ray: _time.0.bias + its gamma(t) columns (mlp_core.h)
         if constexpr (DNERF) {
-            if (P.time_steps) time_bias_tile(ft, h, lds_all + P.tb_off + wv * SW_TB_LDS_FLOATS, lane, ws);
+            if (P.time_steps) {
+                f32x16 temb;
+                pe_time(r.ft, h, temb);
+                ray_init_tile<8>(temb, lds_all + P.tb_off + wv * SW_TB_LDS_FLOATS, lane, ws);
+            }
         }
     }
 
@@ -382,7 +386,7 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     float pr = 0.f, pg = 0.f, pb = 0.f, pd = 0.f, pa = 0.f;
     double Tc = 1.0;                              // transmittance carried across tiles
     const int ntiles = (S + 31) >> 5;
-    // the deferred colour branch (top of this file); DEFER_OK = false compiles every line of it away
+    // the deferred colour branch (view_ws.h); DEFER_OK = false compiles every line of it away
     constexpr bool DEFER_OK = !DNERF && !TRAIN && PREC == 0 && VIEWS;
     const bool defer = DEFER_OK && P.vw.base != nullptr;
     float* vreg = defer ? vw_ray(P.vw, ray) : nullptr;                     // this ray's region of the workspace
@@ -395,6 +399,9 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
         const int s = tile * 32 + j;
         const bool live = s < S && !ghost;
         const int sc = live ? s : S - 1;
+        const TileRow t = {s, j, h, live};
+
+        // ---- depths
         float z, zn;
         if (zrow && tile > 0) {
             // depths given (fine pass): fetched by LDS-DMA while the previous tile's MLP ran - issued before that
@@ -404,220 +411,153 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
             const float z1 = zs[j + 1];
             zn = (s + 1 < S) ? z1 : z;
         } else {
-            z = z_sample(a, ray, near, far, sc);
-            zn = (s + 1 < S) ? z_sample(a, ray, near, far, s + 1) : z;
+            z = z_sample(a, ray, r.near, r.far, sc);
+            zn = (s + 1 < S) ? z_sample(a, ray, r.near, r.far, s + 1) : z;
         }
         if (zrow && tile + 1 < ntiles)
             lds_dma_dword(reinterpret_cast<const char*>(zrow), (unsigned)min(32 * (tile + 1) + lane, S - 1) * 4u,
                           zslot_addr + (unsigned)((tile + 1) & 1) * 256u);
-        // pts = rays_o + rays_d * z  (two roundings, nerf/run.py:385)
-        float px = ox + dx * z, py = oy + dy * z, pz = oz + dz * z;
 
-        f32x16 emb[2], in[8], out[8];
+        // ---- the net on pts = rays_o + rays_d * z  (two roundings, nerf/run.py:385): one branch per instantiation.  On leaving it
+        // head[0] = sigma; rgb = the raw colours, except in the fp32 inference passes with view directions, which leave `in` =
+        // relu(h7) to the colour stage below.  (In line ON PURPOSE: as one __forceinline__ function this stage moves the registers of five
+        // kernels, <true, true> 508 -> 504, <false, true> 420 -> 419, <true> 394 -> 392, the bf16 <true> pair +4 / +2 - profiles/pass_stages.md.)
+        f32x16 in[8];
         float head[3], rgb[3];
         float extra = 0.f;                          // VIEWS = false, out_ch == 5: the fifth channel of output_linear (only `raw` shows it)
+        float px = r.o[0] + r.d[0] * z, py = r.o[1] + r.d[1] * z, pz = r.o[2] + r.d[2] * z;
+        f32x16 emb[2], out[8];
         pe_pos(px, py, pz, h, emb);
-        if (DNERF && TRAIN) {
-            // deformation net, then the canonical net on gamma(x + dx) (model.py:128-151); both save what their dX
-            // chains and weight-gradient GEMMs need, as side stores (see the static branch below).  Always both passes:
-            // the t == 0 / zero_canonical case trains the canonical net alone through the static kernel.
-            const int64_t tix = ray * ntiles + tile, prow = tix * 32 + j;
-            float* act_row = P.act + prow * SW_ACT_LD + 4 * h;
-            float* mask_tile = P.bits + tix * SW_MASK_TILE_FLOATS + lane * 4;
-            float* xs_row = P.xs + prow * SW_XS_LD + 4 * h;
-            f32x4 mb = {0.f, 0.f, 0.f, 0.f};
-            f32x16 demb;
-            // ONE call site for both nets (a runtime loop like the inference kernel's): two would unroll the 8-layer body
-            // twice - 4800 static MFMAs, beyond what the instruction cache holds comfortably
-#pragma nounroll
-            for (int pass = 0; pass < 2; ++pass) {
-                const bool dp = pass == 0;
-                trunk_pass<true, true, true, false, true>(emb, lds_emb, ft, dp, h, in, out, head, ws,
-                                             dp ? P.act_d + prow * SW_ACT_LD + 4 * h : act_row,
-                                             dp ? P.bits_d + tix * SW_MASK_TILE_FLOATS + lane * 4 : mask_tile, dp, &mb,
-                                             dp ? P.xs_d + prow * SW_XS_LD + 4 * h : xs_row, lds_tb);
-                if (dp) {
-                    const float ex = head[0], ey = head[1], ez = head[2];
-                    if (live && h == 0) {
-                        float* o = a.dx + (ray * S + s) * 3;
-                        o[0] = ex; o[1] = ey; o[2] = ez;
-                    }
-                    px = px + ex; py = py + ey; pz = pz + ez;
-                    pe_pos(px, py, pz, h, emb);
-                    tile_fetch(lds_dir, lane, demb);
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 v = {demb[4 * g], demb[4 * g + 1], demb[4 * g + 2], demb[4 * g + 3]};
-                        *reinterpret_cast<f32x4*>(xs_row + 64 + 8 * g) = v;
-                    }
-                }
-            }
-            canon_tail_train(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws, act_row, mask_tile, mb);
-        } else if (DNERF && PREC != 0) {
-            if constexpr (DNERF && PREC != 0) {
-#pragma nounroll
-                for (int pass = P.two_pass ? 0 : 1; pass < 2; ++pass) {
-                    x3_net_dn_pipe<PREC>(px, py, pz, ft, pass == 0, h, v0, v1, v2, head, rgb, xs);
-                    if (pass == 0) {
-                        const float ex = head[0], ey = head[1], ez = head[2];
-                        if (a.dx && live && h == 0) {
-                            float* o = a.dx + (ray * S + s) * 3;
-                            o[0] = ex; o[1] = ey; o[2] = ez;
-                        }
-                        px = px + ex; py = py + ey; pz = pz + ez;        // re-embedded inside the canonical pass
-                    }
-                }
-                if (!P.two_pass && a.dx && live && h == 0) {
-                    float* o = a.dx + (ray * S + s) * 3;
-                    o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
-                }
-                x3_rewind(xs, P.two_pass ? SW_X3_DEFORM_CHUNKS + SW_X3_CANON_CHUNKS : SW_X3_CANON_CHUNKS, lds_bias, lane);
-            }
-        } else if (DNERF) {
+        if constexpr (DNERF && PREC != 0) {
+            // (the dx stores stay in line here: with pass_store_dx the two bf16 D-NeRF kernels went from 425 / 449 to 420 / 443 registers)
 #pragma nounroll
             for (int pass = P.two_pass ? 0 : 1; pass < 2; ++pass) {
-                trunk_pass<true, false, false, false, true>(emb, lds_emb, ft, pass == 0, h, in, out, head, ws, nullptr, nullptr, false, nullptr, nullptr, lds_tb);
+                x3_net_dn_pipe<PREC>(px, py, pz, r.ft, pass == 0, h, r.v[0], r.v[1], r.v[2], head, rgb, xs);
                 if (pass == 0) {
-                    // dx = _time_out(h) (model.py:136,146-149)
                     const float ex = head[0], ey = head[1], ez = head[2];
                     if (a.dx && live && h == 0) {
                         float* o = a.dx + (ray * S + s) * 3;
                         o[0] = ex; o[1] = ey; o[2] = ez;
                     }
-                    px = px + ex; py = py + ey; pz = pz + ez;
-                    pe_pos(px, py, pz, h, emb);                              // re-embed (model.py:148-149)
+                    px = px + ex; py = py + ey; pz = pz + ez;            // re-embedded inside the canonical pass
                 }
             }
             if (!P.two_pass && a.dx && live && h == 0) {
                 float* o = a.dx + (ray * S + s) * 3;
-                o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;                          // model.py:144-145
+                o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
             }
-        } else if (TRAIN && !VIEWS) {
-            // the net without view directions under autograd: the trunk's side stores as below (gamma(x) with layer 0, h_l and
-            // its mask with layer l+1), h7 stored on the spot (no segment follows it), then output_linear as VALU heads
-            const int64_t prow = (ray * ntiles + tile) * 32 + j;
-            float* act_row = P.act + prow * SW_ACT_LD + 4 * h;
-            float* mask_tile = P.bits + (ray * ntiles + tile) * SW_MASK_TILE_FLOATS + lane * 4;
-            float* xs_row = P.xs + prow * SW_XS_LD + 4 * h;
-            f32x4 mb = {0.f, 0.f, 0.f, 0.f};
-            trunk_pass<false, true, true, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws, act_row, mask_tile, true, &mb, xs_row);
-            float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            head_valu_rt<8>(in, ws, a.out_ch, o5);
-            rgb[0] = o5[0] + ws.bias[0]; rgb[1] = o5[1] + ws.bias[1]; rgb[2] = o5[2] + ws.bias[2];
-            head[0] = o5[3] + ws.bias[3]; head[1] = 0.f; head[2] = 0.f;
-            extra = o5[4] + ws.bias[4];
-        } else if (TRAIN) {
-            // the same tile, and everything the backward needs goes out as side stores of the segments (mlp_core.h
-            // SideStore): gamma(x) with layer 0, h_l and its ReLU mask with layer l+1 (h7 with the view layer)
-            const int64_t prow = (ray * ntiles + tile) * 32 + j;
-            float* act_row = P.act + prow * SW_ACT_LD + 4 * h;
-            float* mask_tile = P.bits + (ray * ntiles + tile) * SW_MASK_TILE_FLOATS + lane * 4;
-            float* xs_row = P.xs + prow * SW_XS_LD + 4 * h;
-            f32x4 mb = {0.f, 0.f, 0.f, 0.f};
-            f32x16 demb;
-            tile_fetch(lds_dir, lane, demb);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {                                    // gamma(d): k-tile 2 of the slot-ordered row
-                const f32x4 v = {demb[4 * g], demb[4 * g + 1], demb[4 * g + 2], demb[4 * g + 3]};
-                *reinterpret_cast<f32x4*>(xs_row + 64 + 8 * g) = v;
+            x3_rewind(xs, P.two_pass ? SW_X3_DEFORM_CHUNKS + SW_X3_CANON_CHUNKS : SW_X3_CANON_CHUNKS, lds_bias, lane);
+        } else if constexpr (DNERF) {
+            // deformation net, then the canonical net on gamma(x + dx) (model.py:128-151).  TRAIN: always both passes (the t == 0 /
+            // zero_canonical case trains the canonical net alone through the static kernel), and both nets save what their dX
+            // chains and weight-gradient GEMMs need, as side stores (see the static branch below).
+            TrainRows rc = {}, rd = {};             // the canonical net's rows, the deformation net's
+            if constexpr (TRAIN) {
+                rc = train_rows(P.act, P.bits, P.xs, ray * ntiles + tile, j, h, lane);
+                rd = train_rows(P.act_d, P.bits_d, P.xs_d, ray * ntiles + tile, j, h, lane);
             }
-            trunk_pass<false, true, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws, act_row, mask_tile, false, &mb, xs_row);
-            canon_tail_train(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws, act_row, mask_tile, mb);
+            f32x4 mb = {0.f, 0.f, 0.f, 0.f};
+            // ONE call site for both nets (a runtime loop): two would unroll the 8-layer body twice - 4800 static MFMAs, beyond
+            // what the instruction cache holds comfortably
+#pragma nounroll
+            for (int pass = (TRAIN || P.two_pass) ? 0 : 1; pass < 2; ++pass) {
+                const bool dp = pass == 0;
+                trunk_pass_flat<true, TRAIN, TRAIN, false, true, false>(emb, lds_emb, r.ft, dp, h, in, out, head, ws,      // flat: see mlp_core.h
+                                             dp ? rd.act_row : rc.act_row, dp ? rd.mask_tile : rc.mask_tile, dp, &mb,
+                                             dp ? rd.xs_row : rc.xs_row, lds_tb, nullptr);
+                if (dp) {
+                    // dx = _time_out(h) (model.py:136,146-149)
+                    const float ex = head[0], ey = head[1], ez = head[2];
+                    if (TRAIN || a.dx) pass_store_dx(a, ray, s, live, h, ex, ey, ez);
+                    px = px + ex; py = py + ey; pz = pz + ez;
+                    pe_pos(px, py, pz, h, emb);                              // re-embed (model.py:148-149)
+                    if constexpr (TRAIN) {
+                        f32x16 demb;
+                        tile_fetch(lds_dir, lane, demb);
+                        xs_store_tile(rc.xs_row + 64, demb);
+                    }
+                }
+            }
+            if constexpr (TRAIN) canon_tail<true>(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws, TrunkSide{rc.act_row, rc.mask_tile, false, &mb, rc.xs_row});
+            else if (!P.two_pass && a.dx) pass_store_dx(a, ray, s, live, h, 0.f, 0.f, 0.f);       // model.py:144-145
         } else if constexpr (PREC != 0) {
             head[1] = 0.f; head[2] = 0.f;
             x3_canon_pipe<PREC>(px, py, pz, h, lds_dir, lane, head[0], rgb, xs);
             x3_rewind(xs, SW_X3_CANON_CHUNKS, lds_bias, lane);
-        } else if constexpr (!VIEWS) {
-            trunk_pass<false, false, false, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws);
-            // outputs = output_linear(h) (model.py:59-60): [rgb(3), sigma, (5th, unused by raw2outputs)]
-            float o5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            const int nout = (a.out_ch == 5 && !a.raw) ? 4 : a.out_ch;              // the fifth channel only shows in `raw`
-            head_valu_rt<8>(in, ws, nout, o5);
-            ws.bias += (a.out_ch - nout) * 8 * SW_BIAS_TILE_FLOATS;                 // skip the weight tiles of a channel not evaluated
-            rgb[0] = o5[0] + ws.bias[0]; rgb[1] = o5[1] + ws.bias[1]; rgb[2] = o5[2] + ws.bias[2];
-            head[0] = o5[3] + ws.bias[3]; head[1] = 0.f; head[2] = 0.f;
-            extra = o5[4] + ws.bias[4];
         } else {
-            // a tile that leaves the view segment out continues at the head of MAIN behind layer 7
-            trunk_pass<false, false, false, false, false, true>(emb, lds_emb, 0.f, false, h, in, out, head, ws, nullptr, nullptr, false,
-                                                                nullptr, nullptr, nullptr, stash ? main_head : nullptr);
+            // the static fp32 net.  TRAIN: everything the backward needs goes out as side stores of the segments (mlp_core.h
+            // SideStore): gamma(x) with layer 0, h_l and its ReLU mask with layer l+1, h7 with the view layer (VIEWS = false: on the
+            // spot, no segment follows it), gamma(d) here.  Inference with view directions: a tile that leaves the view segment out
+            // continues at the head of MAIN behind layer 7.
+            f32x4 mb = {0.f, 0.f, 0.f, 0.f};
+            TrunkSide side = {};
+            if constexpr (TRAIN) {
+                const TrainRows rc = train_rows(P.act, P.bits, P.xs, ray * ntiles + tile, j, h, lane);
+                side = TrunkSide{rc.act_row, rc.mask_tile, !VIEWS, &mb, rc.xs_row};
+                if constexpr (VIEWS) {
+                    f32x16 demb;
+                    tile_fetch(lds_dir, lane, demb);
+                    xs_store_tile(side.xs_row + 64, demb);                   // gamma(d): k-tile 2 of the slot-ordered row
+                }
+            }
+            trunk_pass<false, TRAIN, TRAIN, !VIEWS, false, !TRAIN && VIEWS>(emb, lds_emb, 0.f, false, h, in, out, head, ws, side, nullptr,
+                                                                            stash ? main_head : nullptr);
+            // outputs = output_linear(h) (model.py:59-60): [rgb(3), sigma, (5th: only `raw` of an inference launch shows it)]
+            if constexpr (!VIEWS) noview_heads(in, ws, (!TRAIN && a.out_ch == 5 && !a.raw) ? 4 : a.out_ch, a.out_ch, rgb, head, extra);
+            else if constexpr (TRAIN) canon_tail<true>(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws, side);
         }
 
-        // ---- raw2outputs on this tile (composite.h), the density side; both lane halves mirror each other
+        // ---- raw2outputs on this tile, the density side
         const float sg_raw = head[0];
-        float sg = sg_raw;
-        if (a.noise) sg += a.noise[ray * S + sc];
-        const float alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live);
-        const float w = alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
+        float alpha;
+        const float w = pass_weight(a, ray, s, sc, live, j, sg_raw, z, zn, r.dnorm, Tc, alpha);
         if (live) {
-            if (a.weights && h == 0) a.weights[ray * S + s] = w;
-            if (a.z_out && h == 0) a.z_out[ray * S + s] = z;
+            pass_store_wz(a, ray, s, h, w, z);
             if (resample && h == 0) { zc[s] = z; wc[s] = w; }
         }
         comp_accumulate_density(w, z, pd, pa);
 
-        // ---- the deferred colour branch: the tile's live rows go to the ray's region, packed in sample order
+        // ---- the colour branch of the fp32 inference passes with view directions: stashed for phase B, or in line
         bool lit = live;                             // this row's colour enters the outputs
         if constexpr (DEFER_OK) {
             if (defer) {
                 lit = live && (!(alpha == 0.f) || s == 0);
-                if (live && h == 0) vw_w(P.vw, vreg)[s] = w;
-                if (stash) {
-                    const unsigned m = (unsigned)__ballot(lit);          // lanes 0..31: one bit per row
-                    const int slot = wr + __popc(m & ((1u << j) - 1u));
-                    if (lit) {
-                        if (h == 0) vw_sample(P.vw, vreg)[slot] = s;
-                        float* q = vw_row(P.vw, vreg, slot, h);
-                        const int gs = vw_group_stride(P.vw);
-#pragma unroll
-                        for (int c = 0; c < 32; ++c) {
-                            const f32x4 v = {in[c >> 2][4 * (c & 3)], in[c >> 2][4 * (c & 3) + 1], in[c >> 2][4 * (c & 3) + 2], in[c >> 2][4 * (c & 3) + 3]};
-                            *reinterpret_cast<f32x4*>(q + (size_t)c * gs) = v;
-                        }
-                    }
-                    wr += __builtin_amdgcn_readfirstlane(__popc(m));
-                }
+                if (live && h == 0) vw_w(vreg)[s] = w;
+                if (stash) wr += defer_stash(P.vw, vreg, in, lit, wr, t);
             }
         }
-        if (!TRAIN && PREC == 0 && VIEWS) {
+        if constexpr (!TRAIN && PREC == 0 && VIEWS) {
             if (!stash) {
                 if constexpr (DEFER_OK) ws.cont = ws.base + SW_STEPS_VIEWSH * 1024;
-                canon_tail<DEFER_OK>(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws);
+                canon_tail<false, DEFER_OK>(in, lds_vb, rgb, ws.bias - SW_BIAS_TILE_FLOATS, ws);
             } else {
                 rgb[0] = 0.f; rgb[1] = 0.f; rgb[2] = 0.f;
             }
         }
-        // back to the head of MAIN (behind the per-ray DIR prefix and its b_vf tiles)
-        if constexpr (PREC == 0) {               // back to MAIN: behind the per-ray prefixes (DIR, and TIME with its 8 bias tiles)
+        if constexpr (PREC == 0) {               // back to the head of MAIN: behind the per-ray prefixes (DIR with its b_vf tiles, TIME with its 8 bias tiles)
             ws_rewind(ws, P.w0 + (P.dir_steps + P.time_steps) * SW_STEP_FLOATS,
                       lds_bias + ((P.dir_steps ? SW_DIR_BIAS_TILES : 0) + (P.time_steps ? 8 : 0)) * SW_BIAS_TILE_FLOATS, lane);
         }
 
-        // ---- the colour side
+        // ---- outputs: the colours to the ray's region (phase B adds the stashed rows', phase C forms the sums), or raw and the colour sums
         const float c0 = rgb[0], c1 = rgb[1], c2 = rgb[2];
-        if (DEFER_OK && defer) {                 // a stashed row's colour: phase B; the sums: phase C
-            if (live && h == 0) {
-                float* c = vw_c(P.vw, vreg);
-                const bool here = lit && !stash;
-                c[s] = here ? c0 : 0.f; c[P.vw.sp + s] = here ? c1 : 0.f; c[2 * P.vw.sp + s] = here ? c2 : 0.f;
+        if (DEFER_OK && defer) {
+            defer_colours(P.vw, vreg, t, lit && !stash, c0, c1, c2);
+        } else {
+            if (a.raw && live && h == 0) {
+                if (!VIEWS && a.out_ch == 5) {
+                    float* o = a.raw + (ray * S + s) * 5;
+                    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = sg_raw; o[4] = extra;
+                } else {
+                    f32x4 r4 = {c0, c1, c2, sg_raw};
+                    *reinterpret_cast<f32x4*>(a.raw + (ray * S + s) * 4) = r4;
+                }
             }
-            continue;
+            comp_accumulate_colour(w, c0, c1, c2, pr, pg, pb);
         }
-        if (a.raw && live && h == 0) {
-            if (!VIEWS && a.out_ch == 5) {
-                float* o = a.raw + (ray * S + s) * 5;
-                o[0] = c0; o[1] = c1; o[2] = c2; o[3] = sg_raw; o[4] = extra;
-            } else {
-                f32x4 r4 = {c0, c1, c2, sg_raw};
-                *reinterpret_cast<f32x4*>(a.raw + (ray * S + s) * 4) = r4;
-            }
-        }
-        comp_accumulate_colour(w, c0, c1, c2, pr, pg, pb);
     }
 
-    pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
-    pd = wave32_sum(pd); pa = wave32_sum(pa);
-    if (lane == 0 && !ghost) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, defer ? nullptr : a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
+    pass_write_maps(pr, pg, pb, pd, pa, lane, ghost, a, ray, defer ? nullptr : a.rgb_map);
     if constexpr (DEFER_OK) {
         if (defer && lane == 0) { vw_off(P.vw)[ray] = wr; vreg[0] = pa; }
     }
@@ -634,4 +574,3 @@ __global__ void __launch_bounds__(256, 1) render_pass_kernel(PassDev P) {
     }
     wave_rank_merge(zc, S, P.sort_s, srt, Ni, P.sort_n, a.z_fine + ray * (S + Ni), lane);
 }
-

@@ -60,7 +60,7 @@
 //   bias tiles: 64 (the first 8 consumed by TIME) | _time_out.weight 3 x 8 | 1 head-bias tile.
 // _time.0's gamma(t) columns are a per-RAY constant in the fused passes (one frame time per ray, run_dnerf.py:354-360): the D-NeRF
 // blob reads DIR | TIME | MAIN = D0 .. D7 | canonical MAIN, TIME is evaluated once per ray into a per-wave LDS tile
-// (mlp_core.h time_bias_tile) and every tile's D0 accumulators start from it; a tile rewinds to D0.  Kernels whose time varies
+// (mlp_core.h ray_init_tile) and every tile's D0 accumulators start from it; a tile rewinds to D0.  Kernels whose time varies
 // per row (mlp_forward, the op path's training forward) run TIME and D0 in line.
 #define SW_DEFORM_STEPS (SW_STEPS_EMB_T + 4 * SW_STEPS_TRUNK + SW_STEPS_TRUNK + SW_STEPS_EMB + 2 * SW_STEPS_TRUNK)
 #define SW_DEFORM_BIAS_TILES (8 + 32 + 8 + 16 + 24 + 1)

@@ -40,7 +40,7 @@ int sw_tnerf_render_launch(const swnerf_pass_args& a, hipStream_t st) {
 // TNeRF.forward on bare points at ONE frame time with V view directions shared by every point (the grid query of mesh
 // extraction, nerf/extract_mesh.py:27-90, through t_nerf/run_tnerf.py run_network :48-87): one wave per 32 points.  The time is a
 // constant of the launch, so the T0 / T5 tiles are evaluated once per wave; the trunk and the density once per point; per
-// direction v the DIR tile (a shared direction is constant over the wave's 32 rows: tn_ray_tile on gamma(d_v)), the folded layer_9
+// direction v the DIR tile (a shared direction is constant over the wave's 32 rows: ray_init_tile on gamma(d_v)), the folded layer_9
 // (ELU) and `color` (ReLU), summed in direction order.  Direction 0 runs in stream order (its DIR segment sits between T5 and
 // MAIN, layer_9 behind layer 7); every further direction leaves the stream twice (ws_restart onto DIR, then onto layer_9: two
 // exposed L2 round trips per 160 MFMAs - the stream has no loop form of the colour branch).  Same LDS layout as the pass.
@@ -70,10 +70,10 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_query_kernel(
     {
         f32x16 k;
         pe_time(P.ft, h, k);
-        tn_ray_tile<4>(k, lds_t0, lane, ws);     // T0: layers.0 bias + its gamma(t) columns
-        tn_ray_tile<4>(k, lds_t5, lane, ws);     // T5: layers.5 bias + its gamma(t) columns
+        ray_init_tile<4>(k, lds_t0, lane, ws);     // T0: layers.0 bias + its gamma(t) columns
+        ray_init_tile<4>(k, lds_t5, lane, ws);     // T5: layers.5 bias + its gamma(t) columns
         pe_dir(P.dirs[0], P.dirs[1], P.dirs[2], h, k);
-        tn_ray_tile<2>(k, lds_vb, lane, ws);     // DIR of direction 0: b9f + layer_9's gamma(d) columns
+        ray_init_tile<2>(k, lds_vb, lane, ws);     // DIR of direction 0: b9f + layer_9's gamma(d) columns
     }
     const float* main_b = lds_all + SW_TN_PREFIX_BIAS_TILES * SW_BIAS_TILE_FLOATS;
     const float* dir_w = P.w0 + (SW_TN_STEPS_T0 + SW_TN_STEPS_T5) * SW_STEP_FLOATS;
@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_query_kernel(
             pe_dir(P.dirs[v * 3], P.dirs[v * 3 + 1], P.dirs[v * 3 + 2], h, k);
             ws_restart(ws, dir_w);
             ws.bias = lds_all + (SW_TN_PREFIX_BIAS_TILES - 2) * SW_BIAS_TILE_FLOATS + h * 16;      // the b9f tiles
-            tn_ray_tile<2>(k, lds_vb, lane, ws);
+            ray_init_tile<2>(k, lds_vb, lane, ws);
             ws_restart(ws, l9_w);
         }
         f32x16 hv[2];

@@ -15,27 +15,6 @@
 #define SW_TN_WAVE_FLOATS (SW_RING * SW_STEP_FLOATS + 2 * 16 * 64 + SW_TN_PREFIX_BIAS_TILES * SW_BIAS_TILE_FLOATS)
 #define SW_TN_LDS_FLOATS (SW_TN_BIAS_TILES * SW_BIAS_TILE_FLOATS + 4 * SW_TN_WAVE_FLOATS)
 
-// once per ray: c = bias + W[:, cols of k] . k  for the ray-constant k-tile `k` (every column j of the result is the same)
-// -> lds_t[n][h][r], the accumulator-init layout of a bias tile
-template <int NT>
-__device__ __forceinline__ void tn_ray_tile(const f32x16& k, float* lds_t, int lane, WStream& ws) {
-    f32x16 k1[1], c[NT];
-    k1[0] = k;
-    seg_mfma<NT, 1, SEG_BIAS>(c, k1, ws);
-    if ((lane & 31) == 0) {
-        float* o = lds_t + (lane >> 5) * 16;
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v = {c[n][4 * g], c[n][4 * g + 1], c[n][4 * g + 2], c[n][4 * g + 3]};
-                *reinterpret_cast<f32x4*>(o + n * SW_BIAS_TILE_FLOATS + 4 * g) = v;
-            }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <int NT>
 __device__ __forceinline__ void elu_tiles(const f32x16 (&x)[NT], f32x16 (&y)[NT]) {
 #pragma unroll
@@ -47,14 +26,8 @@ __device__ __forceinline__ void elu_tiles(const f32x16 (&x)[NT], f32x16 (&y)[NT]
 // a ray-constant encoding tile (gamma(t) or gamma(d)) into xs columns col0.. of every padded row of the ray (TRAIN)
 __device__ __forceinline__ void tn_xs_ray_tile(const f32x16& k, float* xs_ray, int ntiles, int col0, int j, int h) {
 #pragma nounroll
-    for (int tile = 0; tile < ntiles; ++tile) {
-        float* o = xs_ray + ((int64_t)tile * 32 + j) * SW_TN_XS_LD + col0 + 4 * h;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = {k[4 * g], k[4 * g + 1], k[4 * g + 2], k[4 * g + 3]};
-            *reinterpret_cast<f32x4*>(o + 8 * g) = v;
-        }
-    }
+    for (int tile = 0; tile < ntiles; ++tile)
+        xs_store_tile(xs_ray + ((int64_t)tile * 32 + j) * SW_TN_XS_LD + col0 + 4 * h, k);
 }
 
 template <bool TRAIN>
@@ -75,22 +48,21 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_render_kernel
 
     const int S = a.n_samples;
     const float* rb = a.ray_batch + ray * 12;    // [o, d, near, far, t, viewdirs] (run_tnerf.py:156-164)
-    const float ox = rb[0], oy = rb[1], oz = rb[2], dx = rb[3], dy = rb[4], dz = rb[5];
-    const float near = rb[6], far = rb[7], ft = rb[8];
-    const float dnorm = row_dnorm(ox, oy, oz, dx, dy, dz, near, far, ft);    // run_tnerf.py:362; NaN for a row that is not finite
+    // (the directions are read where pe_dir needs them, behind T0 / T5: loaded here with the row they merge into one wider load - 228 -> 227 global_*)
+    const RayRow r = ray_row_load<false>(rb, 12);
 
     const int ntiles = (S + 31) >> 5;
     WStream ws;
     ws_start(ws, P.w0, lds_all, lds_ring, lane);
     {
         f32x16 k;
-        pe_time(ft, h, k);
+        pe_time(r.ft, h, k);
         if constexpr (TRAIN) tn_xs_ray_tile(k, P.xs + ray * ntiles * 32 * SW_TN_XS_LD, ntiles, 64, j, h);
-        tn_ray_tile<4>(k, lds_t0, lane, ws);     // T0: layers.0 bias + its gamma(t) columns
-        tn_ray_tile<4>(k, lds_t5, lane, ws);     // T5: layers.5 bias + its gamma(t) columns
+        ray_init_tile<4>(k, lds_t0, lane, ws);     // T0: layers.0 bias + its gamma(t) columns
+        ray_init_tile<4>(k, lds_t5, lane, ws);     // T5: layers.5 bias + its gamma(t) columns
         pe_dir(rb[9], rb[10], rb[11], h, k);
         if constexpr (TRAIN) tn_xs_ray_tile(k, P.xs + ray * ntiles * 32 * SW_TN_XS_LD, ntiles, 96, j, h);
-        tn_ray_tile<2>(k, lds_vb, lane, ws);     // DIR: b9f + layer_9's gamma(d) columns
+        ray_init_tile<2>(k, lds_vb, lane, ws);     // DIR: b9f + layer_9's gamma(d) columns
     }
     const float* main_w = P.w0 + SW_TN_PREFIX_STEPS * SW_STEP_FLOATS;
     const float* main_b = lds_all + SW_TN_PREFIX_BIAS_TILES * SW_BIAS_TILE_FLOATS;
@@ -109,11 +81,11 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_render_kernel
             z = zrow[sc];
             zn = (s + 1 < S) ? zrow[s + 1] : z;
         } else {
-            z = z_sample(a, ray, near, far, sc);
-            zn = (s + 1 < S) ? z_sample(a, ray, near, far, s + 1) : z;
+            z = z_sample(a, ray, r.near, r.far, sc);
+            zn = (s + 1 < S) ? z_sample(a, ray, r.near, r.far, s + 1) : z;
         }
         // pts = rays_o + rays_d * z  (two roundings, run_tnerf.py:477)
-        const float px = ox + dx * z, py = oy + dy * z, pz = oz + dz * z;
+        const float px = r.o[0] + r.d[0] * z, py = r.o[1] + r.d[1] * z, pz = r.o[2] + r.d[2] * z;
 
         f32x16 emb[2], in[4], out[4], hv[2];
         pe_pos(px, py, pz, h, emb);
@@ -168,17 +140,11 @@ __global__ void __launch_bounds__(256, SW_TN_WAVES_PER_SIMD) tnerf_render_kernel
             f32x4 r4 = {c0, c1, c2, sg};
             *reinterpret_cast<f32x4*>(a.raw + (ray * S + s) * 4) = r4;
         }
-        if (a.noise) sg += a.noise[ray * S + sc];
-        const float alpha = comp_alpha(sg, comp_dist(s + 1 < S, zn, z, dnorm), live);
-        const float w = alpha * comp_transmittance(excl_cumprod_shfl<32>(comp_survival(alpha), j), Tc);
-        if (live && h == 0) {
-            if (a.weights) a.weights[ray * S + s] = w;
-            if (a.z_out) a.z_out[ray * S + s] = z;
-        }
+        float alpha;
+        const float w = pass_weight(a, ray, s, sc, live, j, sg, z, zn, r.dnorm, Tc, alpha);
+        if (live) pass_store_wz(a, ray, s, h, w, z);
         comp_accumulate(w, c0, c1, c2, z, pr, pg, pb, pd, pa);
     }
 
-    pr = wave32_sum(pr); pg = wave32_sum(pg); pb = wave32_sum(pb);
-    pd = wave32_sum(pd); pa = wave32_sum(pa);
-    if (lane == 0) comp_write_maps(pr, pg, pb, pd, pa, a.white_bkgd, ray, a.rgb_map, a.disp_map, a.acc_map, a.depth_map);
+    pass_write_maps(pr, pg, pb, pd, pa, lane, false, a, ray, a.rgb_map);
 }

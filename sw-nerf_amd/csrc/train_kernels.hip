@@ -156,8 +156,8 @@ __global__ void __launch_bounds__(256, 1) deform_forward_train_kernel(DeformDev 
     const float ft = P.t_emb[rt.rr * P.Ct];                                // column 0 of gamma(t) is t
     WStream ws;
     ws_start(ws, P.w0 + SW_STEPS_DIR * SW_STEP_FLOATS, lds_bias + SW_DIR_BIAS_TILES * SW_BIAS_TILE_FLOATS, rt.lds_ring, rt.lane);   // (behind the per-ray DIR prefix)
-    trunk_pass<true, true>(emb, rt.lds_emb, ft, true, rt.h, in, out, head, ws, P.act + rt.rr * SW_ACT_LD + 4 * rt.h,
-                           P.bits + rt.tile * SW_MASK_TILE_FLOATS + rt.lane * 4, true, nullptr);
+    const TrunkSide side = {P.act + rt.rr * SW_ACT_LD + 4 * rt.h, P.bits + rt.tile * SW_MASK_TILE_FLOATS + rt.lane * 4, true, nullptr, nullptr};
+    trunk_pass<true, true>(emb, rt.lds_emb, ft, true, rt.h, in, out, head, ws, side);
     if (rt.live && rt.h == 0) { P.dx[rt.row * 3] = head[0]; P.dx[rt.row * 3 + 1] = head[1]; P.dx[rt.row * 3 + 2] = head[2]; }
 }
 

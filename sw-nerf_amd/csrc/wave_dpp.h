@@ -73,3 +73,10 @@ __device__ __forceinline__ float wave_sum_to_last_f32(float v) {
     return v;
 }
 __device__ __forceinline__ double wave_sum_to_last_f64(double v) { return wave_incl_sum_f64(v); }
+
+// sum over the 32 lanes of each half of the wave, in every lane (xor butterfly through the LDS pipe: the fused passes' maps)
+__device__ __forceinline__ float wave32_sum(float v) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
+    return v;
+}
