@@ -1015,6 +1015,64 @@ int     swnerf_mesh_fill_emit(const float* verts, const int32_t* faces, const fl
                               const int32_t* loop_fnew, int64_t L, int64_t M, void* workspace, int64_t V_out, int64_t F_out,
                               float* verts_out, int32_t* faces_out, float* colors_out, int32_t* status, void* stream);
 
+/* ---- mesh rendering from the project's cameras (what a trimesh user does with mesh.obj in a viewer, and the check of a mesh against
+ * the frames and depth maps it was made from; csrc/meshrender_math.h, meshrender_kernels.hip, DESIGN.md 6b "Mesh rendering";
+ * tests/meshrender_ref.py is the numpy replay) ------------------------------------------------------------------------------------
+ * This block was added without a step of SWNERF_VERSION, like the hole-filling block: it only adds entry points.
+ * The same conventions as above (nothing allocated, no host synchronisation, integer atomics only, nothing depends on scheduling,
+ * the inputs are never written).  verts / faces as above; normals, colors = DEVICE float32 [V,3]; c2w = DEVICE float32 [N,3,4] as
+ * in swnerf_train_batch; H, W, fx, fy, cx, cy, focal_branch as in swnerf_get_rays (NDC cameras are not rendered).  N H W < 2^31.
+ * workspace = DEVICE, 8-byte aligned, swnerf_mesh_render_workspace_bytes(N, H, W) bytes: the z-buffer, one 64-bit word per pixel
+ *   (0 for refused sizes - a negative N, H or W < 1, N H W >= 2^31 - else a multiple of 256).
+ * The ray of pixel (px, py) of view n: d = the float32 rays_d swnerf_get_rays writes for it, bit for bit, o = c2w[n][:, 3], both
+ *   widened to fp64.  For the face (v0, v1, v2): A = v0 - o, B = v1 - o, C = v2 - o, E(p, q) = d0 (p1 q2 - p2 q1) + d1 (p2 q0 - p0 q2)
+ *   + d2 (p0 q1 - p1 q0) added left to right, U = E(B, C), V = E(C, A), W = E(A, B), det = (U + V) + W.  The ray hits the face iff
+ *   det != 0 and U, V, W are all >= 0 or all <= 0.  E(q, p) = -E(p, q) exactly, so the two faces at an edge agree about it: no
+ *   pinholes; a ray through an edge or a vertex hits every face around it.  t = ((U (A.d) + V (B.d)) + W (C.d)) / det / (d.d), rounded
+ *   once to float32: depth is t along the UNNORMALISED rays_d, the unit of the depth_map of a non-NDC render.  A hit counts iff
+ *   t_f is finite and near < t_f <= far (0 <= near < far; far may be +inf).  det < 0 is the outward (counter-clockwise) side; cull:
+ *   SWNERF_MESH_CULL_NONE, _BACK (drop det > 0), _FRONT (drop det < 0).  Barycentrics = (U, V, W) / det, each rounded once.
+ * A face with an index outside 0..V-1, a repeated index or a coordinate that is not finite is counted and never followed.
+ * mesh_render_raster: two memsets (counts, the z-buffer to all ones = empty) and one launch over the (view, face) pairs.  Each
+ *   pair's pixel box comes from its projected vertices (camera coordinates through the transpose of the rotation, dz = -z_c,
+ *   px = cx + fx x_c / dz, py = cy - fy y_c / dz, widened by a pixel, clamped; the whole image when the face straddles the camera
+ *   plane, a vertex is within 2^-12 of it relative to its distance, or the view's rotation is not orthonormal to 2^-20; nothing when
+ *   every vertex is behind).  A box of at most 64 pixels is walked by its own lane, a larger one by the 64 lanes of its wave.  Every
+ *   hit is one 64-bit atomicMin of (float bits of t_f) << 32 | face id: the nearest wins, the smallest face id on equal depth bits.
+ *   counts int64 [4] = {bad faces, (view, face) pairs behind the camera, pairs with a box above 64 pixels, hits}; all 0 for N = 0.
+ * mesh_render_resolve: one launch, one thread per pixel: decodes the face, recomputes U, V, W, det, t with the same function (the
+ *   depth bits equal the key's) and writes face int32 [N,H,W] (-1 at a miss) and, where the pointer is not NULL, depth [N,H,W] = t_f
+ *   (0 at a miss, as the depth_map of an empty ray), disp = 1 / t_f (0), acc = 1 (0), bary [N,H,W,3] (0), rgb [N,H,W,3]
+ *   (background, HOST float [3]) by `shading`:
+ *   SWNERF_MESH_SHADE_COLORS     the vertex colours by the fp64 barycentrics, clipped to [0, 1], one rounding (needs colors)
+ *   SWNERF_MESH_SHADE_NORMALS    the interpolated vertex normal, normalised (0 when it has no direction), as 0.5 n + 0.5 (needs normals)
+ *   SWNERF_MESH_SHADE_HEADLIGHT  the clipped colour (0.8 without colors) times |n . d / |d|| (needs normals)
+ * mesh_view_compare: acc / depth of a render against a reference.  ref_alpha = DEVICE float32 (alpha_u8 == 0; covered iff > 0.5) or
+ *   uint8 (covered iff >= 128), element alpha_stride * pixel + alpha_offset, so the alpha of [N,H,W,4] RGBA frames is read in place
+ *   (stride 4, offset 3); NULL: covered iff ref_depth > 0.  The mesh covers a pixel iff acc > 0.5.  counts int64 [N,4] = {intersection,
+ *   union, mesh pixels, reference pixels}; sums double [N,3] = {sum |depth - ref_depth|, sum (depth - ref_depth)^2, pixels} over
+ *   the pixels covered by both (0 when depth or ref_depth is NULL), in fp64: one workgroup of 1024 per view, lane l adds its terms
+ *   of pixels l, l + 1024, .. in order from 0.0, the lane sums fold in halves (s[l] += s[l + w], w = 512 .. 1): the same bits on
+ *   every run.  One launch. */
+#define SWNERF_MESH_CULL_NONE 0
+#define SWNERF_MESH_CULL_BACK 1
+#define SWNERF_MESH_CULL_FRONT 2
+#define SWNERF_MESH_SHADE_COLORS 0
+#define SWNERF_MESH_SHADE_NORMALS 1
+#define SWNERF_MESH_SHADE_HEADLIGHT 2
+int64_t swnerf_mesh_render_workspace_bytes(int64_t N, int64_t H, int64_t W);
+int     swnerf_mesh_render_raster(const float* verts, const int32_t* faces, int64_t V, int64_t F, const float* c2w, int64_t N, int H, int W,
+                                  double fx, double fy, double cx, double cy, int focal_branch, float near, float far, int cull,
+                                  void* workspace, int64_t* counts, void* stream);
+int     swnerf_mesh_render_resolve(const float* verts, const int32_t* faces, const float* normals /* may be NULL */,
+                                   const float* colors /* may be NULL */, int64_t V, int64_t F, const float* c2w, int64_t N, int H, int W,
+                                   double fx, double fy, double cx, double cy, int focal_branch, int shading,
+                                   const float* background /*HOST*/, const void* workspace, float* rgb, float* depth, float* disp,
+                                   float* acc, int32_t* face, float* bary, void* stream);
+int     swnerf_mesh_view_compare(const float* acc, const float* depth /* may be NULL */, const void* ref_alpha /* may be NULL */,
+                                 int alpha_u8, int64_t alpha_stride, int64_t alpha_offset, const float* ref_depth /* may be NULL */,
+                                 int64_t N, int64_t H, int64_t W, int64_t* counts, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

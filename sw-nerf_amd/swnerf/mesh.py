@@ -16,7 +16,8 @@ Clean-up and measurement of the extracted mesh (connected components, Taubin smo
 swnerf.meshops and re-exported here: `components`, `keep_components`, `vertex_faces`, `smooth`, `vertex_normals`, `measure`,
 `clean`, and the `clean=` keyword of `generate_mesh` / `nerf_to_mesh`; so are welding and decimation by vertex clustering:
 `cluster`, `weld`, `decimate`, `decimation_cell` (and the `weld` / `decimate` keys of `clean`), and hole filling: `boundary_loops`,
-`fill_holes` (and the `fill_holes` key of `clean`)."""
+`fill_holes` (and the `fill_holes` key of `clean`).  Rendering a mesh from the project's cameras and checking it against reference
+silhouettes and depth maps are in swnerf.meshrender and re-exported here: `render_views`, `render_views_arrays`, `compare_views`."""
 import ctypes
 
 import numpy as np
@@ -344,3 +345,4 @@ def mesh_sequence(net, bounds, times, resolution=64, density_threshold=8, num_vi
 from .meshops import (components, select_components, keep_components, vertex_faces, smooth_step, smooth, vertex_normals,  # noqa: E402,F401
                       measure, measure_raw, clean, Measurement, cluster, collapse_counts, weld, decimate, decimation_cell,
                       simplify_arrays, weld_arrays, decimate_arrays, boundary_loops, fill_holes, fill_holes_arrays)
+from .meshrender import render_views, render_views_arrays, compare_views  # noqa: E402,F401

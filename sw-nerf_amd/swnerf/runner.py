@@ -438,6 +438,73 @@ def evaluate_dir(files_dir, lpips_weights=None, args=None):
     return errors
 
 
+# ---- the extracted mesh from the project's cameras (swnerf.meshrender; DESIGN.md 6b "Mesh rendering") ------------------------
+def render_path_mesh(m, render_poses, hwf, K, savedir=None, render_factor=0, shading="headlight", video=False):
+    """The mesh twin of render.render_path: the mesh `m` (what mesh.render_views takes) from every pose of render_poses ([N,3,4] or
+    [N,4,4]) in one call -> (rgbs [N,H,W,3], disps [N,H,W]) as numpy arrays.  hwf, K and render_factor are render_path's (K = None:
+    the focal branch of hwf's focal).  With `savedir` every frame is written as '{:03d}.png' of to8b(rgb), and with video=True also
+    savedir/video.avi (swnerf.video.mimwrite, as render_test writes it).  A pixel no face covers is white with disparity 0."""
+    from . import meshrender
+    H, W, focal = hwf
+    H, W, focal = int(H), int(W), float(focal)
+    if render_factor != 0:
+        H, W, focal = H // render_factor, W // render_factor, focal / render_factor
+        if K is not None:
+            K = np.asarray(torch.as_tensor(K).cpu(), np.float64).copy()
+            K[:2] /= render_factor
+    if video and savedir is None:
+        raise ValueError("swnerf.runner.render_path_mesh: video=True needs a savedir")
+    out = meshrender.render_views(m, H, W, K, render_poses, shading=shading, white_bkgd=True, outputs=("rgb", "disp"), focal=focal)
+    rgbs, disps = out["rgb"].cpu().numpy(), out["disp"].cpu().numpy()
+    if savedir is not None:
+        os.makedirs(savedir, exist_ok=True)
+        for i, rgb in enumerate(rgbs):
+            write_png(os.path.join(savedir, '{:03d}.png'.format(i)), to8b(rgb))
+        if video:
+            mimwrite(os.path.join(savedir, 'video.avi'), rgbs, fps=30, quality=8)
+    return rgbs, disps
+
+
+_SPLIT_ROWS = {"train": 0, "val": 1, "test": 2}
+
+
+def evaluate_mesh(m, dataset, split="train", net_depths=None, savedir=None):
+    """A mesh against the data it was extracted from: `m` is rendered from the poses of one split of `dataset` (the dict of
+    data.load_dataset: images, poses, hwf, K, i_split) and its silhouette is compared with the alpha channel of the split's frames,
+    read where the loaders keep them (device uint8 or float32 RGBA; frames without an alpha channel count as covered everywhere).
+    net_depths: optionally the NeRF's depth_map of the same frames [n,H,W] (non-NDC rays: the unit of the mesh's depth), for the
+    depth error over the pixels both cover.  -> dict of per-frame lists: frame (the dataset index), iou, depth_mae, depth_rmse,
+    intersection, union, mesh_pixels, ref_pixels.  Nothing is written unless `savedir` is given: then savedir/mesh_eval.json holds the
+    dict and '{:03d}.png' the headlight render of every frame."""
+    from . import meshrender
+    if split not in _SPLIT_ROWS:
+        raise ValueError(f"swnerf.runner.evaluate_mesh: split must be one of {sorted(_SPLIT_ROWS)}, got {split!r}")
+    d = dataset if isinstance(dataset, dict) else _train_data(dataset, False)
+    H, W, focal = d['hwf']
+    H, W, focal = int(H), int(W), float(focal)
+    idx = np.asarray(d['i_split'][_SPLIT_ROWS[split]], dtype=np.int64).reshape(-1)
+    images = torch.as_tensor(d['images'])
+    if tuple(images.shape[1:3]) != (H, W):
+        raise ValueError(f"swnerf.runner.evaluate_mesh: the frames are {tuple(images.shape[1:3])}, hwf says {(H, W)}")
+    poses = torch.as_tensor(np.asarray(torch.as_tensor(d['poses']).cpu(), dtype=np.float32))[torch.from_numpy(idx)]
+    if net_depths is not None and tuple(net_depths.shape) != (len(idx), H, W):
+        raise ValueError(f"swnerf.runner.evaluate_mesh: net_depths must be {(len(idx), H, W)}, got {tuple(net_depths.shape)}")
+    outputs = ("acc", "depth") + (("rgb",) if savedir is not None else ())
+    out = meshrender.render_views(m, H, W, d.get('K'), poses, shading="headlight", white_bkgd=True, outputs=outputs, focal=focal)
+    frames = images.to(out["acc"].device)[torch.from_numpy(idx).to(out["acc"].device)]
+    alpha = frames if frames.shape[-1] == 4 else torch.ones((len(idx), H, W), dtype=torch.float32, device=frames.device)
+    res = meshrender.compare_views(out, alpha=alpha, depth=net_depths)
+    keys = ("iou", "depth_mae", "depth_rmse", "intersection", "union", "mesh_pixels", "ref_pixels")
+    report = {"frame": idx.tolist(), **{k: res[k].tolist() for k in keys}}
+    if savedir is not None:
+        os.makedirs(savedir, exist_ok=True)
+        for i, rgb in enumerate(out["rgb"].cpu().numpy()):
+            write_png(os.path.join(savedir, '{:03d}.png'.format(i)), to8b(rgb))
+        with open(os.path.join(savedir, "mesh_eval.json"), "w") as f:
+            json.dump(report, f, indent=4)
+    return report
+
+
 # ---- train() of the two runners (nerf/run.py:598-796, d_nerf/run_dnerf.py:596-820) ---------------------------------------
 _RENDER_ONLY_KEYS = ('ndc', 'near', 'far', 'use_viewdirs', 'c2w_staticcam')      # what render() consumes before render_rays
 
