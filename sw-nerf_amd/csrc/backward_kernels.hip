@@ -1,7 +1,8 @@
 // backward_kernels.hip - the standalone compositing backward:
 //   raw2outputs backward: d(raw) from d(rgb_map, disp_map, acc_map, depth_map, weights)   (ray.py:155-198)
-// The dX chains and the fused backward live in train_kernels.hip next to the forward they mirror; the weight-gradient GEMMs
-// and everything else swnerf/wgrad.py drives live in wgrad_kernels.hip.
+// The dX chain is written once in mlp_bwd.h; the kernels that run it - per row and fused - live in train_kernels.hip next to
+// the forward they mirror, the per-ray and per-tile set-up of the fused backwards in render_pass.h; the weight-gradient GEMMs and
+// everything else swnerf/wgrad.py drives live in wgrad_kernels.hip.
 #include <hip/hip_runtime.h>
 #include "../../include/swnerf.h"
 #include "swnerf_common.h"

@@ -150,8 +150,61 @@ static inline int pass_resampling(const char* name, const swnerf_pass_args& a, P
     return 0;
 }
 
-// ---- the compositing backward of ONE ray by its wave (autograd of ray.py:155-198; composite.h), shared by the fused backward
-// kernels (train_kernels.hip render_pass_backward_kernel, tnerf_train_kernels.hip tnerf_backward_kernel): forward recompute of T and
+// ---- what the fused backward kernels share (train_kernels.hip render_pass_backward_kernel, tnerf_train_kernels.hip
+// tnerf_backward_kernel): ONE wavefront owns ONE ray, like the forward; rows are the forward's padded rows (TrainRows).
+#define SW_BWD_SMAX 256                          // samples per ray: each wave keeps T[S], w[S], d_raw[S][4] in LDS
+#define SW_BWD_COMP_FLOATS (6 * SW_BWD_SMAX)
+
+// host side: what every entry point of a fused backward checks first (`ptrs`: every pointer this variant requires is there)
+static inline int pass_bwd_check(const char* name, bool ptrs, int64_t n_rays, int n_samples) {
+    if (!ptrs || n_rays < 0) return sw_fail(SWNERF_E_ARG, "%s: NULL pointer or negative n_rays", name);
+    if (n_samples < 2 || n_samples > SW_BWD_SMAX) return sw_fail(SWNERF_E_UNSUPP, "%s: 2 <= n_samples <= %d (got %d)", name, SW_BWD_SMAX, n_samples);
+    return 0;
+}
+
+// A wave's ray as the backward reads it (the forward's RayRow is the model): indices, this ray's saved raw [S, oc] and depths
+// [S], origin and direction.  dnorm is sqrtf(d.d) WITHOUT row_dnorm's finiteness test: the backward never had it.
+struct BwdRay {
+    int lane, j, h, wv;                 // lane of the wave, its row of a tile, its lane half; wave of the workgroup (scalar)
+    int64_t ray; int ntiles;
+    const float* raw; const float* zv;
+    float o[3], d[3], dnorm;
+};
+// The indices, and the bias tiles to LDS: bias_to_lds() holds the workgroup's only barrier, so it stands in front of the early
+// exit of a wave without a ray (r.ray >= n_rays, wave-uniform), which the kernel takes right behind this ...
+__device__ __forceinline__ void bwd_ray_enter(BwdRay& r, float* lds, const float* b0, int nbias) {
+    r.lane = threadIdx.x & 63; r.j = r.lane & 31; r.h = r.lane >> 5;
+    r.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    r.ray = (int64_t)blockIdx.x * 4 + r.wv;
+    bias_to_lds(lds, b0, nbias);
+}
+// ... and the row of a ray that exists
+__device__ __forceinline__ void bwd_ray_load(BwdRay& r, const float* ray_batch, int cols, const float* raw, int oc, const float* z, int S) {
+    r.ntiles = (S + 31) >> 5;
+    const float* rb = ray_batch + r.ray * cols;
+    r.o[0] = rb[0]; r.o[1] = rb[1]; r.o[2] = rb[2]; r.d[0] = rb[3]; r.d[1] = rb[4]; r.d[2] = rb[5];
+    r.dnorm = sqrtf(r.d[0] * r.d[0] + r.d[1] * r.d[1] + r.d[2] * r.d[2]);
+    r.zv = z + r.ray * S;
+    r.raw = raw + r.ray * S * oc;
+}
+
+// The head of a tile: this lane's sample (sc: the last one for lanes past S), its tile and padded row, and d raw of the sample
+// = what comp_bwd_ray left in LDS + the upstream gradient of the returned raw (g_raw4 [N,S,4] or NULL), zero past S.
+struct BwdTile { int s, sc; bool live; int64_t tix, prow; f32x4 dr; };
+__device__ __forceinline__ BwdTile bwd_tile(const BwdRay& r, int tile, int S, const float* dR, const float* g_raw4) {
+    BwdTile t;
+    t.s = tile * 32 + r.j;
+    t.live = t.s < S;
+    t.sc = t.live ? t.s : S - 1;
+    t.tix = r.ray * r.ntiles + tile;
+    t.prow = t.tix * 32 + r.j;
+    t.dr = *reinterpret_cast<const f32x4*>(dR + 4 * t.sc);
+    if (g_raw4) t.dr += *reinterpret_cast<const f32x4*>(g_raw4 + (r.ray * S + t.sc) * 4);
+    if (!t.live) t.dr = f32x4{0.f, 0.f, 0.f, 0.f};
+    return t;
+}
+
+// ---- the compositing backward of ONE ray by its wave (autograd of ray.py:155-198; composite.h): forward recompute of T and
 // w from the saved raw [S, oc] and depths zv [S] (-> T_[S], W_[S] in the wave's LDS slice), suffix sums of G.w in double, d raw of
 // every sample -> dR[S][4] in LDS.  noise: this ray's [S] or NULL; g_rgb [3] / g_disp [1] / g_acc [1]: this ray's upstream
 // gradients, each may be NULL.  VEC4: raw rows are 16-byte aligned (oc == 4).  Ends with the LDS visible to the whole wave.

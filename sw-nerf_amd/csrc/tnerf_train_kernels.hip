@@ -5,12 +5,14 @@
 // encodings in operand slot order (swnerf_common.h SW_TN_*).
 //
 // Backward (tnerf_backward_kernel): per ray
-//   1. the compositing backward (render_pass.h comp_bwd_ray, shared with train_kernels.hip render_pass_backward_kernel): T and w
-//      recomputed from the saved raw and depths, suffix sums of G.w in double, d raw of every sample -> the wave's LDS slice;
+//   1. the compositing backward (render_pass.h: bwd_ray_enter / bwd_ray_load, comp_bwd_ray and, per tile, bwd_tile are shared with
+//      train_kernels.hip render_pass_backward_kernel): T and w recomputed from the saved raw and depths, suffix sums of G.w in
+//      double, d raw of every sample -> the wave's LDS slice;
 //   2. per 32-sample tile the dX chain: d raw -> colour head (ReLU mask from raw; 3 x 64 on the VALU from bias-style tiles) -> ELU'
 //      -> the folded layer_9 transposed (W9f^T, 4 x 2) + density.weight . d sigma (SEG_BIAS_SCALED) -> layers.7 .. layers.1
 //      transposed (4 x 4; layer 5: its h4 columns - gamma(x), gamma(t) are data) with ELU' from the saved activations.
-//      d(pre-activation) of every layer goes to grad [rows, SW_TN_ACT_LD] (the layout of act) as side stores.
+//      d(pre-activation) of every layer goes to grad [rows, SW_TN_ACT_LD] (the layout of act) as side stores.  (The chain of the
+//      8 x 256 ReLU nets is mlp_bwd.h; this 8 x 128 ELU one shares none of it: no bit masks, activations fetched instead.)
 // ELU' needs y itself (1 for y > 0, y + 1 otherwise: the rule of swnerf_elu_grad), not a bit: layer l-1's activations of the tile
 // (16 KiB = 16 LDS-DMA steps) come into a slot of the wave while layer l's segment runs, ONE step every third weight step (every
 // step in the 32-step W9f^T segment), each right behind that step's weight DMA (mlp_core.h SideFetch) - a burst of 16 in front of the
@@ -24,8 +26,6 @@
 // ---- forward, TRAIN ----------------------------------------------------------------------------------------------------------
 extern "C" size_t swnerf_tnerf_act_floats_per_row(void) { return (size_t)SW_TN_ACT_LD; }
 extern "C" size_t swnerf_tnerf_xs_floats_per_row(void) { return (size_t)SW_TN_XS_LD; }
-
-#define TB_SMAX 256
 
 static int sw_tnerf_train_launch(const swnerf_pass_args& a, float* act, float* xs, hipStream_t st) {
     PassDev P = pass_dev(a);
@@ -41,7 +41,7 @@ static int sw_tnerf_train_launch(const swnerf_pass_args& a, float* act, float* x
 
 extern "C" int swnerf_render_pass_train_tnerf(const swnerf_pass_args* args, float* act, float* xs, void* stream) {
     static const PassAccepts accepts = {"render_pass_train_tnerf", {0, 0, 0, SW_COLS(12)}, SWNERF_E_UNSUPP,
-        "%s: T-NeRF (SWNERF_NET_TNERF) with the 12-column ray batch [o, d, near, far, t, viewdirs]", true, TB_SMAX};
+        "%s: T-NeRF (SWNERF_NET_TNERF) with the 12-column ray batch [o, d, near, far, t, viewdirs]", true, SW_BWD_SMAX};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass_train_tnerf: NULL args");
     const swnerf_pass_args& a = *args;
     if (a.n_rays == 0 && a.packed) return 0;
@@ -96,7 +96,7 @@ __device__ __forceinline__ void act_take_elu_grad(const ActRing& ar, f32x16 (&d)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
-#define TB_WAVE_FLOATS (SW_RING * SW_STEP_FLOATS + TB_ACT_SLOT_FLOATS + 6 * TB_SMAX)    // weight ring | act slot | T[S], w[S], d_raw[S][4]
+#define TB_WAVE_FLOATS (SW_RING * SW_STEP_FLOATS + TB_ACT_SLOT_FLOATS + SW_BWD_COMP_FLOATS)    // weight ring | act slot | T[S], w[S], d_raw[S][4]
 #define TB_LDS_FLOATS (SW_TN_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS + 4 * TB_WAVE_FLOATS)
 
 struct TnBwdDev {
@@ -111,53 +111,43 @@ struct TnBwdDev {
 __global__ void __launch_bounds__(256, 1) tnerf_backward_kernel(TnBwdDev P) {
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
     constexpr int BIASF = SW_TN_BWD_BIAS_TILES * SW_BIAS_TILE_FLOATS;
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t ray = (int64_t)blockIdx.x * 4 + wv;
-    bias_to_lds(lds_all, P.b0, BIASF);
-    if (ray >= P.n_rays) return;                      // wave-uniform
-    float* lds_ring = lds_all + BIASF + wv * TB_WAVE_FLOATS;
-    float* lds_act = lds_ring + SW_RING * SW_STEP_FLOATS;
-    float* T_ = lds_act + TB_ACT_SLOT_FLOATS;
-    float* W_ = T_ + TB_SMAX;
-    float* dR = W_ + TB_SMAX;
     const int S = P.S;
-    const int ntiles = (S + 31) >> 5;
-    const float* rb = P.ray_batch + ray * 12;
-    const float ddx = rb[3], ddy = rb[4], ddz = rb[5];
-    const float dnorm = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-    const float* zv = P.z + ray * S;
-    const float* raw = P.raw + ray * S * 4;
+    BwdRay r;
+    bwd_ray_enter(r, lds_all, P.b0, BIASF);
+    if (r.ray >= P.n_rays) return;                    // wave-uniform
+    bwd_ray_load(r, P.ray_batch, 12, P.raw, 4, P.z, S);
+    const int lane = r.lane, h = r.h;
+    float* lds_ring = lds_all + BIASF + r.wv * TB_WAVE_FLOATS;
+    float* lds_act = lds_ring + SW_RING * SW_STEP_FLOATS;
     WStream ws;
     ws_start(ws, P.w0, lds_all, lds_ring, lane);      // the weight ring fills while the compositing backward runs
 
     // ---- 1. compositing backward (render_pass.h comp_bwd_ray; no d(depth_map) and no d(weights) reach the fused step)
-    comp_bwd_ray<true>(raw, 4, zv, P.noise ? P.noise + ray * S : nullptr, S, lane, dnorm, P.white, P.g_rgb ? P.g_rgb + ray * 3 : nullptr,
+    float* T_ = lds_act + TB_ACT_SLOT_FLOATS;
+    float* W_ = T_ + SW_BWD_SMAX;
+    float* dR = W_ + SW_BWD_SMAX;
+    const int64_t ray = r.ray;
+    comp_bwd_ray<true>(r.raw, 4, r.zv, P.noise ? P.noise + ray * S : nullptr, S, lane, r.dnorm, P.white, P.g_rgb ? P.g_rgb + ray * 3 : nullptr,
                        P.g_disp ? P.g_disp + ray : nullptr, P.g_acc ? P.g_acc + ray : nullptr, T_, W_, dR);
 
     // ---- 2. the dX chain, tile by tile
     const f32x4 nomask = {0.f, 0.f, 0.f, 0.f};
 #pragma nounroll
-    for (int tile = 0; tile < ntiles; ++tile) {
-        const int s = tile * 32 + j;
-        const bool live = s < S;
-        const int sc = live ? s : S - 1;
-        const int64_t tix = ray * ntiles + tile;
-        const int64_t prow = tix * 32 + j;
-        ActRing ar;
-        act_start(ar, P.act + tix * 32 * SW_TN_ACT_LD, lds_act, lane);
+    for (int tile = 0; tile < r.ntiles; ++tile) {
+        ActRing ar;                                                          // (the tile index is bwd_tile's tix, written here too: bwd_tile has to stay behind the fetch)
+        act_start(ar, P.act + (r.ray * r.ntiles + tile) * 32 * SW_TN_ACT_LD, lds_act, lane);
         act_fetch<2>(ar, SW_TN_ACT_HV);                                      // the layer_9 hidden; waited for below (once per tile)
-        f32x4 dr = *reinterpret_cast<const f32x4*>(dR + 4 * sc);
-        if (P.g_raw) dr += *reinterpret_cast<const f32x4*>(P.g_raw + (ray * S + sc) * 4);
+        const BwdTile t = bwd_tile(r, tile, S, dR, P.g_raw);                 // (behind the fetch: its loads wait, the DMAs do not)
+        f32x4 dr = t.dr;
         {   // the colour head's ReLU (model.py:188-189): raw holds its OUTPUT, so the mask is raw > 0
-            const f32x4 r4 = *reinterpret_cast<const f32x4*>(raw + sc * 4);
+            const f32x4 r4 = *reinterpret_cast<const f32x4*>(r.raw + t.sc * 4);
             dr[0] = r4[0] > 0.f ? dr[0] : 0.f; dr[1] = r4[1] > 0.f ? dr[1] : 0.f; dr[2] = r4[2] > 0.f ? dr[2] : 0.f;
         }
-        if (!live) dr = nomask;
-        if (h == 0) *reinterpret_cast<f32x4*>(P.d_raw + prow * 4) = dr;
-        float* grad_row = P.grad + prow * SW_TN_ACT_LD + 4 * h;
+        if (h == 0) *reinterpret_cast<f32x4*>(P.d_raw + t.prow * 4) = dr;
+        float* grad_row = P.grad + t.prow * SW_TN_ACT_LD + 4 * h;
         // d hv = color.weight^T . d pre_color: 3 weight rows as bias-style tiles behind density.weight's four (tile n of channel c: [h][r])
         f32x16 dhv[2], in[4], out[4];
+        // (written out ON PURPOSE: as mlp_bwd.h wrows_valu with a tile count of 2 this kernel came out at 204 / 140 registers for 208 / 144 and 291 s_waitcnt for 290)
         const float* wt = lds_all + 4 * SW_BIAS_TILE_FLOATS + h * 16;
 #pragma unroll
         for (int n = 0; n < 2; ++n)
@@ -194,9 +184,7 @@ extern "C" int swnerf_render_pass_backward_tnerf(const float* packed_bwd, const 
                                                  int white_bkgd, const float* g_rgb, const float* g_disp, const float* g_acc,
                                                  const float* g_raw, float* grad, float* d_raw, void* stream) {
     if (n_rays == 0 && packed_bwd) return 0;
-    if (!packed_bwd || !act || !raw || !z_vals || !ray_batch || !grad || !d_raw || n_rays < 0)
-        return sw_fail(SWNERF_E_ARG, "render_pass_backward_tnerf: NULL pointer or negative n_rays");
-    if (n_samples < 2 || n_samples > TB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "render_pass_backward_tnerf: 2 <= n_samples <= %d (got %d)", TB_SMAX, n_samples);
+    if (int rc = pass_bwd_check("render_pass_backward_tnerf", packed_bwd && act && raw && z_vals && ray_batch && grad && d_raw, n_rays, n_samples)) return rc;
     if (cols != 12) return sw_fail(SWNERF_E_ARG, "render_pass_backward_tnerf: T-NeRF needs the 12-column ray batch [o, d, near, far, t, viewdirs], got %d", cols);
     if (((uintptr_t)act | (uintptr_t)raw | (uintptr_t)g_raw | (uintptr_t)grad | (uintptr_t)d_raw | (uintptr_t)packed_bwd) % 16)
         return sw_fail(SWNERF_E_ARG, "render_pass_backward_tnerf: packed_bwd, act, raw, g_raw, grad and d_raw must be 16-byte aligned");

@@ -1,5 +1,6 @@
 // train_kernels.hip - the training path of the MLP: the forward that saves activations
-// and ReLU bit masks, the dX chains of the canonical and the deformation net.  Same building blocks as the render
+// and ReLU bit masks, the kernels that run the dX chain (mlp_bwd.h) on the canonical and the deformation net, per row
+// and fused with the compositing backward (its per-ray set-up: render_pass.h).  Same building blocks as the render
 // kernels (mlp_core.h) but with a 16-deep weight ring: these kernels also issue stores, `vmcnt` retires in order, and
 // a store's write acknowledge takes longer than 6 ring steps often enough to cost 8 % (measured: forward 7.57 ->
 // 6.94 ms, dX chain 6.64 -> 6.32 ms at 786 k rows).  The render kernels keep 8: their LDS also holds 28 KB of
@@ -9,55 +10,11 @@
 #endif
 #include "mlp_kernels.h"
 #include "render_pass.h"
+#include "mlp_bwd.h"
 
 // ------------------------------------------------------------------------------------------
-// Backward of the MLP w.r.t. its activations (the "dX chain"), one wave per 32 rows, mirroring the
-// forward: transposed weight streams, the same register-resident accumulator->operand hand-over.  The ReLU
-// derivative comes from the forward's bit masks, fetched one layer ahead by LDS-DMA into a 1-KiB slot of the
-// wave (nothing the compiler sees is ever pending, like the weight ring); d(pre-activation) of every layer goes
-// to grad[M, SW_ACT_LD] (same column map as act) for the weight-gradient GEMMs as side stores of the segment
-// that consumes it (mlp_core.h SideStore).   model.py:39-62 reversed.
-struct MaskRing {
-    const char* base;        // wave-uniform: this tile's SW_MASK_TILE_FLOATS of bit masks
-    unsigned voff, lds_addr; // lane * 16; LDS byte address of the slot
-    const float* slot;       // the slot + lane * 4 floats
-};
-__device__ __forceinline__ void mask_start(MaskRing& mr, const float* bits, int64_t tile, float* lds_slot, int lane) {
-    mr.base = reinterpret_cast<const char*>(bits + tile * SW_MASK_TILE_FLOATS);
-    mr.voff = (unsigned)lane * 16u;
-    mr.lds_addr = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lds_slot);
-    mr.slot = lds_slot + lane * 4;
-}
-// fetch layer l's mask; the previous contents must have been read (mask_take ends with lgkmcnt(0))
-__device__ __forceinline__ void mask_fetch(const MaskRing& mr, int l) { ws_dma(mr.base + l * 1024, mr.voff, mr.lds_addr); }
-// the mask fetched last; legal once a counted wait behind >= SW_RING later DMAs has passed (any full segment)
-__device__ __forceinline__ f32x4 mask_take(const MaskRing& mr) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(mr.slot);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    return v;
-}
-
-// out = sum_c w_c . d_c (ACC: added to out): NC weight rows of 256 riding as bias-style tiles, tile n of channel c at
-// wt + (c * 8 + n) tiles, as [h][r]; wt already points at the lane half's 16 floats.  Summed left to right.
-template <int NC, bool ACC = false>
-__device__ __forceinline__ void wrows_valu(const float* wt, const float (&d)[NC], f32x16 (&out)[8]) {
-#pragma unroll
-    for (int n = 0; n < 8; ++n)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 w[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) w[c] = *reinterpret_cast<const f32x4*>(wt + (c * 8 + n) * SW_BIAS_TILE_FLOATS + 4 * g);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float s = ACC ? out[n][4 * g + e] + w[0][e] * d[0] : w[0][e] * d[0];
-#pragma unroll
-                for (int c = 1; c < NC; ++c) s += w[c][e] * d[c];
-                out[n][4 * g + e] = s;
-            }
-        }
-}
-
+// Backward of the MLP w.r.t. its activations (the "dX chain"), one wave per 32 rows: the chain itself - mask ring, view
+// head, trunk - is written once in mlp_bwd.h; the kernels here seed it and finish it.
 struct DxDev {
     const float* w0; const float* b0;      // backward stream; its 8 "bias" tiles = alpha_linear.weight
     const float* bits; const float* d_out; // [ceil(M/32), SW_MASK_TILE_FLOATS], [M,4]
@@ -82,36 +39,9 @@ __global__ void __launch_bounds__(256, 1) mlp_backward_dx_kernel(DxDev P) {
     mask_fetch(mr, 8);                                                   // views hidden; older than every weight step
     WStream ws;
     ws_start(ws, P.w0, lds_bias, rt.lds_ring, lane);
-    // d hv = rgb_linear.weight^T . d rgb, masked by hv > 0           (4 tiles <- 1 k-tile holding 3 channels)
-    f32x16 k1[1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) k1[0][r] = 0.f;
-    k1[0][0] = h ? 0.f : dr[0]; k1[0][1] = h ? 0.f : dr[1]; k1[0][2] = h ? 0.f : dr[2];
-    f32x16 dhv[4];
-    seg_mfma<4, 1, SEG_ZERO>(dhv, k1, ws);
-    mask_apply<4>(mask_take(mr), dhv);
-    mask_fetch(mr, 7);
-    // d h7 = W_vf^T . d pre_hv + alpha_linear.weight * d sigma  (W_vf = views_linears.0.weight[:, :256] . feature_linear.weight:
-    // no activation on feature_linear, so the two transposed layers are one, swnerf_common.h SW_BWD_STEPS), masked by h7 > 0 below
     f32x16 in[8], out[8];
-    seg_mfma<8, 4, SEG_BIAS_SCALED, 4>(out, dhv, ws, dr[3], SideStore{grad_row + SW_ACT_HV, nullptr, nomask});
-#pragma nounroll
-    for (int l = 7; l >= 1; --l) {
-        // out = d h_l;  d pre_l = out . [h_l > 0];  d h_{l-1} = W_l[:, -256:]^T . d pre_l
-#pragma unroll
-        for (int n = 0; n < 8; ++n) in[n] = out[n];
-        mask_apply<8>(mask_take(mr), in);
-        mask_fetch(mr, l - 1);
-        if (INGRAD && l == 5) {                                          // the skip input cat[gamma(x), h4]: its gamma(x) part
-            f32x16 ge[2];
-            seg_mfma<2, 8, SEG_ZERO>(ge, in, ws);
-            emb_park(rt.lds_emb, lane, ge);
-        }
-        seg_mfma<8, 8, SEG_ZERO, 8>(out, in, ws, 1.f, SideStore{grad_row + 256 * l, nullptr, nomask});
-    }
-#pragma unroll
-    for (int n = 0; n < 8; ++n) in[n] = out[n];
-    mask_apply<8>(mask_take(mr), in);                                    // d pre_0
+    dx_view_head(dr, h, mr, ws, grad_row, out);                          // d h7
+    dx_trunk<INGRAD>(in, out, mr, ws, grad_row, rt.lds_emb, lane);       // d pre_7 .. d pre_1 stored, in = d pre_0
     if (!INGRAD) {
         tiles_store<8>(grad_row, in);
     } else {
@@ -176,7 +106,6 @@ __global__ void __launch_bounds__(256, 1) deform_backward_dx_kernel(DeformBwdDev
     const int64_t rr = rt.rr;
     const float d3[3] = {P.d_dx[rr * 3], P.d_dx[rr * 3 + 1], P.d_dx[rr * 3 + 2]};
     float* grad_row = P.grad + rr * SW_ACT_LD + 4 * h;
-    const f32x4 nomask = {0.f, 0.f, 0.f, 0.f};
     MaskRing mr;
     mask_start(mr, P.bits, rt.tile, rt.lds_emb + 2 * 16 * 64, lane);
     mask_fetch(mr, 7);
@@ -184,18 +113,8 @@ __global__ void __launch_bounds__(256, 1) deform_backward_dx_kernel(DeformBwdDev
     ws_start(ws, P.w0, lds_bias, rt.lds_ring, lane);
     f32x16 in[8], out[8];
     wrows_valu<3>(ws.bias, d3, out);                                     // d h7 = _time_out.weight^T . d dx
-#pragma nounroll
-    for (int l = 7; l >= 1; --l) {
-#pragma unroll
-        for (int n = 0; n < 8; ++n) in[n] = out[n];
-        mask_apply<8>(mask_take(mr), in);
-        mask_fetch(mr, l - 1);
-        seg_mfma<8, 8, SEG_ZERO, 8>(out, in, ws, 1.f, SideStore{grad_row + 256 * l, nullptr, nomask});
-    }
-#pragma unroll
-    for (int n = 0; n < 8; ++n) in[n] = out[n];
-    mask_apply<8>(mask_take(mr), in);                                    // d pre_0 (x and t are data: no further gradient)
-    tiles_store<8>(grad_row, in);
+    dx_trunk<false>(in, out, mr, ws, grad_row, nullptr, lane);
+    tiles_store<8>(grad_row, in);                                        // d pre_0 (x and t are data: no further gradient)
 }
 
 // ------------------------------------------------------------------------------------------
@@ -206,8 +125,6 @@ __global__ void __launch_bounds__(256, 1) deform_backward_dx_kernel(DeformBwdDev
 //   2. per 32-sample tile the dX chain of mlp_backward_dx_kernel, seeded from LDS: d(pre-activation) of every layer
 //      -> grad[rows, SW_ACT_LD] as side stores.
 // Rows are the forward's padded rows: (ray * ntiles + tile) * 32 + j; samples past S get zero gradients.
-#define PB_SMAX 256
-#define PB_WAVE_FLOATS (6 * PB_SMAX)                 // T[S], w[S], d_raw[S][4]
 struct PassBwdDev {
     const float* w0; const float* b0;                // backward stream; bias tiles: alpha_linear.weight (8) [, _time_out.weight rows (24)]
     const float* bits;                               // [n_rays * ntiles, SW_MASK_TILE_FLOATS]
@@ -231,64 +148,50 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
     constexpr bool DNERF = MODE == 1, NOVIEW = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) float lds_all[];
     constexpr int BIASF = (NOVIEW ? SW_NVBWD_BIAS_TILES : (DNERF ? SW_BWD_BIAS_TILES + SW_DBWD_BIAS_TILES : SW_BWD_BIAS_TILES)) * SW_BIAS_TILE_FLOATS;
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t ray = (int64_t)blockIdx.x * 4 + wv;
     const int oc = NOVIEW ? P.out_ch : 4;
-    bias_to_lds(lds_all, P.b0, NOVIEW ? oc * 8 * SW_BIAS_TILE_FLOATS : BIASF);
-    if (ray >= P.n_rays) return;
-    float* lds_ring = lds_all + BIASF + wv * SW_LDS_RING_FLOATS;
-    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
-    float* T_ = lds_all + BIASF + 4 * SW_LDS_RING_FLOATS + wv * PB_WAVE_FLOATS;
-    float* W_ = T_ + PB_SMAX;
-    float* dR = W_ + PB_SMAX;
     const int S = P.S;
-    const int ntiles = (S + 31) >> 5;
-    const float* rb = P.ray_batch + ray * P.cols;
-    const float rox = rb[0], roy = rb[1], roz = rb[2], ddx = rb[3], ddy = rb[4], ddz = rb[5];
-    const float dnorm = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-    const float* zv = P.z + ray * S;
-    const float* raw = P.raw + ray * S * oc;
+    BwdRay r;
+    bwd_ray_enter(r, lds_all, P.b0, NOVIEW ? oc * 8 * SW_BIAS_TILE_FLOATS : BIASF);
+    if (r.ray >= P.n_rays) return;
+    bwd_ray_load(r, P.ray_batch, P.cols, P.raw, oc, P.z, S);
+    const int lane = r.lane, h = r.h;
+    const int64_t ray = r.ray;
+    float* lds_ring = lds_all + BIASF + r.wv * SW_LDS_RING_FLOATS;
+    float* lds_emb = lds_ring + SW_RING * SW_STEP_FLOATS;
     WStream ws;
     ws_start(ws, P.w0, lds_all, lds_ring, lane);      // the weight ring fills while the compositing backward runs
 
     // ---- 1. compositing backward (render_pass.h comp_bwd_ray; no d(depth_map) and no d(weights) reach the fused step)
-    comp_bwd_ray<!NOVIEW>(raw, oc, zv, P.noise ? P.noise + ray * S : nullptr, S, lane, dnorm, P.white, P.g_rgb ? P.g_rgb + ray * 3 : nullptr,
+    float* T_ = lds_all + BIASF + 4 * SW_LDS_RING_FLOATS + r.wv * SW_BWD_COMP_FLOATS;
+    float* W_ = T_ + SW_BWD_SMAX;
+    float* dR = W_ + SW_BWD_SMAX;
+    comp_bwd_ray<!NOVIEW>(r.raw, oc, r.zv, P.noise ? P.noise + ray * S : nullptr, S, lane, r.dnorm, P.white, P.g_rgb ? P.g_rgb + ray * 3 : nullptr,
                           P.g_disp ? P.g_disp + ray : nullptr, P.g_acc ? P.g_acc + ray : nullptr, T_, W_, dR);
 
-    // ---- 2. the dX chain(s), tile by tile: mlp_backward_dx_kernel<DNERF> [+ deform_backward_dx_kernel]
+    // ---- 2. the dX chain(s) of mlp_bwd.h, tile by tile: mlp_backward_dx_kernel<DNERF> [+ deform_backward_dx_kernel]
     const f32x4 nomask = {0.f, 0.f, 0.f, 0.f};
 #pragma nounroll
-    for (int tile = 0; tile < ntiles; ++tile) {
-        const int s = tile * 32 + j;
-        const bool live = s < S;
-        const int sc = live ? s : S - 1;
-        const int64_t tix = ray * ntiles + tile;
-        const int64_t prow = tix * 32 + j;
-        f32x4 dr = *reinterpret_cast<const f32x4*>(dR + 4 * sc);
+    for (int tile = 0; tile < r.ntiles; ++tile) {
+        const BwdTile bt = bwd_tile(r, tile, S, dR, NOVIEW ? nullptr : P.g_raw);
+        f32x4 dr = bt.dr;
         float dr5 = 0.f;                                                     // NOVIEW, out_ch 5: the fifth channel gets a gradient from g_raw alone
-        if (P.g_raw) {
-            if (NOVIEW) {
-                const float* gq = P.g_raw + (ray * S + sc) * oc;
-                dr[0] += gq[0]; dr[1] += gq[1]; dr[2] += gq[2]; dr[3] += gq[3];
-                if (oc == 5) dr5 = gq[4];
-            } else {
-                dr += *reinterpret_cast<const f32x4*>(P.g_raw + (ray * S + sc) * 4);
-            }
+        if (NOVIEW && P.g_raw && bt.live) {                                  // rows of out_ch floats: no 16-byte loads
+            const float* gq = P.g_raw + (ray * S + bt.sc) * oc;
+            dr[0] += gq[0]; dr[1] += gq[1]; dr[2] += gq[2]; dr[3] += gq[3];
+            if (oc == 5) dr5 = gq[4];
         }
-        if (!live) { dr = nomask; dr5 = 0.f; }
         if (h == 0) {
             if (NOVIEW) {                                                    // [rows, 8]: the A operand of output_linear's weight-gradient GEMM
                 const f32x4 hi4 = {dr5, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4*>(P.d_raw + prow * 8) = dr;
-                *reinterpret_cast<f32x4*>(P.d_raw + prow * 8 + 4) = hi4;
+                *reinterpret_cast<f32x4*>(P.d_raw + bt.prow * 8) = dr;
+                *reinterpret_cast<f32x4*>(P.d_raw + bt.prow * 8 + 4) = hi4;
             } else {
-                *reinterpret_cast<f32x4*>(P.d_raw + prow * 4) = dr;
+                *reinterpret_cast<f32x4*>(P.d_raw + bt.prow * 4) = dr;
             }
         }
-        float* grad_row = P.grad + prow * SW_ACT_LD + 4 * h;
+        float* grad_row = P.grad + bt.prow * SW_ACT_LD + 4 * h;
         MaskRing mr;
-        mask_start(mr, P.bits, tix, lds_emb + 2 * 16 * 64, lane);
+        mask_start(mr, P.bits, bt.tix, lds_emb + 2 * 16 * 64, lane);
         f32x16 in[8], out[8];
         if constexpr (NOVIEW) {
             mask_fetch(mr, 7);
@@ -299,47 +202,23 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
             if (oc == 5) wrows_valu<1, true>(wt + 4 * 8 * SW_BIAS_TILE_FLOATS, d5, out);      // wave-uniform
             ws_wait<0>();            // h7's mask has landed (no segment lies between its fetch and its use here: once per tile, ~1 us)
         } else {
-        mask_fetch(mr, 8);
-        f32x16 k1[1];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) k1[0][r] = 0.f;
-        k1[0][0] = h ? 0.f : dr[0]; k1[0][1] = h ? 0.f : dr[1]; k1[0][2] = h ? 0.f : dr[2];
-        f32x16 dhv[4];
-        seg_mfma<4, 1, SEG_ZERO>(dhv, k1, ws);
-        mask_apply<4>(mask_take(mr), dhv);
-        mask_fetch(mr, 7);
-        // d h7 = W_vf^T . d pre_hv + alpha_linear.weight * d sigma: feature_linear folded into the view layer (SW_BWD_STEPS)
-        seg_mfma<8, 4, SEG_BIAS_SCALED, 4>(out, dhv, ws, dr[3], SideStore{grad_row + SW_ACT_HV, nullptr, nomask});
+            mask_fetch(mr, 8);
+            dx_view_head(dr, h, mr, ws, grad_row, out);
         }
-#pragma nounroll
-        for (int l = 7; l >= 1; --l) {
-#pragma unroll
-            for (int n = 0; n < 8; ++n) in[n] = out[n];
-            mask_apply<8>(mask_take(mr), in);
-            mask_fetch(mr, l - 1);
-            if (DNERF && l == 5) {                                           // the skip input cat[gamma(x+dx), h4]: its gamma part
-                f32x16 ge[2];
-                seg_mfma<2, 8, SEG_ZERO>(ge, in, ws);
-                emb_park(lds_emb, lane, ge);
-            }
-            seg_mfma<8, 8, SEG_ZERO, 8>(out, in, ws, 1.f, SideStore{grad_row + 256 * l, nullptr, nomask});
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) in[n] = out[n];
-        mask_apply<8>(mask_take(mr), in);                                    // d pre_0
+        dx_trunk<DNERF>(in, out, mr, ws, grad_row, lds_emb, lane);           // in = d pre_0 (D-NeRF: the gamma(x+dx) part of the skip input parked)
         if (!DNERF) {
             tiles_store<8>(grad_row, in);
         } else {
             // d gamma(x+dx) -> d(x+dx) through the sin/cos Jacobian (mlp_backward_dx_kernel<true>), + the upstream gradient of
             // position_delta (the TV loss's operand, run_dnerf.py:700-716) = d dx: the seed of the deformation net's chain
-            mask_start(mr, P.bits_d, tix, lds_emb + 2 * 16 * 64, lane);
+            mask_start(mr, P.bits_d, bt.tix, lds_emb + 2 * 16 * 64, lane);
             mask_fetch(mr, 7);                                               // h7 of the deformation net; taken after the next segment
             f32x16 ge[2];
             emb_fetch(lds_emb, lane, ge);
             seg_mfma<2, 8, SEG_ACC, 8>(ge, in, ws, 1.f, SideStore{grad_row, nullptr, nomask});
-            const float z = zv[sc];
-            const float* dxs = P.dx + (ray * S + sc) * 3;
-            const float x0 = rox + ddx * z + dxs[0], x1 = roy + ddy * z + dxs[1], x2 = roz + ddz * z + dxs[2];   // x + dx, as the forward formed it
+            const float z = r.zv[bt.sc];
+            const float* dxs = P.dx + (ray * S + bt.sc) * 3;
+            const float x0 = r.o[0] + r.d[0] * z + dxs[0], x1 = r.o[1] + r.d[1] * z + dxs[1], x2 = r.o[2] + r.d[2] * z + dxs[2];   // x + dx, as the forward formed it
             float g0 = 0.f, g1 = 0.f, g2 = 0.f;                               // the Jacobian of mlp_backward_dx_kernel<true>, in line (see there)
 #pragma unroll
             for (int a = 0; a < 30; ++a) {
@@ -353,25 +232,15 @@ __global__ void __launch_bounds__(256, 1) render_pass_backward_kernel(PassBwdDev
             }
             if (h == 0) { g0 += ge[1][14]; g1 += ge[1][15]; } else { g2 += ge[1][14]; }
             g0 += __shfl_xor(g0, 32, 64); g1 += __shfl_xor(g1, 32, 64); g2 += __shfl_xor(g2, 32, 64);
-            if (P.g_pd) { const float* gp = P.g_pd + (ray * S + sc) * 3; g0 += gp[0]; g1 += gp[1]; g2 += gp[2]; }
-            if (!live) { g0 = 0.f; g1 = 0.f; g2 = 0.f; }
-            if (h == 0) { f32x4 g4 = {g0, g1, g2, 0.f}; *reinterpret_cast<f32x4*>(P.g_dx + prow * 4) = g4; }
+            if (P.g_pd) { const float* gp = P.g_pd + (ray * S + bt.sc) * 3; g0 += gp[0]; g1 += gp[1]; g2 += gp[2]; }
+            if (!bt.live) { g0 = 0.f; g1 = 0.f; g2 = 0.f; }
+            if (h == 0) { f32x4 g4 = {g0, g1, g2, 0.f}; *reinterpret_cast<f32x4*>(P.g_dx + bt.prow * 4) = g4; }
             // d h7 = _time_out.weight^T . d dx  (24 bias-style tiles right behind alpha_linear's 8), then _time.7 .. _time.1
-            float* gd_row = P.grad_d + prow * SW_ACT_LD + 4 * h;
+            float* gd_row = P.grad_d + bt.prow * SW_ACT_LD + 4 * h;
             const float g3[3] = {g0, g1, g2};
             wrows_valu<3>(ws.bias, g3, out);
-#pragma nounroll
-            for (int l = 7; l >= 1; --l) {
-#pragma unroll
-                for (int n = 0; n < 8; ++n) in[n] = out[n];
-                mask_apply<8>(mask_take(mr), in);
-                mask_fetch(mr, l - 1);
-                seg_mfma<8, 8, SEG_ZERO, 8>(out, in, ws, 1.f, SideStore{gd_row + 256 * l, nullptr, nomask});
-            }
-#pragma unroll
-            for (int n = 0; n < 8; ++n) in[n] = out[n];
-            mask_apply<8>(mask_take(mr), in);                                // d pre_0 of the deformation net (x, t are data)
-            tiles_store<8>(gd_row, in);
+            dx_trunk<false>(in, out, mr, ws, gd_row, nullptr, lane);
+            tiles_store<8>(gd_row, in);                                      // d pre_0 of the deformation net (x, t are data)
         }
         ws_rewind(ws, P.w0, lds_all, lane);
     }
@@ -447,7 +316,7 @@ extern "C" int swnerf_xs_floats_per_row(void) { return SW_XS_LD; }
 
 extern "C" int swnerf_render_pass_train(const swnerf_pass_args* args, float* act, float* bits, float* xs, void* stream) {
     static const PassAccepts accepts = {"render_pass_train", {SW_COLS(11) | SW_COLS(12), 0, SW_COLS(8), 0}, SWNERF_E_UNSUPP,
-        "%s: the static net (SWNERF_NET_CANON, 11- or 12-column ray batch) or the one without view directions (SWNERF_NET_NOVIEW, 8 columns)", false, PB_SMAX};
+        "%s: the static net (SWNERF_NET_CANON, 11- or 12-column ray batch) or the one without view directions (SWNERF_NET_NOVIEW, 8 columns)", false, SW_BWD_SMAX};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass_train: NULL args");
     const swnerf_pass_args& a = *args;
     if (a.n_rays == 0 && a.packed) return 0;
@@ -472,14 +341,8 @@ extern "C" int swnerf_render_pass_train(const swnerf_pass_args* args, float* act
     return sw_check(hipGetLastError(), "render_pass_train launch");
 }
 
-// What the three backward entry points share: the checks (`ptrs`: every pointer this variant requires is there), the
-// PassBwdDev they start from (w_floats: where the bias tiles follow the stream; D-NeRF members null, out_ch 4) and the launch.
-static int pass_bwd_check(const char* name, bool ptrs, int64_t n_rays, int n_samples) {
-    if (!ptrs || n_rays < 0) return sw_fail(SWNERF_E_ARG, "%s: NULL pointer or negative n_rays", name);
-    if (n_samples < 2 || n_samples > PB_SMAX) return sw_fail(SWNERF_E_UNSUPP, "%s: 2 <= n_samples <= %d (got %d)", name, PB_SMAX, n_samples);
-    return 0;
-}
-
+// What the three backward entry points share: the checks (render_pass.h pass_bwd_check), the PassBwdDev they start from
+// (w_floats: where the bias tiles follow the stream; D-NeRF members null, out_ch 4) and the launch.
 static PassBwdDev pass_bwd_dev(const float* packed_bwd, size_t w_floats, const float* bits, const float* raw, const float* z_vals,
                                const float* ray_batch, int cols, const float* noise, int64_t n_rays, int n_samples, int white_bkgd,
                                const float* g_rgb, const float* g_disp, const float* g_acc, const float* g_raw, float* grad, float* d_raw) {
@@ -493,7 +356,7 @@ static PassBwdDev pass_bwd_dev(const float* packed_bwd, size_t w_floats, const f
 
 template <int MODE>
 static int pass_bwd_launch(const char* what, const PassBwdDev& P, int bias_tiles, void* stream) {
-    const size_t lds = (bias_tiles * SW_BIAS_TILE_FLOATS + 4 * SW_LDS_RING_FLOATS + 4 * PB_WAVE_FLOATS) * sizeof(float);
+    const size_t lds = (bias_tiles * SW_BIAS_TILE_FLOATS + 4 * SW_LDS_RING_FLOATS + 4 * SW_BWD_COMP_FLOATS) * sizeof(float);
     hipLaunchKernelGGL(render_pass_backward_kernel<MODE>, dim3((unsigned)((P.n_rays + 3) / 4)), dim3(256), lds, (hipStream_t)stream, P);
     return sw_check(hipGetLastError(), what);
 }
@@ -529,7 +392,7 @@ extern "C" int swnerf_render_pass_backward_noview(const float* packed_bwd, const
 extern "C" int swnerf_render_pass_train_dnerf(const swnerf_pass_args* args, float* act, float* bits, float* xs,
                                               float* act_d, float* bits_d, float* xs_d, void* stream) {
     static const PassAccepts accepts = {"render_pass_train_dnerf", {0, SW_COLS(12), 0, 0}, SWNERF_E_UNSUPP,
-        "%s: DirectTemporalNeRF with the deformation pass (t != 0) and a 12-column ray batch", true, PB_SMAX};
+        "%s: DirectTemporalNeRF with the deformation pass (t != 0) and a 12-column ray batch", true, SW_BWD_SMAX};
     if (!args) return sw_fail(SWNERF_E_ARG, "render_pass_train_dnerf: NULL args");
     const swnerf_pass_args& a = *args;
     if (a.n_rays == 0 && a.packed) return 0;
