@@ -18,6 +18,7 @@ from .ray import get_rays, sample_pdf, raw2outputs
 from .embedder import EmbedFn, to8b
 from .png import write_png
 from .model import vallina_NeRF, NeRFOriginal, DirectTemporalNeRF
+from .train_pass import fused_train_pass, TRAIN_FUSED_MAX_SAMPLES   # noqa: F401  (the limit stays importable from here)
 
 DEBUG = False
 PASS_HOOK = None     # bench.py: callable(phase, n_rays, n_samples) with phase in {"begin", "end"} around each launch
@@ -254,117 +255,11 @@ def render_pass(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand
     return out
 
 
-def chunked_backward(rb, act_rows, div, widths, launch, gemm_jobs, rest_on_main=True):
-    """The backward of a fused training pass, per CHUNK of rays.  The gradient buffer [rows, 2432] is as large as the saved
-    activations; the dX chain and the GEMMs that consume it run per chunk, so only one chunk of it is ever alive (GEMMs
-    accumulate: C += A^T.B).  A chunk is TRAIN_BWD_CHUNK_ROWS // div rows (393 216 at the C2 shape: large enough for the
-    split-K GEMMs to fill the chip), whole rays, a multiple of 4.  widths: columns of the buffers a chunk holds;
-    launch(r0, r1, bufs) runs the backward kernel on rays r0:r1; gemm_jobs(a0, a1, m, bufs) -> the jobs of wgrad._chunk_gemms
-    on the rows a0:a1 of the saved tensors (m = a1 - a0 rows of every buffer), which fan out over side streams (wgrad._Fan)."""
-    from .wgrad import _Fan, _chunk_gemms
-    N = rb.shape[0]
-    rows_per_ray = act_rows // N
-    chunk = max(4, (TRAIN_BWD_CHUNK_ROWS // div // rows_per_ray) // 4 * 4)
-    bufs = [torch.empty((min(N, chunk) * rows_per_ray, w), dtype=torch.float32, device=rb.device) for w in widths]
-    fan = _Fan(rb.device)
-    for r0 in range(0, N, chunk):
-        r1 = min(N, r0 + chunk)
-        launch(r0, r1, bufs)
-        _chunk_gemms(_lib.lib(), fan, (r1 - r0) * rows_per_ray, gemm_jobs(r0 * rows_per_ray, r1 * rows_per_ray, (r1 - r0) * rows_per_ray, bufs),
-                     rest_on_main=rest_on_main)
-
-
-def f32_grads(*gs):
-    """Upstream gradients as the kernels read them (an output the loss does not use arrives as None and stays None)."""
-    return [None if g is None else g.contiguous().float() for g in gs]
-
-
-def ray_ptrs(r0, r1, *ts, per_ray=1):
-    """Pointers to the rows of rays r0:r1 of each tensor (None stays NULL)."""
-    return [_lib.ptr(None if t is None else t[r0 * per_ray:r1 * per_ray]) for t in ts]
-
-
-class _FusedPassTrain(torch.autograd.Function):
-    """The fused render pass under autograd (the reference's step is render -> img2mse ->
-    loss.backward(), nerf/run.py:684-708).  forward = swnerf_render_pass_train: the inference pass that also saves
-    activations, ReLU masks, the encodings and raw; backward = swnerf_render_pass_backward (one wave per ray: compositing
-    backward in LDS, then the dX chain per tile) + one TN MFMA GEMM per Linear layer.  No [M,90] embedding, no cat, no
-    pts tensor ever reaches HBM.  Gradients flow to the net's parameters only (rays are data; the depths of the fine
-    pass are detached in the reference, nerf/run.py:398)."""
-
-    @staticmethod
-    def forward(ctx, net, rb, z_vals, S, lindisp, t_rand, noise, white_bkgd, n_importance, u, *params):
-        noview = net._noview_params() is not None              # use_viewdirs=False: 8-column rays, raw [N,S,out_ch]
-        out_ch = 4
-        if noview:
-            packed, Lp, out_ch = net.packed_noview()
-            kind, Ld = _lib.NET_NOVIEW, 0
-        else:
-            kind, packed, Lp, Ld, _ = net.packed()
-        L = _lib.lib()
-        N = rb.shape[0]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
-        rows = L.swnerf_train_rows(N, S)
-        act, bits, xs = new(rows, L.swnerf_act_floats_per_row()), new(L.swnerf_mask_floats(rows)), new(rows, L.swnerf_xs_floats_per_row())
-        a, o, _keep = pass_args(rb, kind, packed, (Lp, Ld, 0), S, out_ch, 0, dict(z_vals=z_vals, t_rand=t_rand, noise=noise, u=u),
-                                ["rgb_map", "disp_map", "acc_map", "raw"] + ([] if z_vals is not None else ["z_out"]), n_importance,
-                                lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_train")
-        z = z_vals if z_vals is not None else o["z_out"]
-        z_fine, z_std = (o["z_fine"], o["z_std"]) if n_importance > 0 else (new(0), new(0))
-        if PASS_HOOK is not None:
-            PASS_HOOK("begin", N, S)
-        _lib.check(L.swnerf_render_pass_train(a, _lib.ptr(act), _lib.ptr(bits), _lib.ptr(xs), _lib.stream_of(rb)), "render_pass_train")
-        if PASS_HOOK is not None:
-            PASS_HOOK("end", N, S)
-        ctx.net, ctx.S, ctx.white, ctx.bands = net, S, bool(white_bkgd), (Lp, Ld)
-        ctx.has_noise, ctx.noview, ctx.out_ch = noise is not None, noview, out_ch
-        ctx.save_for_backward(rb, z, o["raw"], act, bits, xs, noise if noise is not None else new(0), *params)
-        ctx.mark_non_differentiable(z_fine, z_std)
-        ctx.set_materialize_grads(False)       # an output the loss does not use arrives as None (no zero fill, no read of zeros in the kernel)
-        # raw is an output as well (retraw=True is what the reference's train() passes, nerf/run.py:685): a gradient
-        # arriving on it is added to d raw in the backward kernel
-        return o["rgb_map"], o["disp_map"], o["acc_map"], z_fine, z_std, o["raw"]
-
-    @staticmethod
-    def backward(ctx, *grads_out):
-        from .wgrad import WeightGrads
-        rb, z, raw, act, bits, xs, noise, *params = ctx.saved_tensors
-        net, S, nv = ctx.net, ctx.S, ctx.noview
-        Lp, Ld = ctx.bands
-        L = _lib.lib()
-        N, cols = rb.shape
-        st = _lib.stream_of(rb)
-        g_rgb, g_disp, g_acc, _gz, _gs, g_raw = f32_grads(*grads_out)
-        wg = WeightGrads(L, "noview" if nv else "canon", params, fused=True, Cpos=net.input_ch, Cdir=0 if nv else net.input_ch_views, bands=(Lp, Ld, 0))
-        packed_bwd = net.packed_bwd_noview() if nv else net.packed_bwd()
-        fn, what = (L.swnerf_render_pass_backward_noview, "render_pass_backward_noview") if nv else (L.swnerf_render_pass_backward, "render_pass_backward")
-
-        def launch(r0, r1, bufs):
-            _lib.check(fn(_lib.ptr(packed_bwd), *ray_ptrs(r0, r1, bits, per_ray=bits.numel() // N), *ray_ptrs(r0, r1, raw, z, rb), cols,
-                          *ray_ptrs(r0, r1, noise if ctx.has_noise else None), r1 - r0, S, int(ctx.white), *([ctx.out_ch] if nv else []),
-                          *ray_ptrs(r0, r1, g_rgb, g_disp, g_acc, g_raw), _lib.ptr(bufs[0]), _lib.ptr(bufs[1]), st), what)
-
-        jobs = lambda a0, a1, m, bufs: [lambda st_, part: wg.chunk(st_, m, bufs[0][:m], act[a0:a1], xs[a0:a1], bufs[1][:m], part=part)]
-        chunked_backward(rb, act.shape[0], 1, (act.shape[1], 8 if nv else 4), launch, jobs, rest_on_main=not nv)   # (the no-view net has no fused narrow kernel)
-        return (None,) * 10 + tuple(gi.to(p.dtype) for gi, p in zip(wg.finish(st), params))
-
-
 def render_pass_train(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand=None, noise=None, white_bkgd=False,
                       n_importance=0, u=None):
-    """One differentiable fused pass (`_FusedPassTrain`): dict with rgb_map disp_map acc_map raw (+ z_fine z_std)."""
-    from .model import _CANON_ORDER, _NOVIEW_ORDER
-    rb = _lib.dev_f32(ray_batch.detach(), "ray_batch")
-    S = int(n_samples)
-    chk = lambda t, name, last: None if t is None else _lib.dev_f32(t.detach(), name, last)
-    z_vals, t_rand, noise, u = chk(z_vals, "z_vals", S), chk(t_rand, "t_rand", S), chk(noise, "noise", S), chk(u, "u", int(n_importance))
-    sd = dict(net.named_parameters())
-    rgb, disp, acc, z_fine, z_std, raw = _FusedPassTrain.apply(net, rb, z_vals, S, bool(lindisp), t_rand, noise, bool(white_bkgd),
-                                                               int(n_importance), u,
-                                                               *[sd[n] for n in (_NOVIEW_ORDER if net._noview_params() is not None else _CANON_ORDER)])
-    out = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "raw": raw}
-    if n_importance > 0:
-        out["z_fine"], out["z_std"] = z_fine, z_std
-    return out
+    """One differentiable fused pass of a static net (train_pass.fused_train_pass): dict with rgb_map disp_map acc_map raw (+ z_fine z_std)."""
+    return fused_train_pass("noview" if net._noview_params() is not None else "canon", ray_batch, net, n_samples, z_vals=z_vals, lindisp=lindisp,
+                            t_rand=t_rand, noise=noise, white_bkgd=white_bkgd, n_importance=n_importance, u=u)
 
 
 PASS_MAX_COARSE, PASS_MAX_SORT = 256, 1024   # csrc/render_pass.h SW_LDS_SC / SW_LDS_SORT: the in-LDS resampling of swnerf_render_pass
@@ -399,7 +294,6 @@ def coarse_pass_resampled(ray_batch, net, N_samples, N_importance, *, want, u=No
     return p0
 
 
-TRAIN_FUSED_MAX_SAMPLES = 256      # include/swnerf.h: swnerf_render_pass_train
 # rows of the gradient buffer alive at once in the fused backward (393 216 rows = 3.8 GB); each chunk costs a backward-kernel
 # tail, one grouped GEMM launch and the narrow GEMMs' tail, so not smaller than needed
 TRAIN_BWD_CHUNK_ROWS = int(os.environ.get("SWNERF_TRAIN_BWD_CHUNK_ROWS", "393216"))

@@ -11,9 +11,9 @@ from . import _lib
 from .embedder import to8b
 from .png import write_png
 from .ray import get_rays, sample_pdf, raw2outputs
-from .render import (fused_plan, render_pass, render_pass_train, pack_ray_batch, _rng_inputs, _coarse_z, coarse_pass_resampled,
-                     pipelined_frames, sample_coarse, wants_grad, result_dict, batchify_rays_with, image_outputs, pass_args,
-                     chunked_backward, f32_grads, ray_ptrs, TRAIN_FUSED_MAX_SAMPLES)
+from .render import (fused_plan, render_pass, pack_ray_batch, _rng_inputs, _coarse_z, coarse_pass_resampled, pipelined_frames,
+                     sample_coarse, wants_grad, result_dict, batchify_rays_with, image_outputs)
+from .train_pass import fused_train_pass, TRAIN_FUSED_MAX_SAMPLES
 from .model import DirectTemporalNeRF, NeRFOriginal
 
 DEBUG = False
@@ -81,86 +81,9 @@ def runs_deform(net, t0):
     return isinstance(net, DirectTemporalNeRF) and not (t0 == 0. and net.zero_canonical)
 
 
-class _FusedPassTrainDnerf(torch.autograd.Function):
-    """The fused D-NeRF pass under autograd (DirectTemporalNeRF at t != 0, model.py:128-151; the loss of
-    d_nerf/run_dnerf.py:690-725 puts gradients on the image and on position_delta).  forward =
-    swnerf_render_pass_train_dnerf: deformation net -> x + dx -> canonical net -> compositing in one kernel, saving both
-    nets' activations / masks / encodings as side stores; backward = swnerf_render_pass_backward_dnerf: per ray the
-    compositing backward, then per tile the canonical dX chain incl. d gamma(x+dx) -> d(x+dx) through the sin/cos
-    Jacobian, + the upstream gradient of position_delta, then the deformation net's dX chain - ONE weight ring over both
-    transposed streams; then one TN GEMM per Linear layer of both nets."""
-
-    @staticmethod
-    def forward(ctx, net, rb, z_vals, S, lindisp, t_rand, noise, white_bkgd, *params):
-        kind, packed, Lp, Ld, Lt = net.packed()
-        L = _lib.lib()
-        N = rb.shape[0]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
-        rows = L.swnerf_train_rows(N, S)
-        nact, nxs, nbits = L.swnerf_act_floats_per_row(), L.swnerf_xs_floats_per_row(), L.swnerf_mask_floats(rows)
-        act, bits, xs = new(rows, nact), new(nbits), new(rows, nxs)
-        act_d, bits_d, xs_d = new(rows, nact), new(nbits), new(rows, nxs)
-        a, o, _keep = pass_args(rb, kind, packed, (Lp, Ld, Lt), S, 4, 1, dict(z_vals=z_vals, t_rand=t_rand, noise=noise),
-                                ["rgb_map", "disp_map", "acc_map", "raw", "dx"] + ([] if z_vals is not None else ["z_out"]),
-                                lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_train_dnerf")
-        z = z_vals if z_vals is not None else o["z_out"]
-        _lib.check(L.swnerf_render_pass_train_dnerf(a, _lib.ptr(act), _lib.ptr(bits), _lib.ptr(xs), _lib.ptr(act_d), _lib.ptr(bits_d),
-                                                    _lib.ptr(xs_d), _lib.stream_of(rb)), "render_pass_train_dnerf")
-        ctx.net, ctx.S, ctx.white, ctx.bands = net, S, bool(white_bkgd), (Lp, Ld, Lt)
-        ctx.has_noise = noise is not None
-        ctx.save_for_backward(rb, z, o["raw"], o["dx"], act, bits, xs, act_d, bits_d, xs_d, noise if noise is not None else new(0), *params)
-        ctx.mark_non_differentiable(z)
-        ctx.set_materialize_grads(False)       # an output the loss does not use arrives as None (no zero fill, no read of zeros in the kernel)
-        return o["rgb_map"], o["disp_map"], o["acc_map"], o["dx"], z, o["raw"]
-
-    @staticmethod
-    def backward(ctx, *grads_out):
-        from .wgrad import WeightGrads
-        rb, z, raw, dx, act, bits, xs, act_d, bits_d, xs_d, noise, *params = ctx.saved_tensors
-        net, S = ctx.net, ctx.S
-        Lp, Ld, Lt = ctx.bands
-        L = _lib.lib()
-        N, cols = rb.shape
-        st = _lib.stream_of(rb)
-        g_rgb, g_disp, g_acc, g_dx_up, _gz, g_raw = f32_grads(*grads_out)
-        Cpos, Cdir = net.input_ch, net.input_ch_views
-        wc = WeightGrads(L, "canon", params[:24], fused=True, Cpos=Cpos, Cdir=Cdir, bands=(Lp, Ld, Lt))       # the 24 `_occ` tensors
-        wd = WeightGrads(L, "deform", params[24:], fused=True, Cpos=Cpos, bands=(Lp, Ld, Lt))                 # the 18 `_time` / `_time_out`
-        packed_bwd = net.packed_bwd(_lib.BWD_DNERF_FUSED)
-
-        def launch(r0, r1, bufs):
-            grad, grad_d, d_raw, g_dx = bufs
-            _lib.check(L.swnerf_render_pass_backward_dnerf(
-                _lib.ptr(packed_bwd), *ray_ptrs(r0, r1, bits, bits_d, per_ray=bits.numel() // N), *ray_ptrs(r0, r1, raw, z, rb), cols,
-                *ray_ptrs(r0, r1, noise if ctx.has_noise else None, dx, g_dx_up), r1 - r0, S, int(ctx.white), Lp,
-                *ray_ptrs(r0, r1, g_rgb, g_disp, g_acc, g_raw), _lib.ptr(grad), _lib.ptr(grad_d), _lib.ptr(d_raw), _lib.ptr(g_dx), st),
-                "render_pass_backward_dnerf")
-
-        def jobs(a0, a1, m, bufs):
-            grad, grad_d, d_raw, g_dx = bufs
-            return [lambda st_, part: wc.chunk(st_, m, grad[:m], act[a0:a1], xs[a0:a1], d_raw[:m], part=part),
-                    lambda st_, part: wd.chunk(st_, m, grad_d[:m], act_d[a0:a1], xs_d[a0:a1], g_dx[:m], part=part)]
-
-        # two gradient buffers (canonical + deformation net) per chunk: half of TRAIN_BWD_CHUNK_ROWS rows each, so that a chunk
-        # holds the 3.8 GB the static backward's chunk does; the GEMMs of a chunk fan out over side streams (wgrad._Fan), which
-        # hides most of what an extra chunk used to cost (one atomic epilogue per GEMM).  Round 2 held the whole fine pass in
-        # one chunk: 15 GB of gradients, 29.6 GiB peak for a 4096-ray step.
-        chunked_backward(rb, act.shape[0], DNERF_CHUNK_DIV, (act.shape[1], act.shape[1], 4, 4), launch, jobs)
-        g = wc.finish(st) + wd.finish(st)
-        return (None,) * 8 + tuple(gi.to(p.dtype) for gi, p in zip(g, params))
-
-
 def _render_pass_train_dnerf(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand=None, noise=None, white_bkgd=False):
-    """One differentiable fused D-NeRF pass: dict with rgb_map disp_map acc_map dx z raw."""
-    rb = _lib.dev_f32(ray_batch.detach(), "ray_batch")
-    N, S = rb.shape[0], int(n_samples)
-    chk = lambda t, name: None if t is None else _lib.dev_f32(t.detach(), name, S)
-    z_vals, t_rand, noise = chk(z_vals, "z_vals"), chk(t_rand, "t_rand"), chk(noise, "noise")
-    kind, names, Lp, Ld, Lt = net._pack_params()
-    sd = dict(net.named_parameters())
-    rgb, disp, acc, dx, z, raw = _FusedPassTrainDnerf.apply(net, rb, z_vals, S, bool(lindisp), t_rand, noise, bool(white_bkgd),
-                                                           *[sd[n] for n in names])
-    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "dx": dx, "z": z, "raw": raw}
+    """One differentiable fused D-NeRF pass (train_pass.fused_train_pass): dict with rgb_map disp_map acc_map dx z raw."""
+    return fused_train_pass("dnerf", ray_batch, net, n_samples, z_vals=z_vals, lindisp=lindisp, t_rand=t_rand, noise=noise, white_bkgd=white_bkgd)
 
 
 def _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples, retraw, lindisp, perturb, N_importance,
@@ -186,11 +109,12 @@ def _render_rays_train_fused(ray_batch, network_fn, network_query_fn, N_samples,
 
     def train_pass(net, S, z_in, tr, nz):
         """-> (dict with rgb_map disp_map acc_map raw, depths, position_delta) of one differentiable pass of `net`"""
-        if runs_deform(net, t0):
-            p = _render_pass_train_dnerf(ray_batch, net, S, z_vals=z_in, lindisp=lindisp, t_rand=tr, noise=nz, white_bkgd=white_bkgd)
+        deform = runs_deform(net, t0)                            # else the static pass on the canonical net, position_delta = 0
+        run = net._occ if isinstance(net, DirectTemporalNeRF) and not deform else net
+        p = fused_train_pass("dnerf" if deform else "canon", ray_batch, run, S, z_vals=z_in, lindisp=lindisp, t_rand=tr, noise=nz,
+                             white_bkgd=white_bkgd)
+        if deform:
             return p, p["z"], p["dx"]
-        canon = net._occ if isinstance(net, DirectTemporalNeRF) else net
-        p = render_pass_train(ray_batch, canon, S, z_vals=z_in, lindisp=lindisp, t_rand=tr, noise=nz, white_bkgd=white_bkgd)
         if z_in is None:
             with torch.no_grad():
                 z_in = sample_coarse(ray_batch.detach(), S, lindisp, tr)

@@ -4,7 +4,7 @@ run_network, batchify_rays, render, render_path and render_rays with the referen
 render_rays takes the fused T-NeRF pass (csrc/tnerf_kernels.hip: one wave per ray, the 8 x 128 ELU net in registers,
 compositing in the same kernel) when `tnerf_plan` holds: no grad, a GPU TNeRF of depth 8 / width 128 / skip 4, the
 closure's standard encoders with matching sizes, and embd_time_discr.  It keeps run_network's one-time-per-batch assertion.
-Under grad with `fused_train=True` (opt-in) and 2 <= S <= 256 it takes the fused training pass instead (`_FusedPassTrainTnerf`,
+Under grad with `fused_train=True` (opt-in) and 2 <= S <= 256 it takes the fused training pass instead (train_pass.py kind "tnerf",
 csrc/tnerf_train_kernels.hip: the same forward that also saves activations, a one-wave-per-ray backward, TN GEMMs for dW).
 Otherwise it takes the differentiable op path: the HIP sampling op,
 `network_query_fn` (embedders + TNeRF.forward on the generic GEMMs with ELU) and the raw2outputs op with its backward.
@@ -22,8 +22,8 @@ from . import _lib
 from .embedder import to8b, EmbedFn
 from .png import write_png
 from .ray import get_rays, ndc_rays, raw2outputs
-from .render import (closure_embedders, wants_grad, sample_coarse, pass_args, result_dict, batchify_rays_with, image_outputs,
-                     chunked_backward, f32_grads, ray_ptrs, TRAIN_FUSED_MAX_SAMPLES)
+from .render import closure_embedders, wants_grad, sample_coarse, pass_args, result_dict, batchify_rays_with, image_outputs
+from .train_pass import fused_train_pass, TRAIN_FUSED_MAX_SAMPLES
 from .model import TNeRF
 
 DEBUG = False
@@ -119,67 +119,9 @@ def render_pass_tnerf(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, 
     return out
 
 
-class _FusedPassTrainTnerf(torch.autograd.Function):
-    """The fused T-NeRF pass under autograd (the step of t_nerf/run_tnerf.py:680-720: render -> img2mse -> loss.backward()).
-    forward = swnerf_render_pass_train_tnerf: the inference pass, bit for bit, that also saves the post-ELU activations and the
-    encodings; backward = swnerf_render_pass_backward_tnerf (one wave per ray: compositing backward in LDS, then the dX chain
-    per tile with ELU' from the saved activations) + one TN GEMM per weight block (wgrad.WeightGrads kind "tnerf"; `feature` is
-    un-folded from G in swnerf_tnerf_feature_finish).  Gradients flow to the net's parameters only (rays are data)."""
-
-    @staticmethod
-    def forward(ctx, net, rb, z_vals, S, lindisp, t_rand, noise, white_bkgd, *params):
-        kind, packed, Lp, Ld, Lt = net.packed()
-        L = _lib.lib()
-        N = rb.shape[0]
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rb.device)
-        rows = L.swnerf_train_rows(N, S)
-        act, xs = new(rows, L.swnerf_tnerf_act_floats_per_row()), new(rows, L.swnerf_tnerf_xs_floats_per_row())
-        a, o, _keep = pass_args(rb, kind, packed, (Lp, Ld, Lt), S, 4, 0, dict(z_vals=z_vals, t_rand=t_rand, noise=noise),
-                                ["rgb_map", "disp_map", "acc_map", "raw"] + ([] if z_vals is not None else ["z_out"]),
-                                lindisp=lindisp, white_bkgd=white_bkgd, who="render_pass_train_tnerf")
-        z = z_vals if z_vals is not None else o["z_out"]
-        _lib.check(L.swnerf_render_pass_train_tnerf(a, _lib.ptr(act), _lib.ptr(xs), _lib.stream_of(rb)), "render_pass_train_tnerf")
-        ctx.net, ctx.S, ctx.white, ctx.bands = net, S, bool(white_bkgd), (Lp, Ld, Lt)
-        ctx.has_noise = noise is not None
-        ctx.save_for_backward(rb, z, o["raw"], act, xs, noise if noise is not None else new(0), *params)
-        ctx.mark_non_differentiable(z)
-        ctx.set_materialize_grads(False)       # an output the loss does not use arrives as None (no zero fill, no read of zeros in the kernel)
-        return o["rgb_map"], o["disp_map"], o["acc_map"], z, o["raw"]
-
-    @staticmethod
-    def backward(ctx, *grads_out):
-        from .wgrad import WeightGrads
-        rb, z, raw, act, xs, noise, *params = ctx.saved_tensors
-        net, S = ctx.net, ctx.S
-        L = _lib.lib()
-        N, cols = rb.shape
-        st = _lib.stream_of(rb)
-        g_rgb, g_disp, g_acc, _gz, g_raw = f32_grads(*grads_out)
-        wg = WeightGrads(L, "tnerf", params, fused=True, Cpos=net.in_feat, Cdir=net.dir_feat, Ct=net.time_feat, bands=ctx.bands)
-        packed_bwd = net.packed_bwd()
-
-        def launch(r0, r1, bufs):
-            _lib.check(L.swnerf_render_pass_backward_tnerf(
-                _lib.ptr(packed_bwd), *ray_ptrs(r0, r1, act, per_ray=act.shape[0] // N), *ray_ptrs(r0, r1, raw, z, rb), cols,
-                *ray_ptrs(r0, r1, noise if ctx.has_noise else None), r1 - r0, S, int(ctx.white),
-                *ray_ptrs(r0, r1, g_rgb, g_disp, g_acc, g_raw), _lib.ptr(bufs[0]), _lib.ptr(bufs[1]), st), "render_pass_backward_tnerf")
-
-        jobs = lambda a0, a1, m, bufs: [lambda st_, part: wg.chunk(st_, m, bufs[0][:m], act[a0:a1], xs[a0:a1], bufs[1][:m], part=part)]
-        chunked_backward(rb, act.shape[0], 1, (act.shape[1], 4), launch, jobs, rest_on_main=False)
-        return (None,) * 8 + tuple(gi.to(p.dtype) for gi, p in zip(wg.finish(st), params))
-
-
 def render_pass_train_tnerf(ray_batch, net, n_samples, *, z_vals=None, lindisp=False, t_rand=None, noise=None, white_bkgd=False):
-    """One differentiable fused T-NeRF pass (`_FusedPassTrainTnerf`): dict with rgb_map disp_map acc_map raw z."""
-    from .model import _TNERF_ORDER
-    rb = _lib.dev_f32(ray_batch.detach(), "ray_batch", 12)
-    S = int(n_samples)
-    chk = lambda t, name: None if t is None else _lib.dev_f32(t.detach(), name, S)
-    z_vals, t_rand, noise = chk(z_vals, "z_vals"), chk(t_rand, "t_rand"), chk(noise, "noise")
-    sd = dict(net.named_parameters())
-    rgb, disp, acc, z, raw = _FusedPassTrainTnerf.apply(net, rb, z_vals, S, bool(lindisp), t_rand, noise, bool(white_bkgd),
-                                                        *[sd[n] for n in _TNERF_ORDER])
-    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "raw": raw, "z": z}
+    """One differentiable fused T-NeRF pass (train_pass.fused_train_pass): dict with rgb_map disp_map acc_map raw z."""
+    return fused_train_pass("tnerf", ray_batch, net, n_samples, z_vals=z_vals, lindisp=lindisp, t_rand=t_rand, noise=noise, white_bkgd=white_bkgd)
 
 
 def _rng(N, S, perturb, raw_noise_std, pytest, dev, need_t_rand):
